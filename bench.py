@@ -25,10 +25,13 @@ region-growing round (ncclSend/Recv + a 4-byte all-reduce, one enqueue-only call
 Launch: under torchrun (RANK / WORLD_SIZE / LOCAL_RANK in the environment) or plainly `python bench.py --gpus N`,
 which then starts the N ranks itself; fewer than N visible GPUs is an error, never a silent N=1.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel family of the step, measured live with HIP
-events on the stream the kernels run on; `cpu_baseline` is the CPU oracle (a C/numpy restatement of the reference:
-"port") timed on the SAME volume on this box's host cores; its outputs double as the full-size parity gate
-(`parity`: region voxels, triangle count and a CRC of the whole mask must equal the oracle's).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the line (`value`,
+`ms_per_step`; `roofline` of the region growing, whose HIP events are recorded inside the timed steps).  `--full` adds
+everything else: the per-stage table and per-stage roofline from extra steps after the timed region, the measured copy
+bandwidth, the end-to-end passes, `cpu_baseline` -- the CPU oracle (a C/numpy restatement of the reference: "port") timed
+on the SAME volume on the host cores, its outputs doubling as the full-size parity gate (`parity`: region voxels,
+triangle count and a CRC of the whole mask must equal the oracle's) -- `other_configs` and, at N > 1, `strong_scaling`.
+`--dump-outputs DIR` writes what the last timed step computed (rank 0) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -325,6 +328,32 @@ def copy_bandwidth(vol, nvox):
     return 4.0 * nvox / (copy_ms * 1e-3) / 1e9
 
 
+DUMP_MASK_SAMPLE = 4_000_000  # voxels (float32: 16 MB)
+DUMP_TRI_SAMPLE = 500_000  # triangles (3 x 3 float32: 18 MB)
+
+
+def _seeded_rows(a, k, seed):
+    """a fixed, seeded sample of k of a's rows in their own order (the same rows for the same length), or all of them"""
+    if len(a) <= k:
+        return a
+    return a[np.unique(np.random.default_rng(seed).integers(0, len(a), k))]
+
+
+def dump_grow_mc(path, vol, reached, ntri):
+    """--dump-outputs: what a caller of the step receives, from the last timed step -- the uint8 mask (255 threshold / 254
+    region) and the float32 triangle soup -- as float32 samples, plus float64 summaries of the whole outputs"""
+    os.makedirs(path, exist_ok=True)
+    mask = vol.download_mask()
+    tris = vol._tris.download((ntri, 3, 3), np.float32) if ntri else np.zeros((0, 3, 3), np.float32)
+    out = {"mask_sample": _seeded_rows(mask.reshape(-1), DUMP_MASK_SAMPLE, SEED).astype(np.float32),
+           "mask_slice_sums": mask.reshape(mask.shape[0], -1).sum(axis=1, dtype=np.int64).astype(np.float64),
+           "triangles_sample": _seeded_rows(tris, DUMP_TRI_SAMPLE, SEED + 1),
+           "triangle_sums": tris.reshape(-1, 9).sum(axis=0, dtype=np.float64),
+           "counts": np.array([reached, ntri], np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def roofline(kernel, nbytes, ms, traffic, copy_gbs, extra=None):
     achieved = nbytes / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
     r = {"bound": "hbm", "kernel": kernel, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -438,24 +467,29 @@ def run_grow_mc(args, job):
     dt = time.perf_counter() - t0
     spans_timed = vol.timer.collect()
     vol.timer.only = None
-    step()  # the sequential path's own one-time work (its triangle-list workspace) stays out of the table
-    barrier()
-    vol.timer.collect()
-    n_extra = max(1, min(args.steps, 5))
-    for _ in range(n_extra):
-        step()
-    barrier()
-    spans = vol.timer.collect()
-    # N > 1: device time of the collectives per step (HIP events around every ivx_comm_* call of the bracketed steps), so that
-    # the 1 -> 8 curve arrives with its communication share attached
-    comm_ms = {k[5:]: {"ms_per_step": round(float(np.sum(v)) / n_extra, 4), "calls_per_step": round(len(v) / n_extra, 2)}
-               for k, v in spans.items() if k.startswith("comm_")}
+    if args.dump_outputs and rank == 0:
+        dump_grow_mc(args.dump_outputs, vol, vol.reached_count(), ntri)
+    full = getattr(args, "full", True)
+    spans, comm_ms = {}, {}
+    if full:
+        step()  # the sequential path's own one-time work (its triangle-list workspace) stays out of the table
+        barrier()
+        vol.timer.collect()
+        n_extra = max(1, min(args.steps, 5))
+        for _ in range(n_extra):
+            step()
+        barrier()
+        spans = vol.timer.collect()
+        # N > 1: device time of the collectives per step (HIP events around every ivx_comm_* call of the bracketed steps), so that
+        # the 1 -> 8 curve arrives with its communication share attached
+        comm_ms = {k[5:]: {"ms_per_step": round(float(np.sum(v)) / n_extra, 4), "calls_per_step": round(len(v) / n_extra, 2)}
+                   for k, v in spans.items() if k.startswith("comm_")}
     spans["region_grow"] = spans_timed.get("region_grow", spans.get("region_grow", []))
     reached = vol.reached_count()
-    copy_gbs = copy_bandwidth(vol, nvox) if rank == 0 else None
+    copy_gbs = copy_bandwidth(vol, nvox) if rank == 0 and full else None
     # one step the way a caller without a resident volume pays for it: host -> HBM, the step, mask + triangles -> host
     e2e_ms = e2e_first_ms = None
-    e2e = world == 1 and not force_slab and not hbm
+    e2e = full and world == 1 and not force_slab and not hbm
     mask_crc = ntri_dl = None
     if e2e:
         for k in range(2):  # the first pass also pays the process's first pageable copies (page locking set-up, lane buffers)
@@ -489,7 +523,7 @@ def run_grow_mc(args, job):
         del p_img, p_mask, p_tris, m2, t2
     dt = job.max(dt)
     ntri_all, reached_all = job.sum(ntri), job.sum(reached)
-    if world == 1 and not force_slab and not e2e:  # (the HBM-made volume: the parity gate's mask CRC without the end-to-end passes)
+    if args.cpu and world == 1 and not force_slab and not e2e:  # (the HBM-made volume: the parity gate's mask CRC without the end-to-end passes)
         mask_crc, ntri_dl = zlib.crc32(vol.download_mask()), ntri
     if rank != 0:
         return None
@@ -523,7 +557,8 @@ def run_grow_mc(args, job):
         if len(spans.get("region_grow", [])) else None,
         "timed_region_s": round(dt, 6),
         "stage_ms_source": "region_grow: HIP events inside the timed steps; other stages: HIP events in up to 5 extra steps "
-                           "after the timed region, one stage after the other (every recorded event idles the stream for ~4 us)",
+                           "after the timed region, one stage after the other (every recorded event idles the stream for ~4 us)"
+                           if full else "region_grow: HIP events inside the timed steps (the other stages: --full)",
         "stage_mvoxel_per_s": {k: round(nvox / (v * 1e-3) / 1e6, 1) for k, v in stage_time.items() if v > 0},
         "end_to_end_ms": round(e2e_ms, 2) if e2e_ms else None,
         "end_to_end_first_call_ms": round(e2e_first_ms, 2) if e2e_first_ms else None,
@@ -532,7 +567,7 @@ def run_grow_mc(args, job):
                            "`end_to_end_ms` with pageable numpy arrays (results into fresh np.empty arrays; second pass -- "
                            "`end_to_end_first_call_ms` is the first, which also sets up the process's page-locking and lane buffers), "
                            "`end_to_end_pinned_ms` with the caller's three arrays in page-locked memory (_lib.pinned_empty); first upload "
-                           "at start-up took %.1f ms" % upload_ms,
+                           "at start-up took %.1f ms" % upload_ms if full else None,
         "roofline": roofline(dom, stage_bytes[dom], stage_time[dom], traffic, copy_gbs,
                              {"per_stage_frac": {k: round(stage_bytes[k] / (stage_time[k] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
                                                  for k in stage_time if stage_time[k] > 0}}),
@@ -1397,6 +1432,7 @@ def other_configs(args, job, runners):
             continue
         a = copy.copy(args)
         a.config, a.size, a.steps, a.warmup, a.ws_raw, a.bounded, a.hbm_synth, a.scaling = cfg, size, steps, warmup, False, True, hbm, "weak"
+        a.dump_outputs = None
         t = time.perf_counter()
         try:
             with contextlib.redirect_stdout(sys.stderr):  # (a failing gate prints its own record: keep stdout to ONE line)
@@ -1431,10 +1467,16 @@ def main():
                     "(--size 1024 in seconds); the CPU oracle then runs on the downloaded volume")
     ap.add_argument("--size", type=int, default=None, help="edge of the volume (defaults: 512 / 1024 / 512 per GPU; 2048 in total for sharded2048)")
     ap.add_argument("--ws-raw", action="store_true", help="watershed_sk: the image - image.min() branch instead of the GUI's default window/level")
-    ap.add_argument("--no-cpu", dest="cpu", action="store_false", help="skip the CPU baseline + full-size parity check")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline figure: CPU baseline + full-size parity, the per-stage table, copy bandwidth and end-to-end "
+                         "passes, `other_configs` and (N > 1) `strong_scaling`; a plain run does none of these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy, float32 / float64, "
+                         "a fixed seeded sample where the output is large")
+    ap.add_argument("--no-cpu", dest="cpu", action="store_false", help="with --full: skip the CPU baseline + full-size parity check")
     ap.add_argument("--no-others", dest="others", action="store_false",
-                    help="default config only: do not run configs[2] (both branches, 512^3), configs[4] and configs[3] (one GPU) once each "
-                         "after the headline's timed region (`other_configs` of the JSON line)")
+                    help="with --full, default config only: do not run configs[2] (both branches, 512^3), configs[4] and configs[3] (one "
+                         "GPU) once each after the headline's timed region (`other_configs` of the JSON line)")
     ap.add_argument("--live-reference", action="store_true",
                     help="watershed: run live scipy and the serial oracle on the WHOLE timed volume instead of quoting "
                          "tests/golden/ws{512,1024}_full.npz (512^3: ~3 min of one core; 1024^3: ~25 min and ~50 GB of RAM)")
@@ -1442,8 +1484,12 @@ def main():
     ap.add_argument("--dry-comm", action="store_true", help="bring the communicator up, run ivx_comm_selftest on every rank "
                     "(at --gpus 1: on a one-rank RCCL communicator), print one JSON line and exit")
     args = ap.parse_args()
-    if args.cpu_slices == 0:
+    if args.cpu_slices == 0 or not args.full:
         args.cpu = False
+    if not args.full:
+        args.others = False
+    if args.dump_outputs and args.config != "grow_mc":
+        raise SystemExit("bench.py --dump-outputs: only the default config (grow_mc) writes its outputs")
     dflt = {"grow_mc": (20, 3), "grow_generic": (20, 3), "watershed": (3, 1), "watershed_sk": (2, 1), "mip": (20, 3), "sharded2048": (5, 2), "surface_tail": (5, 1)}[args.config]
     args.steps = dflt[0] if args.steps is None else args.steps
     args.warmup = dflt[1] if args.warmup is None else args.warmup
@@ -1464,14 +1510,14 @@ def main():
     if res is not None and args.config == "grow_mc" and args.others and args.cpu and world == 1 and args.size is None \
             and not args.hbm_synth and os.environ.get("IVX_FORCE_SLAB") != "1":
         res["other_configs"] = other_configs(args, job, runners)
-    if args.config == "grow_mc" and world > 1 and args.scaling == "weak" and args.size is None and not args.hbm_synth \
+    if args.full and args.config == "grow_mc" and world > 1 and args.scaling == "weak" and args.size is None and not args.hbm_synth \
             and os.environ.get("IVX_BENCH_NO_STRONG") != "1":
         # The metric reads "512^3 ... 1/2/4/8 GPU": the first multi-GPU run yields BOTH curves -- the line's own numbers are weak
         # scaling (512^3 per GPU), `strong_scaling` is configs[1]'s one 512^3 volume split over the same ranks, same steps,
         # same keys.  Every rank takes part (the slabs exchange planes); a failure is recorded, the weak line still goes out.
         import copy
         a = copy.copy(args)
-        a.scaling, a.cpu = "strong", False
+        a.scaling, a.cpu, a.dump_outputs = "strong", False, None
         try:
             r2 = run_grow_mc(a, job)
             if res is not None and r2 is not None:

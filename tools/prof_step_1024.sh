@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof1024_${1:-r05}
 mkdir -p $O
 cd /tmp
-CMD="python $R/bench.py --size 1024 --hbm-synth --steps 5 --warmup 1 --no-cpu --no-others"
+CMD="python $R/bench.py --full --size 1024 --hbm-synth --steps 5 --warmup 1 --no-cpu --no-others"
 timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o kt -- $CMD < /dev/null > $O/kt.log 2>&1
 timeout -k 5 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O -o fetch -- $CMD < /dev/null > /dev/null 2>&1
 timeout -k 5 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O -o write -- $CMD < /dev/null > /dev/null 2>&1
