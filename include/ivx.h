@@ -724,6 +724,42 @@ int ivx_dev_zoom_order2(int dtype, const void *in, const int64_t ishape[3], void
 int ivx_zoom_order2(int dtype, const void *in, const int64_t ishape[3], void *out, const int64_t oshape[3]);
 
 /* ------------------------------------------------------------------------------------------------
+ * image filters of the Image Filters dialog, int16 only (any other dtype -> IVX_EINVAL)
+ *   replaces invesalius/data/filters.py:5-66 (gaussian_blur_filter, median_blur_filter, mean_blur_filter,
+ *            sharpening_filter, despeckle_filter, border_detection_filter = scipy.ndimage gaussian_filter /
+ *            median_filter / uniform_filter / sobel, mode "reflect") as dispatched by Slice.__apply_image_filter /
+ *            _run_filter (invesalius/data/slice_.py:2330-2430), bit for bit with scipy 1.15.
+ * kind: the reference's filter_type.  plane_axis -1 = the 3-D filter; 0/1/2 = "2D" with orientation Axial / Coronal /
+ * Sagittal: every slice m[i], m[:, i] or m[:, :, i] filtered as a 2-D image (no pass along the slice axis, window extent
+ * 1; sharpen's clip range and border detection's normalisation per slice).  A 2-D image is shape {1, h, w}, plane 0.
+ * w, radius: the 2r+1 Gaussian weights exp(-0.5/sigma^2 x^2) / sum as numpy computes them (scipy's _gaussian_kernel1d,
+ * r = int(4 sigma + 0.5)), read on the host; radius -1 = sigma <= 1e-15 (no pass).  Sharpen takes sigma 1's weights.
+ * median size = max(3, min(int(2v + 1), 5)); mean size = int(2v + 1) (<= 1: identity); the ivx_dev_* forms take the
+ * size, the host form the dialog's value.  Device buffers are dense C order; out must not alias in.
+ * ---------------------------------------------------------------------------------------------- */
+#define IVX_FILTER_GAUSSIAN 0
+#define IVX_FILTER_MEDIAN 1
+#define IVX_FILTER_MEAN 2
+#define IVX_FILTER_SHARPEN 3
+#define IVX_FILTER_DESPECKLE 4
+#define IVX_FILTER_BORDER 5 /* Sobel magnitude of the Gaussian-smoothed image */
+#define IVX_FILTER_MAX_RADIUS 255
+int ivx_filter_scratch_bytes(int kind, const int64_t shape[3], int plane_axis, size_t *nbytes);
+int ivx_dev_filter_gaussian_i16(const int16_t *in, const int64_t shape[3], int plane_axis, const double *w, int radius,
+                                int16_t *out, void *scratch, void *stream);
+int ivx_dev_filter_median_i16(const int16_t *in, const int64_t shape[3], int plane_axis, int size, int16_t *out,
+                              void *stream);
+int ivx_dev_filter_mean_i16(const int16_t *in, const int64_t shape[3], int plane_axis, int size, int16_t *out,
+                            void *scratch, void *stream);
+int ivx_dev_filter_sharpen_i16(const int16_t *in, const int64_t shape[3], int plane_axis, double value, const double *w,
+                               int radius, int16_t *out, void *scratch, void *stream);
+int ivx_dev_filter_border_i16(const int16_t *in, const int64_t shape[3], int plane_axis, int normalize, const double *w,
+                              int radius, int16_t *out, void *scratch, void *stream);
+int ivx_image_filter(int kind, double value, int plane_axis, int normalize, const double *w, int radius, int dtype,
+                     const void *img, const int64_t shape[3], const int64_t strides[3], void *out,
+                     const int64_t ostrides[3]);
+
+/* ------------------------------------------------------------------------------------------------
  * bench / test input made in HBM (no reference counterpart): a CT-like int16 phantom -- six Gaussian blobs + sinusoid +
  * hashed N(0,25) noise, clipped to [-1024, 3071] -- for the slices [z0, z0 + dz) of a z_total-slice volume; deterministic
  * in (seed, global voxel index), so slabs made by different ranks tile the whole volume.  centres_zyx_sigma: 6 x (cz, cy,

@@ -814,6 +814,49 @@ class DeviceVolume:
     def forget_image_range(self):
         self._range_valid = False
 
+    # -- image filters (filters.py via Slice.__apply_image_filter, slice_.py:2330-2430) ----------------------------------
+    def filter_image(self, filter_type: int, value, dimension: str = "3D", orientation: str = "Axial"):
+        """Replace the resident image by the dialog's filter `filter_type` (0 Gaussian, 1 median, 2 mean, 3 sharpen,
+        4 despeckle, 5 border detection) with `value`, in HBM, no host round trip; ``dimension != "3D"`` filters every
+        slice along the orientation's axis.  Everything derived from the image is dropped (``_image_touched``), so a
+        threshold, region growing or surface after it works on the filtered image, as it does after _after_filter."""
+        from . import filters as F
+        from .slice_ import _FILTER_PLANES
+
+        if filter_type not in F.FILTER_NAMES:
+            raise ValueError("unknown filter type %r" % (filter_type,))
+        plane = -1 if dimension == "3D" else _FILTER_PLANES.get(orientation, 0)
+        lib, shape = L.lib(), L.i64(self.shape)
+        nb = ctypes.c_size_t(0)
+        L.check(lib.ivx_filter_scratch_bytes(int(filter_type), shape, plane, ctypes.byref(nb)), "filter_scratch_bytes")
+        self._join_prefetch()  # a surface count still reading the image must see the old one
+        out, scratch = DeviceBuffer(self.n * 2), DeviceBuffer(nb.value)
+        try:
+            st, src = self.stream, self.image.raw
+            if filter_type == F.MEDIAN:
+                rc = lib.ivx_dev_filter_median_i16(src, shape, plane, F.median_size(value), out.ptr, st)
+            elif filter_type == F.MEAN:
+                rc = lib.ivx_dev_filter_mean_i16(src, shape, plane, F.mean_size(value), out.ptr, scratch.ptr, st)
+            else:
+                w, r = F.gaussian_weights(1.0 if filter_type == F.SHARPEN else value)
+                if r > F.MAX_RADIUS:
+                    raise ValueError("sigma %r needs a kernel radius of %d (at most %d)" % (value, r, F.MAX_RADIUS))
+                wp = None if w is None else L.ptr(w)
+                if filter_type == F.SHARPEN:
+                    rc = lib.ivx_dev_filter_sharpen_i16(src, shape, plane, ctypes.c_double(float(value)), wp, int(r), out.ptr,
+                                                        scratch.ptr, st)
+                elif filter_type == F.BORDER:
+                    rc = lib.ivx_dev_filter_border_i16(src, shape, plane, 1, wp, int(r), out.ptr, scratch.ptr, st)
+                else:
+                    rc = lib.ivx_dev_filter_gaussian_i16(src, shape, plane, wp, int(r), out.ptr, scratch.ptr, st)
+            L.check(rc, "filter_image")
+            L.check(lib.ivx_memcpy_d2d(self.image.ptr, out.ptr, ctypes.c_size_t(self.n * 2), st), "filter_image copy")
+            self.sync()  # the buffers go out of scope here
+        finally:
+            out.close()
+            scratch.close()
+        self._image_touched()
+
     def mida(self, axis: int, wl, ww, out: DeviceBuffer, status: DeviceBuffer):
         """mida (mips.rs:102-168) of the resident image along `axis` into `out` (int16 image of the projection's shape); the
         volume's range comes from `image_range()`.  `status` (int32, zeroed by the caller) receives IVX_EDOM where the

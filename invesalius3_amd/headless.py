@@ -2,9 +2,10 @@
 
     python -m invesalius3_amd.headless CASE.inv3 --threshold 226 3071 --seed 250 260 100 --largest --smooth \\
         --stl bone.stl --save CASE_out.inv3
+    python -m invesalius3_amd.headless CASE.inv3 --filter median 3 --threshold 226 3071 --stl bone.stl
 
 What the reference does through its GUI for the same result: Slice.SetMaskThreshold / do_threshold_to_all_slices
-(invesalius/data/slice_.py:1240-1247, 1739-1769), the region-growing tool (styles.py:3151-3216),
+(invesalius/data/slice_.py:1240-1247, 1739-1769), the Image Filters dialog (slice_.py:2330-2539), the region-growing tool (styles.py:3151-3216),
 SurfaceManager.AddNewActor -> create_surface_piece / join_process_surface (surface.py:1362-1380,
 surface_process.py:71-472) and vtkSTLWriter (surface.py:1827-1829).  No wx, no VTK here; one JSON line on stdout."""
 from __future__ import annotations
@@ -23,6 +24,10 @@ from . import surface_process as sp
 from .device import DeviceVolume, c64
 
 
+# --filter NAME -> the reference's filter_type (slice_.py:2370-2381)
+FILTER_TYPES = {"gaussian": 0, "median": 1, "mean": 2, "sharpen": 3, "despeckle": 4, "border": 5}
+
+
 def run(args) -> dict:
     t_all = time.perf_counter()
     proj = prj.open_inv3(args.project)
@@ -32,6 +37,17 @@ def run(args) -> dict:
     vol = DeviceVolume(np.ascontiguousarray(proj.matrix), spacing=proj.spacing)
     lib = L.lib()
     try:
+        filtered = None
+        if args.filter is not None:
+            # the Image Filters dialog (Slice.__apply_image_filter, slice_.py:2330-2430) on the resident image
+            ftype, fvalue = FILTER_TYPES[args.filter[0]], float(args.filter[1])
+            dimension, orientation = ("3D", "Axial") if args.filter_2d is None else ("2D", args.filter_2d.capitalize())
+            with vol.timer.span("filter"):
+                vol.filter_image(ftype, fvalue, dimension, orientation)
+            out["filter"] = {"type": args.filter[0], "value": fvalue, "dimension": dimension, "orientation": orientation}
+            if args.save:
+                vol.sync()
+                filtered = (vol.image.download(vol.shape, np.int16), ftype, fvalue, dimension, orientation)
         if args.threshold is not None:
             lo, hi = args.threshold
             with vol.timer.span("threshold"):
@@ -105,6 +121,11 @@ def run(args) -> dict:
             rec = prj.new_mask(proj, args.mask_name, (lo, hi))
             rec.matrix[1:, 1:, 1:] = mask
             rec.matrix[1:, 0, 0] = 1  # per-slice "already thresholded" flags, as SetMaskThreshold leaves them (slice_.py:1246)
+            if filtered is not None:
+                img, ftype, fvalue, dimension, orientation = filtered
+                label = prj.add_image_version(proj, img, ftype, fvalue, dimension, orientation)
+                rec.derived_from = label  # _after_filter's create_new_mask(derived_from=label)
+                out["image_version"] = label
             prj.save_inv3(args.save, proj)
             out["saved"] = args.save
         out["gpu_ms"] = {k: round(float(sum(v)), 4) for k, v in vol.timer.collect().items()}
@@ -130,6 +151,11 @@ def main(argv=None) -> int:
     g.add_argument("--threshold", nargs=2, type=int, metavar=("LO", "HI"), help="threshold the image into a new mask")
     g.add_argument("--mask", type=int, default=0, help="use the project's mask with this index (default 0)")
     ap.add_argument("--seed", nargs="+", type=int, default=None, metavar="X Y Z", help="keep the region grown (in the image, inside the threshold range) from these voxels; refused for a hand-edited --mask")
+    ap.add_argument("--filter", nargs=2, metavar=("NAME", "VALUE"), default=None,
+                    help="image filter applied before --threshold / --seed: NAME one of %s, VALUE the dialog's value "
+                         "(sigma, or the size parameter)" % ",".join(FILTER_TYPES))
+    ap.add_argument("--filter-2d", choices=("axial", "coronal", "sagittal"), default=None,
+                    help="filter slice by slice along this orientation instead of in 3-D")
     ap.add_argument("--connectivity", type=int, choices=(6, 18, 26), default=26)
     ap.add_argument("--largest", action="store_true", help="keep the largest connected surface")
     ap.add_argument("--smooth", action="store_true", help="context-aware smoothing")
@@ -143,6 +169,15 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
     if args.seed and len(args.seed) % 3:
         ap.error("--seed takes triples of x y z")
+    if args.filter is not None:
+        if args.filter[0] not in FILTER_TYPES:
+            ap.error("--filter NAME must be one of %s" % ", ".join(FILTER_TYPES))
+        try:
+            float(args.filter[1])
+        except ValueError:
+            ap.error("--filter VALUE must be a number")
+    elif args.filter_2d is not None:
+        ap.error("--filter-2d needs --filter")
     print(json.dumps(run(args)))
     return 0
 

@@ -30,6 +30,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 FORMAT_VERSION = 1.1  # invesalius/constants.py:32
+# what Slice._after_filter records per filtered image version (slice_.py:2480-2486)
+VERSION_META_KEYS = ("applied_filter", "sigma_smooth", "derived", "dimension", "orientation")
 
 
 @dataclass
@@ -72,6 +74,7 @@ class Project:
     surfaces: dict = field(default_factory=dict)
     measurements: dict = field(default_factory=dict)
     image_versions: list = field(default_factory=list)
+    image_versions_meta: dict = field(default_factory=dict)  # label -> {applied_filter, sigma_smooth, derived, ...}
     dirpath: str = ""
     _owned_tmp: str = ""  # the directory open_inv3 made with mkdtemp (removed by close()); never a caller's workdir
 
@@ -80,6 +83,7 @@ class Project:
         self.matrix = None
         self.masks.clear()
         self.image_versions.clear()
+        self.image_versions_meta.clear()
         if self._owned_tmp and os.path.isdir(self._owned_tmp):
             shutil.rmtree(self._owned_tmp, ignore_errors=True)
         self._owned_tmp = ""
@@ -170,6 +174,9 @@ def load_from_folder(dirpath: str) -> Project:
     p.matrix = np.memmap(p.matrix_filename, shape=p.matrix_shape, dtype=p.matrix_dtype, mode="r+")
     for version in main.get("image_versions", []):
         vpath = _inside(dirpath, version["filename"])
+        meta = {k: version[k] for k in VERSION_META_KEYS if k in version}  # project.py:448-457 (+ dimension / orientation)
+        if meta:
+            p.image_versions_meta[version["label"]] = meta
         if os.path.exists(vpath):
             p.image_versions.append((version["label"], np.memmap(vpath, shape=p.matrix_shape, dtype=p.matrix_dtype, mode="r+")))
     masks = main.get("masks", {})
@@ -236,9 +243,9 @@ def open_inv3(filename, workdir: str | None = None) -> Project:
 
 
 def save_inv3(filename, project: Project, gz: bool | None = None):
-    """Project.SavePlistProject (project.py:219-345): image, filtered image versions, masks, surfaces (plist + polydata
-    file) and measurements.  A project opened with open_inv3 and written back keeps all of them (not carried: the
-    per-version filter parameters and `active_image_version` of project.py:253-293)."""
+    """Project.SavePlistProject (project.py:219-345): image, filtered image versions with their filter parameters,
+    masks, surfaces (plist + polydata file) and measurements.  A project opened with open_inv3 and written back keeps
+    all of them (not carried: `active_image_version` of project.py:253-254)."""
     gz = project.compress if gz is None else gz
     tmp = tempfile.mkdtemp(prefix="ivx3_save_")
     try:
@@ -270,7 +277,10 @@ def save_inv3(filename, project: Project, gz: bool | None = None):
             vpath = os.path.join(tmp, vname)
             np.ascontiguousarray(mat).tofile(vpath)
             filelist[vpath] = vname
-            versions.append({"label": label, "filename": vname})
+            entry = {"label": label, "filename": vname}
+            if label in project.image_versions_meta:  # project.py:291-292
+                entry.update(project.image_versions_meta[label])
+            versions.append(entry)
         main["image_versions"] = versions
         if project.affine is not None:
             main["affine"] = project.affine
@@ -335,3 +345,27 @@ def new_mask(project: Project, name: str, threshold_range, index: int | None = N
                      edition_threshold_range=tuple(threshold_range))
     project.masks[index] = rec
     return rec
+
+
+def add_image_version(project: Project, result: np.ndarray, filter_type=None, value=None, dimension: str = "3D",
+                      orientation: str = "Axial", derived: str = "original", label_prefix: str = "Filtered") -> str:
+    """File a filter's result as Slice.__apply_image_filter / _after_filter do (slice_.py:2342-2361, 2432-2486): the
+    unfiltered image becomes version "original" when the list is empty, the result is appended as "Filtered N"
+    (N = 1 + the versions already labelled so) and, for a known `filter_type`, its image_versions_meta entry is made.
+    Returns the label."""
+    if not project.image_versions:
+        project.image_versions.append(("original", project.matrix))
+    n = sum(1 for lbl, _m in project.image_versions if lbl.startswith(label_prefix))
+    label = "%s %d" % (label_prefix, n + 1)
+    project.image_versions.append((label, result))
+    if filter_type is not None:
+        from .filters import FILTER_NAMES
+
+        project.image_versions_meta[label] = {
+            "applied_filter": FILTER_NAMES.get(filter_type, "unknown"),
+            "sigma_smooth": str(value),
+            "derived": derived,
+            "dimension": dimension,
+            "orientation": orientation,
+        }
+    return label

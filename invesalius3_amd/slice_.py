@@ -256,3 +256,30 @@ def calc_image_density(image: np.ndarray, mask_matrix: np.ndarray):
     mean = s1 / cnt
     var = max(s2 / cnt - mean * mean, 0.0)
     return int(lo), int(hi), float(mean), float(np.sqrt(var))
+
+
+_FILTER_PLANES = {"Axial": 0, "Coronal": 1, "Sagittal": 2}  # _run_filter's axis_map (slice_.py:2384)
+
+
+def apply_image_filter(matrix: np.ndarray, filter_type: int, value, dimension: str = "3D", orientation: str = "Axial"):
+    """The compute part of Slice.__apply_image_filter / _run_filter (slice_.py:2330-2430): filter type 0 Gaussian,
+    1 median, 2 mean, 3 sharpen, 4 despeckle, 5 border detection (filters.py) over the whole volume, or with
+    ``dimension != "3D"`` slice by slice along the orientation's axis (Axial 0, Coronal 1, Sagittal 2; anything else 0)
+    -- in one library call, not one per slice.  Returns ``result.astype(matrix.dtype)`` as the reference stashes it;
+    an unknown filter type returns None (the reference returns without a result)."""
+    from . import filters
+
+    if filter_type not in filters.FILTER_NAMES:
+        return None
+    if dimension == "3D":
+        plane = -1
+    else:
+        if getattr(matrix, "ndim", 0) != 3:
+            raise TypeError("the 2D mode filters the slices of a 3-D image")
+        plane = _FILTER_PLANES.get(orientation, 0)
+    if filter_type == filters.MEDIAN:
+        filters.median_size(value)
+    elif filter_type == filters.MEAN:
+        filters.mean_size(value)
+    result = filters.image_filter(matrix, filter_type, value, plane)
+    return result.astype(matrix.dtype)
