@@ -760,6 +760,50 @@ int ivx_image_filter(int kind, double value, int plane_axis, int normalize, cons
                      const int64_t ostrides[3]);
 
 /* ------------------------------------------------------------------------------------------------
+ * deep-learning segmentation: the Unet3D of invesalius/segmentation/deep_learning/model.py:9-113 (brain MRI T1 and
+ * trachea CT, BrainSegmentProcess / TracheaSegmentProcess, segment.py:505-541, 919-953), float32, eval mode.
+ *   ivx_unet3d_load: network from a host float32 blob of FOLDED parameters (BatchNorm folded on the host in float64:
+ *     w * g / sqrt(v + eps), (b - m) * g / sqrt(v + eps) + beta, rounded to float32 once), in this order:
+ *       enc1, enc2, enc3, enc4, bottleneck: conv1 w (cout, cin, 5, 5, 5), conv1 b (cout), conv2 w, conv2 b;
+ *       then for upconv4 / decoder4, upconv3 / decoder3, upconv2 / decoder2, upconv1 / decoder1:
+ *         upconv w (cin, cout, 4, 4, 4) (torch's ConvTranspose3d layout), upconv b, conv1 w (cout, 2 cout, 5, 5, 5)
+ *         (input channels: upsampled first, then the skip), conv1 b, conv2 w, conv2 b;
+ *       final conv w (8), b (1).  ivx_unet3d_param_count gives the total.
+ *   ivx_dev_unet3d_forward: the raw network on n patches of patch^3 (dense float32 in / out, patch a multiple of 16);
+ *     the workspace holds some batch of patches and the call runs n in chunks of it.
+ *   ivx_dev_unet3d_normalize: image_normalize(image, 0.0, 1.0, float32) (imagedata_utils.py:580-587) in numpy 2
+ *     promotion, int16 wraps included; minmax2 = 2 device floats of scratch.
+ *   ivx_dev_unet3d_segment: segment_torch's loop (segment.py:162-191) on the normalised volume: gen_patches' cuts,
+ *     batches of `batch` patches, every voxel's covering cuts added in cut order onto prob (float32, read and written),
+ *     then prob /= the cover count.  The result does not depend on `batch`.  progress (host, may be NULL) receives the
+ *     fraction of cuts done after each batch.  Workspace: ivx_unet3d_workspace_bytes(net, patch, batch).
+ *   ivx_dev_segment_threshold: apply_segment_threshold (segment.py:465-490): (prob >= threshold) * 255, float32
+ *     comparison.  border = 1: mask is the (d+1, h+1, w+1) mask.matrix (strides in elements), written at [1:, 1:, 1:],
+ *     and its lines [:, 0, 0], [0, :, 0], [0, 0, :] set to 2; border = 0: mask is the (d, h, w) interior alone.
+ *   ivx_segment_unet3d: host form of _run_segmentation + segment_torch (int16 image of any strides, optional
+ *     get_LUT_value(ww, wl), dense float32 prob in / out).
+ * ---------------------------------------------------------------------------------------------- */
+int ivx_unet3d_param_count(int64_t *nfloats);
+int ivx_unet3d_load(const float *blob, int64_t nfloats, void **net);
+int ivx_unet3d_free(void *net);
+int ivx_unet3d_workspace_bytes(const void *net, int patch, int batch, size_t *nbytes);
+int ivx_dev_unet3d_forward(const void *net, const float *in, int64_t n, int patch, float *out, void *workspace,
+                           size_t ws_bytes, void *stream);
+/* the forward once with a HIP event after each of its 27 launches (encoder: conv1, conv2, pool per level; bottleneck
+ * conv1, conv2; decoder: upconv, conv1, conv2 per level; head); n patches must fit the workspace in one batch */
+int ivx_unet3d_layer_times(const void *net, const float *in, int64_t n, int patch, float *out, void *workspace,
+                           size_t ws_bytes, void *stream, float *ms /* 27 */);
+int ivx_dev_unet3d_normalize(const int16_t *img, int64_t n, float *out, float *minmax2, void *stream);
+int ivx_segment_cut_count(const int64_t shape[3], int patch, int overlap, int64_t *ncuts);
+int ivx_dev_unet3d_segment(const void *net, const float *vol, const int64_t shape[3], int patch, int overlap, int batch,
+                           float *prob, void *workspace, size_t ws_bytes, float *progress, void *stream);
+int ivx_dev_segment_threshold(const float *prob, const int64_t shape[3], float threshold, uint8_t *mask,
+                              const int64_t mstrides[3], int border, void *stream);
+int ivx_segment_unet3d(const void *net, const int16_t *img, const int64_t shape[3], const int64_t strides[3],
+                       int apply_wwwl, double window, double level, int patch, int overlap, int batch, float *prob,
+                       float *progress);
+
+/* ------------------------------------------------------------------------------------------------
  * bench / test input made in HBM (no reference counterpart): a CT-like int16 phantom -- six Gaussian blobs + sinusoid +
  * hashed N(0,25) noise, clipped to [-1024, 3071] -- for the slices [z0, z0 + dz) of a z_total-slice volume; deterministic
  * in (seed, global voxel index), so slabs made by different ranks tile the whole volume.  centres_zyx_sigma: 6 x (cz, cy,

@@ -274,7 +274,8 @@ class DeviceVolume:
         for b in (self.image, self.mask, self.out_mask):
             b._on_touch = None  # freeing is not "somebody looked at the contents"
         for b in (self.image, self.mask, self.out_mask, self.cand, self.reached, self._mbits, self.flood_scratch,
-                  self._mc_scratch, self._tris, self._verts, self._faces, self._gate, getattr(self, "_range_buf", None)):
+                  self._mc_scratch, self._tris, self._verts, self._faces, self._gate, getattr(self, "_range_buf", None),
+                  getattr(self, "prob", None)):
             if b is not None:
                 b.close()
         if self.stream is not None:
@@ -856,6 +857,49 @@ class DeviceVolume:
             out.close()
             scratch.close()
         self._image_touched()
+
+    # -- deep-learning segmentation (segment_torch, segment.py:162-191; apply_segment_threshold, :465-490) -------------
+    def segment_unet3d(self, weights, overlap: int = 50, patch_size: int = 48, apply_wwwl: bool = False, window_width=255,
+                       window_level=127, batch: int | None = None) -> DeviceBuffer:
+        """The U-Net segmentation of the resident image (get_LUT_value first if `apply_wwwl`) into the resident float32
+        probability map `self.prob`, which is returned; `weights` as for segment.load_weights, or a segment.Unet3D.
+        The image and the mask are left as they are: apply_segment_threshold writes the mask."""
+        from . import segment as SG
+
+        SG._check_args(patch_size, overlap)
+        net = weights if isinstance(weights, SG.Unet3D) else SG.Unet3D(weights)
+        batch = SG.DEFAULT_BATCH if batch is None else int(batch)
+        lib, st, n = L.lib(), self.stream, self.n
+        if getattr(self, "prob", None) is None:
+            self.prob = DeviceBuffer(n * 4)
+        ws, norm, small = DeviceBuffer(net.workspace_bytes(patch_size, batch)), DeviceBuffer(n * 4), DeviceBuffer(64)
+        lut = DeviceBuffer(n * 2) if apply_wwwl else None
+        try:
+            src = self.image.raw
+            if apply_wwwl:  # get_LUT_value keeps int16 (np.piecewise)
+                L.check(lib.ivx_dev_lut_i16(src, c64(n), ctypes.c_double(float(window_width)),
+                                            ctypes.c_double(float(window_level)), 0, lut.ptr, st), "segment lut")
+                src = lut.ptr
+            L.check(lib.ivx_dev_unet3d_normalize(src, c64(n), norm.ptr, small.ptr, st), "segment normalize")
+            self.prob.zero(st)
+            L.check(lib.ivx_dev_unet3d_segment(net.handle, norm.ptr, L.i64(self.shape), int(patch_size), int(overlap), batch,
+                                               self.prob.ptr, ws.ptr, ctypes.c_size_t(ws.nbytes), None, st), "segment_unet3d")
+            self.sync()  # the buffers go out of scope here
+        finally:
+            for b in (ws, norm, small, lut):
+                if b is not None:
+                    b.close()
+        return self.prob
+
+    def apply_segment_threshold(self, threshold: float):
+        """mask.matrix[1:, 1:, 1:] = (prob >= float32(threshold)) * 255 on the resident mask: one kernel per slider move;
+        marching_cubes follows without an upload.  The per-slice flag lines live in the host mask's border
+        (segment.apply_segment_threshold writes them there)."""
+        if getattr(self, "prob", None) is None:
+            raise RuntimeError("apply_segment_threshold: no probability map (run segment_unet3d first)")
+        L.check(L.lib().ivx_dev_segment_threshold(self.prob.ptr, L.i64(self.shape), ctypes.c_float(float(threshold)),
+                                                  self.mask.ptr, L.i64([self.dy * self.dx, self.dx, 1]), 0, self.stream),
+                "segment_threshold")
 
     def mida(self, axis: int, wl, ww, out: DeviceBuffer, status: DeviceBuffer):
         """mida (mips.rs:102-168) of the resident image along `axis` into `out` (int16 image of the projection's shape); the

@@ -3,9 +3,10 @@
     python -m invesalius3_amd.headless CASE.inv3 --threshold 226 3071 --seed 250 260 100 --largest --smooth \\
         --stl bone.stl --save CASE_out.inv3
     python -m invesalius3_amd.headless CASE.inv3 --filter median 3 --threshold 226 3071 --stl bone.stl
+    python -m invesalius3_amd.headless CASE.inv3 --segment brain --weights brain_mri_t1.pt --stl brain.stl
 
 What the reference does through its GUI for the same result: Slice.SetMaskThreshold / do_threshold_to_all_slices
-(invesalius/data/slice_.py:1240-1247, 1739-1769), the Image Filters dialog (slice_.py:2330-2539), the region-growing tool (styles.py:3151-3216),
+(invesalius/data/slice_.py:1240-1247, 1739-1769), the Image Filters dialog (slice_.py:2330-2539), the deep-learning segmentation (segmentation/deep_learning/segment.py), the region-growing tool (styles.py:3151-3216),
 SurfaceManager.AddNewActor -> create_surface_piece / join_process_surface (surface.py:1362-1380,
 surface_process.py:71-472) and vtkSTLWriter (surface.py:1827-1829).  No wx, no VTK here; one JSON line on stdout."""
 from __future__ import annotations
@@ -48,7 +49,25 @@ def run(args) -> dict:
             if args.save:
                 vol.sync()
                 filtered = (vol.image.download(vol.shape, np.int16), ftype, fvalue, dimension, orientation)
-        if args.threshold is not None:
+        segmented = False
+        if args.segment is not None:
+            # the Segmentation menu's deep-learning tool (BrainSegmentProcess / TracheaSegmentProcess, segment.py:505-541,
+            # 919-953) into the resident mask: probabilities, then apply_segment_threshold
+            from . import segment as SG
+            pre = SG.PRESETS[args.segment]
+            wwwl = args.apply_wwwl is not None
+            ww, wl = args.apply_wwwl if wwwl else (255, 127)
+            with vol.timer.span("segment"):
+                vol.segment_unet3d(args.weights, overlap=args.overlap, patch_size=pre.patch_size, apply_wwwl=wwwl,
+                                   window_width=ww, window_level=wl)
+            with vol.timer.span("segment_threshold"):
+                vol.apply_segment_threshold(args.seg_threshold)
+            out["segment"] = {"tool": pre.name, "weights": str(args.weights), "overlap": args.overlap,
+                              "patch_size": pre.patch_size, "threshold": args.seg_threshold,
+                              "apply_wwwl": [ww, wl] if wwwl else None}
+            lo, hi = 0, 0
+            segmented = True
+        elif args.threshold is not None:
             lo, hi = args.threshold
             with vol.timer.span("threshold"):
                 vol.threshold(lo, hi)
@@ -120,7 +139,12 @@ def run(args) -> dict:
         if args.save:
             rec = prj.new_mask(proj, args.mask_name, (lo, hi))
             rec.matrix[1:, 1:, 1:] = mask
-            rec.matrix[1:, 0, 0] = 1  # per-slice "already thresholded" flags, as SetMaskThreshold leaves them (slice_.py:1246)
+            if segmented:  # apply_segment_threshold's "fully edited" flag lines (segment.py:481-486)
+                rec.matrix[:, 0, 0] = 2
+                rec.matrix[0, :, 0] = 2
+                rec.matrix[0, 0, :] = 2
+            else:
+                rec.matrix[1:, 0, 0] = 1  # per-slice "already thresholded" flags, as SetMaskThreshold leaves them (slice_.py:1246)
             if filtered is not None:
                 img, ftype, fvalue, dimension, orientation = filtered
                 label = prj.add_image_version(proj, img, ftype, fvalue, dimension, orientation)
@@ -150,6 +174,14 @@ def main(argv=None) -> int:
     g = ap.add_mutually_exclusive_group()
     g.add_argument("--threshold", nargs=2, type=int, metavar=("LO", "HI"), help="threshold the image into a new mask")
     g.add_argument("--mask", type=int, default=0, help="use the project's mask with this index (default 0)")
+    g.add_argument("--segment", choices=("brain", "trachea"), default=None,
+                   help="deep-learning segmentation into a new mask (Brain MRI T1 / Trachea CT); needs --weights")
+    ap.add_argument("--weights", default=None, help="the tool's torch.save weights file (brain_mri_t1.pt / trachea_ct.pt) "
+                                                   "or an .npz of the same keys; never downloaded")
+    ap.add_argument("--seg-threshold", type=float, default=0.75, help="probability threshold of --segment (default 0.75)")
+    ap.add_argument("--overlap", type=int, choices=(0, 10, 25, 50), default=50, help="patch overlap in %% (default 50)")
+    ap.add_argument("--apply-wwwl", nargs=2, type=float, metavar=("WW", "WL"), default=None,
+                    help="window the image (get_LUT_value) before --segment")
     ap.add_argument("--seed", nargs="+", type=int, default=None, metavar="X Y Z", help="keep the region grown (in the image, inside the threshold range) from these voxels; refused for a hand-edited --mask")
     ap.add_argument("--filter", nargs=2, metavar=("NAME", "VALUE"), default=None,
                     help="image filter applied before --threshold / --seed: NAME one of %s, VALUE the dialog's value "
@@ -167,6 +199,13 @@ def main(argv=None) -> int:
     ap.add_argument("--save", help="write the project back with the new mask appended")
     ap.add_argument("--mask-name", default="GPU mask")
     args = ap.parse_args(argv)
+    if args.segment is not None:
+        if args.weights is None:
+            ap.error("--segment needs --weights FILE")
+        if args.seed:
+            ap.error("--seed does not combine with --segment")
+    elif args.weights is not None or args.apply_wwwl is not None:
+        ap.error("--weights / --apply-wwwl need --segment")
     if args.seed and len(args.seed) % 3:
         ap.error("--seed takes triples of x y z")
     if args.filter is not None:

@@ -1,0 +1,152 @@
+"""Float64 numpy restatement of the reference's Unet3D (invesalius/segmentation/deep_learning/model.py:9-113, eval mode)
+and of segment_torch's accumulation, for the tests.  No torch: the state dict is a dict of numpy arrays in the
+reference's key names (invesalius3_amd.segment.param_spec)."""
+from __future__ import annotations
+
+import zlib
+
+import numpy as np
+
+WEIGHT_SEED = 20261016
+
+
+def make_weights(seed: int = WEIGHT_SEED) -> dict:
+    """Seeded He-scaled weights in the names and shapes of Unet3D().state_dict(), with BatchNorm running statistics that
+    are not the identity, and a head bias that puts the probabilities of a normalised CT-like volume on both sides of
+    0.75."""
+    from invesalius3_amd.segment import param_spec
+
+    rng = np.random.default_rng(seed)
+    sd = {}
+    for k, shp in param_spec():
+        if k.endswith("num_batches_tracked"):
+            sd[k] = np.array(1000, np.int64)
+        elif k.endswith("running_var"):
+            sd[k] = rng.uniform(0.5, 2.0, shp).astype(np.float32)
+        elif k.endswith("running_mean"):
+            sd[k] = rng.normal(0.0, 0.1, shp).astype(np.float32)
+        elif "norm" in k and k.endswith(".weight"):
+            sd[k] = rng.uniform(0.8, 1.25, shp).astype(np.float32)
+        elif k.endswith(".bias"):
+            sd[k] = rng.normal(0.0, 0.05, shp).astype(np.float32)
+        else:
+            if k.startswith("upconv"):
+                fan_in = shp[0] * 8  # each output sees cin x 2^3 taps
+            else:
+                fan_in = int(np.prod(shp[1:]))
+            sd[k] = (rng.standard_normal(shp) * np.sqrt(2.0 / fan_in)).astype(np.float32)
+    sd["conv.weight"] = sd["conv.weight"] * np.float32(4.0)  # spread the logits
+    sd["conv.bias"] = np.array([1.2], np.float32)
+    return sd
+
+
+def weights_crc(sd: dict) -> int:
+    from invesalius3_amd.segment import param_spec
+
+    c = 0
+    for k, _ in param_spec():
+        c = zlib.crc32(np.ascontiguousarray(sd[k]).tobytes(), c)
+    return c
+
+
+def _conv5(x, w, b):
+    """x (cin, S, S, S), w (cout, cin, 5, 5, 5): Conv3d(k 5, pad 2) + bias, float64"""
+    S = x.shape[1]
+    xp = np.pad(x, ((0, 0), (2, 2), (2, 2), (2, 2)))
+    out = np.zeros((w.shape[0], S, S, S))
+    for kz in range(5):
+        for ky in range(5):
+            for kx in range(5):
+                out += np.tensordot(w[:, :, kz, ky, kx], xp[:, kz:kz + S, ky:ky + S, kx:kx + S], axes=(1, 0))
+    return out + b[:, None, None, None]
+
+
+def _upconv(x, w, b):
+    """ConvTranspose3d(k 4, stride 2, pad 1); w (cin, cout, 4, 4, 4)"""
+    S = x.shape[1]
+    full = np.zeros((w.shape[1], 2 * S + 2, 2 * S + 2, 2 * S + 2))
+    for kz in range(4):
+        for ky in range(4):
+            for kx in range(4):
+                full[:, kz:kz + 2 * S:2, ky:ky + 2 * S:2, kx:kx + 2 * S:2] += np.tensordot(w[:, :, kz, ky, kx], x, axes=(0, 0))
+    return full[:, 1:2 * S + 1, 1:2 * S + 1, 1:2 * S + 1] + b[:, None, None, None]
+
+
+def _block(sd, prefix, name, x):
+    for i in (1, 2):
+        g = lambda p: sd["%s.%s_%s" % (prefix, name, p)].astype(np.float64)  # noqa: E731
+        x = _conv5(x, g("conv%d.weight" % i), g("conv%d.bias" % i))
+        x = (x - g("norm%d.running_mean" % i)[:, None, None, None]) / np.sqrt(g("norm%d.running_var" % i) + 1e-5)[:, None, None, None]
+        x = x * g("norm%d.weight" % i)[:, None, None, None] + g("norm%d.bias" % i)[:, None, None, None]
+        x = np.maximum(x, 0.0)
+    return x
+
+
+def _pool(x):
+    c, s = x.shape[0], x.shape[1] // 2
+    return x.reshape(c, s, 2, s, 2, s, 2).max(axis=(2, 4, 6))
+
+
+def forward64(sd: dict, patch: np.ndarray) -> np.ndarray:
+    """model(patch) of one (P, P, P) patch in float64 -> (P, P, P) probabilities"""
+    x = np.asarray(patch, np.float64)[None]
+    e1 = _block(sd, "encoder1", "enc1", x)
+    e2 = _block(sd, "encoder2", "enc2", _pool(e1))
+    e3 = _block(sd, "encoder3", "enc3", _pool(e2))
+    e4 = _block(sd, "encoder4", "enc4", _pool(e3))
+    d = _block(sd, "bottleneck", "bottleneck", _pool(e4))
+    for lvl, skip in ((4, e4), (3, e3), (2, e2), (1, e1)):
+        up = _upconv(d, sd["upconv%d.weight" % lvl].astype(np.float64), sd["upconv%d.bias" % lvl].astype(np.float64))
+        d = _block(sd, "decoder%d" % lvl, "dec4", np.concatenate([up, skip], 0))
+    z = np.tensordot(sd["conv.weight"].astype(np.float64)[:, :, 0, 0, 0], d, axes=(1, 0))[0] + float(sd["conv.bias"][0])
+    return 1.0 / (1.0 + np.exp(-z))
+
+
+def accumulate(image_norm: np.ndarray, patch_size: int, overlap: int, outputs, prob0=None) -> np.ndarray:
+    """segment_torch's loop (segment.py:182-190) in float32 numpy, over given per-cut network outputs (P^3 each)"""
+    from invesalius3_amd.segment import gen_patches
+
+    prob = np.zeros(image_norm.shape, np.float32) if prob0 is None else prob0.astype(np.float32).copy()
+    sums = np.zeros_like(prob)
+    for (_, _, cut), out in zip(gen_patches(image_norm, patch_size, overlap), outputs):
+        (iz, ez), (iy, ey), (ix, ex) = cut
+        prob[iz:ez, iy:ey, ix:ex] += out[: ez - iz, : ey - iy, : ex - ix]
+        sums[iz:ez, iy:ey, ix:ex] += 1
+    prob /= sums
+    return prob
+
+
+def ct_volume(shape, seed, lo=-1000, hi=1500) -> np.ndarray:
+    """a smooth int16 CT-like test volume: a few blobs over noise"""
+    rng = np.random.default_rng(seed)
+    z, y, x = np.meshgrid(*[np.linspace(-1, 1, s) for s in shape], indexing="ij")
+    v = np.zeros(shape)
+    for _ in range(4):
+        c = rng.uniform(-0.6, 0.6, 3)
+        r = rng.uniform(0.2, 0.5)
+        v += np.exp(-((z - c[0]) ** 2 + (y - c[1]) ** 2 + (x - c[2]) ** 2) / (2 * r * r))
+    v = v / v.max()
+    v = lo + (hi - lo) * v + rng.normal(0, 30, shape)
+    return np.clip(v, -32768, 32767).astype(np.int16)
+
+
+def get_lut_value(data: np.ndarray, window, level) -> np.ndarray:
+    """imagedata_utils.get_LUT_value (imagedata_utils.py:555-564): np.piecewise keeps the int16 dtype"""
+    shape = data.shape
+    d = data.ravel()
+    out = np.piecewise(d, [d <= (level - 0.5 - (window - 1) / 2), d > (level - 0.5 + (window - 1) / 2)],
+                       [0, window, lambda v: ((v - (level - 0.5)) / (window - 1) + 0.5) * (window)])
+    out.shape = shape
+    return out
+
+
+def host_pipeline(net, image, patch_size, overlap, apply_wwwl=False, ww=255, wl=127):
+    """segment_torch's accumulation (numpy, float32) over the device network's outputs on numpy-normalised patches"""
+    from invesalius3_amd.segment import gen_patches, image_normalize_f32
+
+    if apply_wwwl:
+        image = get_lut_value(image, ww, wl)
+    nrm = image_normalize_f32(image)
+    patches = np.stack([p.copy() for _, p, _ in gen_patches(nrm, patch_size, overlap)])
+    outs = net.forward(patches)
+    return accumulate(nrm, patch_size, overlap, outs), nrm
