@@ -804,6 +804,54 @@ int ivx_segment_unet3d(const void *net, const int16_t *img, const int64_t shape[
                        float *progress);
 
 /* ------------------------------------------------------------------------------------------------
+ * volume rendering: the 3-D view's ray caster with the raycasting presets
+ *   replaces invesalius/data/volume.py:575-707 (Volume.LoadVolume: vtkImageShiftScale, ApplyConvolution's
+ *   vtkImageConvolve "Basic Smooth 5x5", vtkFixedPointVolumeRayCastMapper with a parallel camera) and
+ *   CalculateHistogram (:723-735).  The contract (geometry, sampling, shading, compositing) is DESIGN.md section 7d; the
+ *   tables come from invesalius3_amd/volume.py.  Device buffers are dense C order (z, y, x).
+ * ivx_dev_volren_prepare   out = uint16(img + shift), then `nsmooth` passes of the 5x5 kernel (weights k / 60.0 in float64,
+ *                          taps in row-major order, out-of-volume taps skipped, truncated toward zero) over every XY slice;
+ *                          scratch: n uint16 when nsmooth >= 1 (else may be NULL); out must not alias img.
+ * ivx_dev_volren_cells     per IVX_VOLREN_CELL^3 macro cell the min and max of the prepared field over the cell's voxels
+ *                          plus one voxel on every side: cells[2 c] = min, cells[2 c + 1] = max, cell c = (cz, cy, cx) of a
+ *                          grid of ceil(n / IVX_VOLREN_CELL) per axis.
+ * ivx_dev_volren_render    one ray per pixel; table: n_table float4 (r, g, b, a' corrected for the sample distance),
+ *                          alpha: n_table uncorrected a (MIP), prefix: n_table + 1 counts of entries with a' > 0; out:
+ *                          height x width x 4 float32, or uint8 when out_u8; stats (optional, 4 uint64, accumulated):
+ *                          samples classified, samples skipped, rays terminated early, rays that hit the box.
+ * ivx_dev_volren_histogram counts[i] = voxels equal to lo + i for 0 <= i < nbins (uint64; zeroed here).
+ * ivx_volume_render        host form: int16 image of any strides in, prepare + cells + render, the image out.
+ * ---------------------------------------------------------------------------------------------- */
+#define IVX_VOLREN_CELL 8
+typedef struct ivx_volren_params {
+    int32_t width, height; /* viewport in pixels; row 0 of out is the top */
+    int32_t mip;           /* 0 composite (front to back), 1 maximum intensity */
+    int32_t shade;         /* composite only: headlight shading with the four coefficients below */
+    int32_t skip;          /* empty-space skipping over the macro cells (changes no bit of the result) */
+    int32_t n_table;       /* entries of table / alpha (>= 2): scalar s reads entries floor(s), floor(s) + 1 */
+    int32_t out_u8;        /* out is uint8 RGBA (floor(255 v + 0.5), clamped) instead of float32 RGBA */
+    int32_t clip;          /* keep only n . (p - o) >= 0 of the clip plane below */
+    double origin[3];      /* world position of pixel (0, 0)'s centre on the plane through the focal point */
+    double du[3], dv[3];   /* world step per pixel column / per pixel row */
+    double dir[3];         /* unit direction of the (parallel) rays */
+    double spacing[3];     /* sx, sy, sz: voxel (z, y, x) sits at world (x sx, -y sy, z sz) */
+    double dt;             /* sample distance along the ray (world units) */
+    double ambient, diffuse, specular, specular_power;
+    double background[3];  /* r, g, b in 0..1 */
+    double clip_normal[3], clip_origin[3];
+} ivx_volren_params;
+int ivx_dev_volren_prepare(const int16_t *img, const int64_t shape[3], int shift, int nsmooth, uint16_t *out,
+                           uint16_t *scratch, void *stream);
+int ivx_dev_volren_cells(const uint16_t *vol, const int64_t shape[3], uint16_t *cells, void *stream);
+int ivx_dev_volren_render(const uint16_t *vol, const uint16_t *cells, const int64_t shape[3], const float *table,
+                          const float *alpha, const uint32_t *prefix, const ivx_volren_params *p, void *out,
+                          uint64_t *stats, void *stream);
+int ivx_dev_volren_histogram(const int16_t *img, int64_t n, int lo, int nbins, uint64_t *counts, void *stream);
+int ivx_volume_render(const int16_t *img, const int64_t shape[3], const int64_t strides[3], int shift, int nsmooth,
+                      const float *table, const float *alpha, const uint32_t *prefix, const ivx_volren_params *p,
+                      void *out);
+
+/* ------------------------------------------------------------------------------------------------
  * bench / test input made in HBM (no reference counterpart): a CT-like int16 phantom -- six Gaussian blobs + sinusoid +
  * hashed N(0,25) noise, clipped to [-1024, 3071] -- for the slices [z0, z0 + dz) of a z_total-slice volume; deterministic
  * in (seed, global voxel index), so slabs made by different ranks tile the whole volume.  centres_zyx_sigma: 6 x (cz, cy,

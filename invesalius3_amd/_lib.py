@@ -39,6 +39,19 @@ class FloodPlan(ctypes.Structure):
     _fields_ = [("dz", c_i64), ("dy", c_i64), ("dx", c_i64), ("wx", c_i64), ("strct_bits", ctypes.c_uint32)]
 
 
+class VolrenParams(ctypes.Structure):
+    """struct ivx_volren_params (include/ivx.h)."""
+    _fields_ = [
+        ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("mip", ctypes.c_int32), ("shade", ctypes.c_int32),
+        ("skip", ctypes.c_int32), ("n_table", ctypes.c_int32), ("out_u8", ctypes.c_int32), ("clip", ctypes.c_int32),
+        ("origin", ctypes.c_double * 3), ("du", ctypes.c_double * 3), ("dv", ctypes.c_double * 3),
+        ("dir", ctypes.c_double * 3), ("spacing", ctypes.c_double * 3), ("dt", ctypes.c_double),
+        ("ambient", ctypes.c_double), ("diffuse", ctypes.c_double), ("specular", ctypes.c_double),
+        ("specular_power", ctypes.c_double), ("background", ctypes.c_double * 3), ("clip_normal", ctypes.c_double * 3),
+        ("clip_origin", ctypes.c_double * 3),
+    ]
+
+
 _lib = None
 
 

@@ -1,0 +1,474 @@
+// k_volren.hip -- volume rendering of the 3-D view (invesalius/data/volume.py:575-707, Volume.LoadVolume with
+// vtkFixedPointVolumeRayCastMapper) and the volume histogram (CalculateHistogram, :723-735).
+//
+// prepare: uint16(img + shift), then the preset's "Basic Smooth 5x5" passes per XY slice (float64, row-major taps,
+//          out-of-volume taps skipped, truncated toward zero: bit for bit with tests/_volren_ref.py).
+// cells:   min / max of the prepared field per 8^3 macro cell, one voxel of apron on every side.
+// render:  one lane per ray, 8x8 pixel tiles per wave; parallel rays, samples t_in + k dt (from k, never accumulated),
+//          trilinear interpolation, classification by linear interpolation of the baked table, optional headlight
+//          shading from central differences, front-to-back compositing with early termination at A >= 1 - 2^-12, or the
+//          maximum intensity.  Empty-space skipping jumps over macro cells whose table entries [min - 1, max + 1] are all
+//          transparent (MIP: whose max cannot raise the running maximum); a jump lands only where every skipped sample
+//          lies in the cell, so skipping changes no bit.
+// histogram: uint64 counts, privatised in LDS where the bins fit; integer atomics only.
+#include "ivx_internal.h"
+
+using namespace ivx;
+
+namespace {
+
+constexpr int CELL = IVX_VOLREN_CELL;
+constexpr int TILE = 8;                        // render tile edge: 64 rays = one wave
+constexpr float OPAQUE = 1.0f - 1.0f / 4096.0f; // early ray termination
+constexpr int HIST_LDS_BINS = 16384;           // 64 KiB of uint32 counters
+
+struct Kern25 {
+    double w[25];
+};
+
+// volume.py:52-81 "Basic Smooth 5x5"
+const double BASIC_SMOOTH_5X5[25] = {1, 1, 1, 1, 1, 1, 4, 4, 4, 1, 1, 4, 12, 4, 1, 1, 4, 4, 4, 1, 1, 1, 1, 1, 1};
+
+struct Dims {
+    int nz, ny, nx;
+};
+
+__global__ __launch_bounds__(256) void k_vr_shift(const int16_t *__restrict__ img, int64_t n, int shift,
+                                                 uint16_t *__restrict__ out) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = (uint16_t)((int)img[i] + shift);
+}
+
+// vtkImageConvolve's 5x5 kernel on every XY slice; block (64, 4) of one slice
+__global__ __launch_bounds__(256) void k_vr_smooth(const uint16_t *__restrict__ in, uint16_t *__restrict__ out, Dims d,
+                                                  Kern25 k) {
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y, z = blockIdx.z;
+    if (x >= d.nx || y >= d.ny) return;
+    const uint16_t *sl = in + (int64_t)z * d.ny * d.nx;
+    double acc = 0.0;
+    for (int ky = 0; ky < 5; ky++) {
+        const int yy = y + ky - 2;
+        if (yy < 0 || yy >= d.ny) continue;
+        for (int kx = 0; kx < 5; kx++) {
+            const int xx = x + kx - 2;
+            if (xx < 0 || xx >= d.nx) continue;
+            acc = acc + k.w[ky * 5 + kx] * (double)sl[(int64_t)yy * d.nx + xx];
+        }
+    }
+    out[((int64_t)z * d.ny + y) * d.nx + x] = (uint16_t)acc;
+}
+
+__global__ __launch_bounds__(256) void k_vr_cells(const uint16_t *__restrict__ v, Dims d, Dims c,
+                                                 uint16_t *__restrict__ cells) {
+    const int64_t ci = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t ncell = (int64_t)c.nz * c.ny * c.nx;
+    if (ci >= ncell) return;
+    const int cx = (int)(ci % c.nx), cy = (int)((ci / c.nx) % c.ny), cz = (int)(ci / ((int64_t)c.nx * c.ny));
+    const int x0 = max(cx * CELL - 1, 0), x1 = min(cx * CELL + CELL, d.nx - 1);
+    const int y0 = max(cy * CELL - 1, 0), y1 = min(cy * CELL + CELL, d.ny - 1);
+    const int z0 = max(cz * CELL - 1, 0), z1 = min(cz * CELL + CELL, d.nz - 1);
+    unsigned lo = 0xffffu, hi = 0;
+    for (int z = z0; z <= z1; z++)
+        for (int y = y0; y <= y1; y++) {
+            const uint16_t *row = v + ((int64_t)z * d.ny + y) * d.nx;
+            for (int x = x0; x <= x1; x++) {
+                const unsigned s = row[x];
+                lo = min(lo, s);
+                hi = max(hi, s);
+            }
+        }
+    cells[2 * ci] = (uint16_t)lo;
+    cells[2 * ci + 1] = (uint16_t)hi;
+}
+
+__device__ __forceinline__ float lerpf(float a, float b, float f) { return a + f * (b - a); }
+
+// trilinear interpolation at index position (x, y, z), already clamped to the volume
+__device__ __forceinline__ float tri(const uint16_t *__restrict__ v, const Dims &d, float x, float y, float z) {
+    int x0 = (int)x, y0 = (int)y, z0 = (int)z;
+    x0 = min(x0, max(d.nx - 2, 0));
+    y0 = min(y0, max(d.ny - 2, 0));
+    z0 = min(z0, max(d.nz - 2, 0));
+    const float fx = x - (float)x0, fy = y - (float)y0, fz = z - (float)z0;
+    const int x1 = min(x0 + 1, d.nx - 1), y1 = min(y0 + 1, d.ny - 1), z1 = min(z0 + 1, d.nz - 1);
+    const int64_t sy = d.nx, sz = (int64_t)d.ny * d.nx;
+    const uint16_t *p00 = v + z0 * sz + y0 * sy, *p01 = v + z0 * sz + y1 * sy;
+    const uint16_t *p10 = v + z1 * sz + y0 * sy, *p11 = v + z1 * sz + y1 * sy;
+    const float c00 = lerpf((float)p00[x0], (float)p00[x1], fx);
+    const float c01 = lerpf((float)p01[x0], (float)p01[x1], fx);
+    const float c10 = lerpf((float)p10[x0], (float)p10[x1], fx);
+    const float c11 = lerpf((float)p11[x0], (float)p11[x1], fx);
+    return lerpf(lerpf(c00, c01, fy), lerpf(c10, c11, fy), fz);
+}
+
+__device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
+
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
+
+struct RayCtx {
+    float I0[3], S[3]; // index position of sample 0 and step per sample
+    long long kmax;    // last sample index (-1: no sample)
+};
+
+// the ray of pixel (px, py) in index space and its samples' range; false = the ray misses
+__device__ bool setup_ray(const ivx_volren_params &p, const Dims &d, int px, int py, RayCtx &r) {
+    double P0[3], A[3], B[3];
+    for (int a = 0; a < 3; a++) P0[a] = p.origin[a] + (double)px * p.du[a] + (double)py * p.dv[a];
+    A[0] = P0[0] / p.spacing[0];
+    A[1] = -P0[1] / p.spacing[1];
+    A[2] = P0[2] / p.spacing[2];
+    B[0] = p.dir[0] / p.spacing[0];
+    B[1] = -p.dir[1] / p.spacing[1];
+    B[2] = p.dir[2] / p.spacing[2];
+    const double hi[3] = {(double)(d.nx - 1), (double)(d.ny - 1), (double)(d.nz - 1)};
+    double tin = -1e300, tout = 1e300;
+    for (int a = 0; a < 3; a++) {
+        if (B[a] != 0.0) {
+            double t0 = (0.0 - A[a]) / B[a], t1 = (hi[a] - A[a]) / B[a];
+            if (t0 > t1) {
+                const double t = t0;
+                t0 = t1;
+                t1 = t;
+            }
+            tin = fmax(tin, t0);
+            tout = fmin(tout, t1);
+        } else if (A[a] < 0.0 || A[a] > hi[a]) {
+            return false;
+        }
+    }
+    if (p.clip) {
+        double nd = 0.0, c0 = 0.0;
+        for (int a = 0; a < 3; a++) {
+            nd += p.clip_normal[a] * p.dir[a];
+            c0 += p.clip_normal[a] * (P0[a] - p.clip_origin[a]);
+        }
+        if (nd > 0.0) tin = fmax(tin, -c0 / nd);
+        else if (nd < 0.0) tout = fmin(tout, -c0 / nd);
+        else if (c0 < 0.0) return false;
+    }
+    if (!(tin <= tout)) return false;
+    r.kmax = (long long)floor((tout - tin) / p.dt);
+    for (int a = 0; a < 3; a++) {
+        r.I0[a] = (float)(A[a] + tin * B[a]);
+        r.S[a] = (float)(B[a] * p.dt);
+    }
+    return true;
+}
+
+__device__ __forceinline__ void sample_pos(const RayCtx &r, const Dims &d, long long k, float &x, float &y, float &z) {
+    const float fk = (float)k;
+    x = clampf(r.I0[0] + fk * r.S[0], 0.0f, (float)(d.nx - 1));
+    y = clampf(r.I0[1] + fk * r.S[1], 0.0f, (float)(d.ny - 1));
+    z = clampf(r.I0[2] + fk * r.S[2], 0.0f, (float)(d.nz - 1));
+}
+
+// Samples k + 1 .. (returned) - 1 lie in the same macro cell as sample k (cell index (cx, cy, cz)): the landing sample
+// is the first one at or past the cell's exit plane, accepted only if the sample before it is still in the cell (the
+// positions are monotone in k along every axis, so then every sample in between is too); else k + 1.
+__device__ __forceinline__ long long cell_exit(const RayCtx &r, const Dims &d, long long k, int cx, int cy, int cz) {
+    const int c[3] = {cx, cy, cz};
+    float kk = 3.0e38f;
+    for (int a = 0; a < 3; a++) {
+        if (r.S[a] > 0.0f) kk = fminf(kk, ((float)((c[a] + 1) * CELL) - r.I0[a]) / r.S[a]);
+        else if (r.S[a] < 0.0f) kk = fminf(kk, ((float)(c[a] * CELL) - r.I0[a]) / r.S[a]);
+    }
+    if (!(kk < 9.0e18f)) return r.kmax + 1;
+    long long kn = (long long)floorf(kk);
+    if (kn <= k + 1) return k + 1;
+    float x, y, z;
+    sample_pos(r, d, kn - 1, x, y, z);
+    if ((int)x / CELL != cx || (int)y / CELL != cy || (int)z / CELL != cz) return k + 1;
+    return kn;
+}
+
+__global__ __launch_bounds__(64) void k_vr_render(const uint16_t *__restrict__ v, const uint16_t *__restrict__ cells, Dims d,
+                                                 Dims c, const float4 *__restrict__ table, const float *__restrict__ alpha,
+                                                 const uint32_t *__restrict__ prefix, ivx_volren_params p, void *out,
+                                                 unsigned long long *stats) {
+    const int px = blockIdx.x * TILE + (threadIdx.x & (TILE - 1));
+    const int py = blockIdx.y * TILE + (threadIdx.x / TILE);
+    const bool active = px < p.width && py < p.height;
+    unsigned long long n_taken = 0, n_skipped = 0, n_early = 0, n_hit = 0;
+    float r = (float)p.background[0], g = (float)p.background[1], b = (float)p.background[2], A = 0.0f;
+    RayCtx ray;
+    if (active && setup_ray(p, d, px, py, ray)) {
+        n_hit = 1;
+        const int nt = p.n_table;
+        const float vmaxf = (float)(nt - 2);
+        if (p.mip) {
+            float vmax = -1.0f;
+            for (long long k = 0; k <= ray.kmax;) {
+                float x, y, z;
+                sample_pos(ray, d, k, x, y, z);
+                if (p.skip) {
+                    const int cx = (int)x / CELL, cy = (int)y / CELL, cz = (int)z / CELL;
+                    const int64_t ci = ((int64_t)cz * c.ny + cy) * c.nx + cx;
+                    if ((float)cells[2 * ci + 1] <= vmax) {
+                        const long long kn = cell_exit(ray, d, k, cx, cy, cz);
+                        n_skipped += (unsigned long long)(kn - k);
+                        k = kn;
+                        continue;
+                    }
+                }
+                const float s = tri(v, d, x, y, z);
+                n_taken++;
+                if (s > vmax) vmax = s;
+                k++;
+            }
+            if (vmax >= 0.0f) {
+                const float s = fminf(vmax, vmaxf + 1.0f);
+                const int i0 = min((int)s, nt - 2);
+                const float f = s - (float)i0;
+                const float4 e0 = table[i0], e1 = table[i0 + 1];
+                const float a = lerpf(alpha[i0], alpha[i0 + 1], f);
+                r = a * lerpf(e0.x, e1.x, f) + (1.0f - a) * r;
+                g = a * lerpf(e0.y, e1.y, f) + (1.0f - a) * g;
+                b = a * lerpf(e0.z, e1.z, f) + (1.0f - a) * b;
+                A = a;
+            }
+        } else {
+            const float ka = (float)p.ambient, kd = (float)p.diffuse, ks = (float)p.specular, pw = (float)p.specular_power;
+            const float dx = (float)p.dir[0], dy = (float)p.dir[1], dz = (float)p.dir[2];
+            const float isx = (float)(0.5 / p.spacing[0]), isy = (float)(0.5 / p.spacing[1]), isz = (float)(0.5 / p.spacing[2]);
+            const float hx = (float)(d.nx - 1), hy = (float)(d.ny - 1), hz = (float)(d.nz - 1);
+            float ar = 0.0f, ag = 0.0f, ab = 0.0f;
+            for (long long k = 0; k <= ray.kmax;) {
+                float x, y, z;
+                sample_pos(ray, d, k, x, y, z);
+                if (p.skip) {
+                    const int cx = (int)x / CELL, cy = (int)y / CELL, cz = (int)z / CELL;
+                    const int64_t ci = ((int64_t)cz * c.ny + cy) * c.nx + cx;
+                    const int lo = max((int)cells[2 * ci] - 1, 0), hi = min((int)cells[2 * ci + 1] + 1, nt - 1);
+                    if (prefix[hi + 1] == prefix[lo]) {
+                        const long long kn = cell_exit(ray, d, k, cx, cy, cz);
+                        n_skipped += (unsigned long long)(kn - k);
+                        k = kn;
+                        continue;
+                    }
+                }
+                const float s = tri(v, d, x, y, z);
+                n_taken++;
+                const int i0 = min((int)s, nt - 2);
+                const float f = s - (float)i0;
+                const float4 e0 = table[i0], e1 = table[i0 + 1];
+                const float a = lerpf(e0.w, e1.w, f);
+                if (a > 0.0f) {
+                    float cr = lerpf(e0.x, e1.x, f), cg = lerpf(e0.y, e1.y, f), cb = lerpf(e0.z, e1.z, f);
+                    if (p.shade) {
+                        // gradient in world axes: world y = -index y
+                        const float gx = (tri(v, d, fminf(x + 1.0f, hx), y, z) - tri(v, d, fmaxf(x - 1.0f, 0.0f), y, z)) * isx;
+                        const float gy = (tri(v, d, x, fmaxf(y - 1.0f, 0.0f), z) - tri(v, d, x, fminf(y + 1.0f, hy), z)) * isy;
+                        const float gz = (tri(v, d, x, y, fminf(z + 1.0f, hz)) - tri(v, d, x, y, fmaxf(z - 1.0f, 0.0f))) * isz;
+                        const float gn = sqrtf(gx * gx + gy * gy + gz * gz);
+                        float ndl = 0.0f;
+                        if (gn > 0.0f) ndl = fabsf(gx * dx + gy * dy + gz * dz) / gn;
+                        const float diff = ka + kd * ndl;
+                        const float spec = ndl > 0.0f ? ks * powf(ndl, pw) : 0.0f;
+                        cr = clampf(cr * diff + spec, 0.0f, 1.0f);
+                        cg = clampf(cg * diff + spec, 0.0f, 1.0f);
+                        cb = clampf(cb * diff + spec, 0.0f, 1.0f);
+                    }
+                    const float w = (1.0f - A) * a;
+                    ar += w * cr;
+                    ag += w * cg;
+                    ab += w * cb;
+                    A += w;
+                    if (A >= OPAQUE) {
+                        n_early = 1;
+                        break;
+                    }
+                }
+                k++;
+            }
+            r = ar + (1.0f - A) * r;
+            g = ag + (1.0f - A) * g;
+            b = ab + (1.0f - A) * b;
+        }
+    }
+    if (active) {
+        const int64_t o = ((int64_t)py * p.width + px) * 4;
+        if (p.out_u8) {
+            uint8_t *q = (uint8_t *)out + o;
+            const float vals[4] = {r, g, b, A};
+            for (int i = 0; i < 4; i++) q[i] = (uint8_t)clampf(floorf(255.0f * vals[i] + 0.5f), 0.0f, 255.0f);
+        } else {
+            float *q = (float *)out + o;
+            q[0] = r;
+            q[1] = g;
+            q[2] = b;
+            q[3] = A;
+        }
+    }
+    if (stats) {
+        n_taken = wave_sum(n_taken);
+        n_skipped = wave_sum(n_skipped);
+        n_early = wave_sum(n_early);
+        n_hit = wave_sum(n_hit);
+        if (threadIdx.x == 0) {
+            atomicAdd(stats + 0, n_taken);
+            atomicAdd(stats + 1, n_skipped);
+            atomicAdd(stats + 2, n_early);
+            atomicAdd(stats + 3, n_hit);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_vr_hist_lds(const int16_t *__restrict__ img, int64_t n, int lo, int nbins,
+                                                    unsigned long long *__restrict__ counts) {
+    __shared__ uint32_t bins[HIST_LDS_BINS];
+    for (int i = threadIdx.x; i < nbins; i += blockDim.x) bins[i] = 0;
+    __syncthreads();
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int b = (int)img[i] - lo;
+        if (b >= 0 && b < nbins) atomicAdd(&bins[b], 1u);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nbins; i += blockDim.x)
+        if (bins[i]) atomicAdd(counts + i, (unsigned long long)bins[i]);
+}
+
+__global__ __launch_bounds__(256) void k_vr_hist_global(const int16_t *__restrict__ img, int64_t n, int lo, int nbins,
+                                                       unsigned long long *__restrict__ counts) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int b = (int)img[i] - lo;
+        if (b >= 0 && b < nbins) atomicAdd(counts + b, 1ull);
+    }
+}
+
+int check_shape(const int64_t shape[3], Dims &d) {
+    IVX_REQUIRE(shape, IVX_EINVAL, "volren: null shape");
+    for (int a = 0; a < 3; a++)
+        IVX_REQUIRE(shape[a] >= 1 && shape[a] <= 32768, IVX_EINVAL, "volren: shape[%d] = %lld", a, (long long)shape[a]);
+    d.nz = (int)shape[0];
+    d.ny = (int)shape[1];
+    d.nx = (int)shape[2];
+    return IVX_OK;
+}
+
+Dims cell_dims(const Dims &d) {
+    return Dims{(int)cdiv(d.nz, CELL), (int)cdiv(d.ny, CELL), (int)cdiv(d.nx, CELL)};
+}
+
+int check_params(const ivx_volren_params *p) {
+    IVX_REQUIRE(p, IVX_EINVAL, "volren: null params");
+    IVX_REQUIRE(p->width >= 1 && p->height >= 1 && p->width <= 32768 && p->height <= 32768, IVX_EINVAL,
+                "volren: viewport %d x %d", p->width, p->height);
+    IVX_REQUIRE(p->n_table >= 2 && p->n_table <= 65537, IVX_EINVAL, "volren: n_table %d (2 .. 65537)", p->n_table);
+    IVX_REQUIRE(p->dt > 0.0 && p->spacing[0] > 0.0 && p->spacing[1] > 0.0 && p->spacing[2] > 0.0, IVX_EINVAL,
+                "volren: sample distance and spacing must be positive");
+    const double dn = p->dir[0] * p->dir[0] + p->dir[1] * p->dir[1] + p->dir[2] * p->dir[2];
+    IVX_REQUIRE(dn > 0.5 && dn < 2.0, IVX_EINVAL, "volren: ray direction must be a unit vector");
+    return IVX_OK;
+}
+
+} // namespace
+
+extern "C" int ivx_dev_volren_prepare(const int16_t *img, const int64_t shape[3], int shift, int nsmooth, uint16_t *out,
+                                      uint16_t *scratch, void *stream) {
+    Dims d;
+    int rc;
+    if ((rc = check_shape(shape, d))) return rc;
+    IVX_REQUIRE(img && out && (void *)img != (void *)out, IVX_EINVAL, "volren: prepare needs distinct in / out buffers");
+    IVX_REQUIRE(nsmooth >= 0 && nsmooth <= 64, IVX_EINVAL, "volren: %d smoothing passes", nsmooth);
+    IVX_REQUIRE(nsmooth < 1 || (scratch && (void *)scratch != (void *)out), IVX_EINVAL, "volren: prepare needs scratch");
+    IVX_REQUIRE(shift >= 0 && shift <= 65535, IVX_EINVAL, "volren: shift %d", shift);
+    const int64_t n = (int64_t)d.nz * d.ny * d.nx;
+    hipStream_t st = S(stream);
+    // shift, then the passes ping-pong between out and scratch so that the last write lands in out
+    uint16_t *bufs[2] = {out, scratch};
+    int cur = nsmooth & 1;
+    hipLaunchKernelGGL(k_vr_shift, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, img, n, shift, bufs[cur]);
+    IVX_LAUNCH_CHECK();
+    Kern25 k;
+    for (int i = 0; i < 25; i++) k.w[i] = BASIC_SMOOTH_5X5[i] / 60.0;
+    dim3 grid((unsigned)cdiv(d.nx, 64), (unsigned)cdiv(d.ny, 4), (unsigned)d.nz);
+    for (int pass = 0; pass < nsmooth; pass++) {
+        const uint16_t *src = bufs[cur];
+        cur ^= 1;
+        hipLaunchKernelGGL(k_vr_smooth, grid, dim3(64, 4), 0, st, src, bufs[cur], d, k);
+        IVX_LAUNCH_CHECK();
+    }
+    return IVX_OK;
+}
+
+extern "C" int ivx_dev_volren_cells(const uint16_t *vol, const int64_t shape[3], uint16_t *cells, void *stream) {
+    Dims d;
+    int rc;
+    if ((rc = check_shape(shape, d))) return rc;
+    IVX_REQUIRE(vol && cells, IVX_EINVAL, "volren: null buffer");
+    const Dims c = cell_dims(d);
+    const int64_t nc = (int64_t)c.nz * c.ny * c.nx;
+    hipLaunchKernelGGL(k_vr_cells, dim3((unsigned)cdiv(nc, 256)), dim3(256), 0, S(stream), vol, d, c, cells);
+    IVX_LAUNCH_CHECK();
+    return IVX_OK;
+}
+
+extern "C" int ivx_dev_volren_render(const uint16_t *vol, const uint16_t *cells, const int64_t shape[3], const float *table,
+                                     const float *alpha, const uint32_t *prefix, const ivx_volren_params *p, void *out,
+                                     uint64_t *stats, void *stream) {
+    Dims d;
+    int rc;
+    if ((rc = check_shape(shape, d)) || (rc = check_params(p))) return rc;
+    IVX_REQUIRE(vol && table && alpha && out, IVX_EINVAL, "volren: null buffer");
+    IVX_REQUIRE(!p->skip || (cells && prefix), IVX_EINVAL, "volren: skipping needs the cells and the prefix counts");
+    const Dims c = cell_dims(d);
+    dim3 grid((unsigned)cdiv(p->width, TILE), (unsigned)cdiv(p->height, TILE));
+    hipLaunchKernelGGL(k_vr_render, grid, dim3(TILE * TILE), 0, S(stream), vol, cells, d, c, (const float4 *)table, alpha,
+                       prefix, *p, out, (unsigned long long *)stats);
+    IVX_LAUNCH_CHECK();
+    return IVX_OK;
+}
+
+extern "C" int ivx_dev_volren_histogram(const int16_t *img, int64_t n, int lo, int nbins, uint64_t *counts, void *stream) {
+    IVX_REQUIRE(n >= 0 && nbins >= 0 && nbins <= 65536, IVX_EINVAL, "volren: histogram of %lld voxels, %d bins", (long long)n,
+                nbins);
+    if (nbins == 0) return IVX_OK;
+    IVX_REQUIRE(img && counts, IVX_EINVAL, "volren: null buffer");
+    hipStream_t st = S(stream);
+    IVX_HIP(hipMemsetAsync(counts, 0, (size_t)nbins * 8, st));
+    if (n == 0) return IVX_OK;
+    const int64_t nb = cdiv(n, 256 * 16);
+    const unsigned blocks = (unsigned)(nb < 2048 ? nb : 2048);
+    if (nbins <= HIST_LDS_BINS)
+        hipLaunchKernelGGL(k_vr_hist_lds, dim3(blocks), dim3(256), 0, st, img, n, lo, nbins, (unsigned long long *)counts);
+    else
+        hipLaunchKernelGGL(k_vr_hist_global, dim3(blocks), dim3(256), 0, st, img, n, lo, nbins, (unsigned long long *)counts);
+    IVX_LAUNCH_CHECK();
+    return IVX_OK;
+}
+
+extern "C" int ivx_volume_render(const int16_t *img, const int64_t shape[3], const int64_t strides[3], int shift, int nsmooth,
+                                 const float *table, const float *alpha, const uint32_t *prefix, const ivx_volren_params *p,
+                                 void *out) {
+    HostCallGuard guard;
+    Dims d;
+    int rc;
+    if ((rc = check_shape(shape, d)) || (rc = check_params(p))) return rc;
+    IVX_REQUIRE(img && strides && table && alpha && prefix && out, IVX_EINVAL, "volren: null buffer");
+    const int64_t n = (int64_t)d.nz * d.ny * d.nx;
+    const Dims c = cell_dims(d);
+    const size_t ncell = (size_t)c.nz * c.ny * c.nx;
+    const size_t nt = (size_t)p->n_table;
+    const size_t tb = nt * 16, ab = nt * 4, pb = (nt + 1) * 4;
+    const size_t ob = (size_t)p->width * p->height * 4 * (p->out_u8 ? 1 : 4);
+    void *d_in, *d_vol, *d_s, *d_cells, *d_lut, *d_out;
+    if ((rc = ws_get(WS_IN, (size_t)n * 2, &d_in)) || (rc = ws_get(WS_AUX0, (size_t)n * 2, &d_vol)) ||
+        (rc = ws_get(WS_AUX1, (size_t)n * 2, &d_s)) || (rc = ws_get(WS_AUX2, ncell * 4, &d_cells)) ||
+        (rc = ws_get(WS_LUT, tb + ab + pb, &d_lut)) || (rc = ws_get(WS_OUT, ob, &d_out)))
+        return rc;
+    if ((rc = upload_strided(d_in, img, shape, strides, 2, WS_IN))) return rc;
+    char *lut = (char *)d_lut;
+    if ((rc = copy_h2d(lut, table, tb)) || (rc = copy_h2d(lut + tb, alpha, ab)) || (rc = copy_h2d(lut + tb + ab, prefix, pb)))
+        return rc;
+    if ((rc = ivx_dev_volren_prepare((const int16_t *)d_in, shape, shift, nsmooth, (uint16_t *)d_vol, (uint16_t *)d_s, nullptr)))
+        return rc;
+    if ((rc = ivx_dev_volren_cells((const uint16_t *)d_vol, shape, (uint16_t *)d_cells, nullptr))) return rc;
+    if ((rc = ivx_dev_volren_render((const uint16_t *)d_vol, (const uint16_t *)d_cells, shape, (const float *)lut,
+                                    (const float *)(lut + tb), (const uint32_t *)(lut + tb + ab), p, d_out, nullptr, nullptr)))
+        return rc;
+    IVX_HIP(hipDeviceSynchronize());
+    return copy_d2h(out, d_out, ob);
+}

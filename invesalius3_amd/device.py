@@ -222,6 +222,7 @@ class DeviceVolume:
     def _image_touched(self):
         self._mbits_range = None
         self._range_valid = False
+        self._drop_volren()
 
     def _mask_touched(self):
         self._mbits_valid = False
@@ -273,6 +274,7 @@ class DeviceVolume:
         self._sync_events = []
         for b in (self.image, self.mask, self.out_mask):
             b._on_touch = None  # freeing is not "somebody looked at the contents"
+        self._drop_volren(all_buffers=True)
         for b in (self.image, self.mask, self.out_mask, self.cand, self.reached, self._mbits, self.flood_scratch,
                   self._mc_scratch, self._tris, self._verts, self._faces, self._gate, getattr(self, "_range_buf", None),
                   getattr(self, "prob", None)):
@@ -900,6 +902,123 @@ class DeviceVolume:
         L.check(L.lib().ivx_dev_segment_threshold(self.prob.ptr, L.i64(self.shape), ctypes.c_float(float(threshold)),
                                                   self.mask.ptr, L.i64([self.dy * self.dx, self.dx, 1]), 0, self.stream),
                 "segment_threshold")
+
+    # -- volume rendering (Volume.LoadVolume, volume.py:575-707; CalculateHistogram, :723-735) ---------------------------
+    def _drop_volren(self, all_buffers: bool = False):
+        """The prepared field and its macro cells depend on the image; the table, output and stats buffers do not."""
+        vr = getattr(self, "_vr", None)
+        if vr is not None:
+            for b in (vr["vol"], vr["cells"]):
+                b.close()
+            self._vr = None
+        if all_buffers:
+            for name in ("_vr_table", "_vr_out", "_vr_stats"):
+                b = getattr(self, name, None)
+                if b is not None:
+                    b.close()
+                setattr(self, name, None)
+
+    def _image_scale(self):
+        """(min, max) of the resident image as integers (GetScalarRange of LoadVolume)"""
+        rng = np.empty(2, np.float32)
+        buf = self.image_range()
+        self.sync()
+        buf.download((2,), np.float32, rng)
+        return int(rng[0]), int(rng[1])
+
+    def _volren_field(self, shift: int, kernels) -> dict:
+        """The prepared uint16 field (shift + the preset's smoothing passes) and its macro cells, kept per (shift, filter
+        list) until the image changes: a camera move or a WW/WL change only re-bakes the table."""
+        from . import volume as V
+
+        key = (int(shift), len(kernels))
+        vr = getattr(self, "_vr", None)
+        if vr is not None and vr["key"] == key:
+            return vr
+        self._drop_volren()
+        cshape = [-(-s // V.CELL) for s in self.shape]
+        vol, cells = DeviceBuffer(self.n * 2), DeviceBuffer(int(np.prod(cshape)) * 4)
+        scratch = DeviceBuffer(self.n * 2) if kernels else None
+        try:
+            lib, shape = L.lib(), L.i64(self.shape)
+            L.check(lib.ivx_dev_volren_prepare(self.image.raw, shape, int(shift), len(kernels), vol.ptr,
+                                               None if scratch is None else scratch.ptr, self.stream), "volren_prepare")
+            L.check(lib.ivx_dev_volren_cells(vol.ptr, shape, cells.ptr, self.stream), "volren_cells")
+            self.sync()  # scratch goes out of scope here
+        except Exception:
+            vol.close()
+            cells.close()
+            raise
+        finally:
+            if scratch is not None:
+                scratch.close()
+        self._vr = {"key": key, "vol": vol, "cells": cells, "cshape": cshape}
+        return self._vr
+
+    @staticmethod
+    def _grow(owner, name, nbytes):
+        b = getattr(owner, name, None)
+        if b is None or b.nbytes < nbytes:
+            if b is not None:
+                b.close()
+            b = DeviceBuffer(nbytes)
+            setattr(owner, name, b)
+        return b
+
+    def render_volume(self, preset, camera, size, clip_plane=None, shade=None, color_lists=None, download: bool = True,
+                      rgba8: bool = False, presets_dir=None):
+        """The 3-D view of the resident image with a raycasting preset (a dict, a .plist path, or a name in
+        `presets_dir`).  `camera`: a standard view name ("front", "back", "left", "right", "top", "bottom", "iso") or a
+        dict from volume.camera_for_view; `size` (width, height) in pixels.  `shade` None follows the preset's useShading
+        (see volume.shading).  Returns (height, width, 4) float32 RGBA (uint8 with `rgba8`), or the device buffer when not
+        `download`.  The sample counts of the render are left in ``last_render_stats``."""
+        from . import volume as V
+
+        w, h = int(size[0]), int(size[1])
+        if isinstance(camera, str):
+            cam = V.camera_for_view(camera, self.shape, self.spacing, (w, h))
+        else:
+            cam = dict(camera, viewport=(w, h))
+        scale = self._image_scale()
+        setup = V.render_setup(preset, scale, cam, clip_plane, shade, color_lists, presets_dir)
+        vr = self._volren_field(setup["shift"], setup["kernels"])
+        rgba, alpha, prefix = V.device_tables(setup)
+        tb = self._grow(self, "_vr_table", rgba.nbytes + alpha.nbytes + prefix.nbytes)
+        lib = L.lib()
+        self.sync()  # the table buffer may still be read by the previous render
+        host = np.concatenate([rgba.view(np.uint8).ravel(), alpha.view(np.uint8).ravel(), prefix.view(np.uint8).ravel()])
+        tb.upload(host)
+        p = V.volren_params(setup, self.spacing, rgba8)
+        out = self._grow(self, "_vr_out", w * h * 4 * (1 if rgba8 else 4))
+        stats = self._grow(self, "_vr_stats", 32)
+        stats.zero(self.stream, 32)
+        L.check(lib.ivx_dev_volren_render(vr["vol"].ptr, vr["cells"].ptr, L.i64(self.shape), tb.ptr,
+                                          tb.at(rgba.nbytes), tb.at(rgba.nbytes + alpha.nbytes), ctypes.byref(p), out.ptr,
+                                          stats.ptr, self.stream), "render_volume")
+        self._vr_setup = setup
+        if not download:
+            return out
+        self.sync()
+        st = stats.download((4,), np.uint64)
+        self.last_render_stats = {"samples": int(st[0]), "skipped": int(st[1]), "early": int(st[2]), "rays_hit": int(st[3]),
+                                  "rays": w * h}
+        return out.download((h, w, 4), np.uint8 if rgba8 else np.float32)
+
+    def volume_histogram(self) -> np.ndarray:
+        """CalculateHistogram (volume.py:723-735) of the resident image: uint64 counts of the int(max - min) unit bins
+        from min (voxels equal to max are not counted; a constant image gives an empty histogram)."""
+        lo, hi = self._image_scale()
+        nb = hi - lo
+        if nb <= 0:
+            return np.zeros(0, np.uint64)
+        counts = DeviceBuffer(nb * 8)
+        try:
+            L.check(L.lib().ivx_dev_volren_histogram(self.image.raw, c64(self.n), int(lo), int(nb), counts.ptr, self.stream),
+                    "volume_histogram")
+            self.sync()
+            return counts.download((nb,), np.uint64)
+        finally:
+            counts.close()
 
     def mida(self, axis: int, wl, ww, out: DeviceBuffer, status: DeviceBuffer):
         """mida (mips.rs:102-168) of the resident image along `axis` into `out` (int16 image of the projection's shape); the

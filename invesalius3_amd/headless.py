@@ -4,9 +4,10 @@
         --stl bone.stl --save CASE_out.inv3
     python -m invesalius3_amd.headless CASE.inv3 --filter median 3 --threshold 226 3071 --stl bone.stl
     python -m invesalius3_amd.headless CASE.inv3 --segment brain --weights brain_mri_t1.pt --stl brain.stl
+    python -m invesalius3_amd.headless CASE.inv3 --render "Bone + Skin" --presets-dir DIR --view iso --png out.png
 
 What the reference does through its GUI for the same result: Slice.SetMaskThreshold / do_threshold_to_all_slices
-(invesalius/data/slice_.py:1240-1247, 1739-1769), the Image Filters dialog (slice_.py:2330-2539), the deep-learning segmentation (segmentation/deep_learning/segment.py), the region-growing tool (styles.py:3151-3216),
+(invesalius/data/slice_.py:1240-1247, 1739-1769), the Image Filters dialog (slice_.py:2330-2539), the deep-learning segmentation (segmentation/deep_learning/segment.py), the 3-D view's volume rendering (data/volume.py:575-707), the region-growing tool (styles.py:3151-3216),
 SurfaceManager.AddNewActor -> create_surface_piece / join_process_surface (surface.py:1362-1380,
 surface_process.py:71-472) and vtkSTLWriter (surface.py:1827-1829).  No wx, no VTK here; one JSON line on stdout."""
 from __future__ import annotations
@@ -14,6 +15,7 @@ from __future__ import annotations
 import argparse
 import ctypes
 import json
+import os
 import sys
 import time
 
@@ -49,6 +51,22 @@ def run(args) -> dict:
             if args.save:
                 vol.sync()
                 filtered = (vol.image.download(vol.shape, np.int16), ftype, fvalue, dimension, orientation)
+        if args.render is not None:
+            # the 3-D view (Volume.LoadVolume + the viewer's SetViewAngle, volume.py:575-707) of the resident image
+            from . import volume as V
+            pdir = args.presets_dir
+            if pdir is None and args.render.endswith(".plist"):
+                pdir = os.path.dirname(os.path.abspath(args.render))  # its colour lists sit next to it
+            w, h = args.size
+            with vol.timer.span("render"):
+                rgba8 = vol.render_volume(args.render, args.view, (w, h), presets_dir=pdir, rgba8=True)
+            out["render"] = {"preset": args.render, "view": args.view, "size": [w, h], **vol.last_render_stats}
+            if args.png:
+                V.write_png(args.png, rgba8)
+                out["render"]["png"] = args.png
+            if _render_only(args):
+                out["gpu_ms"] = {k: round(float(sum(v)), 4) for k, v in vol.timer.collect().items()}
+                return out
         segmented = False
         if args.segment is not None:
             # the Segmentation menu's deep-learning tool (BrainSegmentProcess / TracheaSegmentProcess, segment.py:505-541,
@@ -159,8 +177,14 @@ def run(args) -> dict:
     finally:
         vol.close()
         proj.close()
-    out["wall_s"] = round(time.perf_counter() - t_all, 3)
+        out["wall_s"] = round(time.perf_counter() - t_all, 3)
     return out
+
+
+def _render_only(args) -> bool:
+    """--render without anything that asks for a mask or a surface: the image is all there is to make"""
+    return (args.threshold is None and args.segment is None and not args.seed and not args.stl and not args.save
+            and not args.largest and not args.smooth and "--mask" not in (args.argv or []))
 
 
 def _strct(conn: int) -> np.ndarray:
@@ -188,6 +212,13 @@ def main(argv=None) -> int:
                          "(sigma, or the size parameter)" % ",".join(FILTER_TYPES))
     ap.add_argument("--filter-2d", choices=("axial", "coronal", "sagittal"), default=None,
                     help="filter slice by slice along this orientation instead of in 3-D")
+    ap.add_argument("--render", metavar="PRESET", default=None,
+                    help="volume-render the image (after --filter) with a raycasting preset: a .plist file, or a preset "
+                         "name looked up in --presets-dir")
+    ap.add_argument("--presets-dir", metavar="DIR", default=None, help="the raycasting presets directory (with color_list/)")
+    ap.add_argument("--view", choices=("front", "back", "left", "right", "top", "bottom", "iso"), default="iso")
+    ap.add_argument("--size", nargs=2, type=int, metavar=("W", "H"), default=(512, 512), help="image size (default 512 512)")
+    ap.add_argument("--png", metavar="OUT", default=None, help="write the rendered image as an RGBA PNG")
     ap.add_argument("--connectivity", type=int, choices=(6, 18, 26), default=26)
     ap.add_argument("--largest", action="store_true", help="keep the largest connected surface")
     ap.add_argument("--smooth", action="store_true", help="context-aware smoothing")
@@ -199,6 +230,7 @@ def main(argv=None) -> int:
     ap.add_argument("--save", help="write the project back with the new mask appended")
     ap.add_argument("--mask-name", default="GPU mask")
     args = ap.parse_args(argv)
+    args.argv = list(sys.argv[1:] if argv is None else argv)
     if args.segment is not None:
         if args.weights is None:
             ap.error("--segment needs --weights FILE")
@@ -217,6 +249,13 @@ def main(argv=None) -> int:
             ap.error("--filter VALUE must be a number")
     elif args.filter_2d is not None:
         ap.error("--filter-2d needs --filter")
+    if args.render is not None:
+        if not args.render.endswith(".plist") and args.presets_dir is None:
+            ap.error("--render NAME needs --presets-dir DIR (or give the .plist file)")
+        if args.size[0] <= 0 or args.size[1] <= 0:
+            ap.error("--size W H must be positive")
+    elif args.png is not None:
+        ap.error("--png needs --render")
     print(json.dumps(run(args)))
     return 0
 
