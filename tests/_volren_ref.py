@@ -174,7 +174,8 @@ def fixture():
 
 
 def synth_volume(shape, seed=0, shell=3):
-    """A CT-like int16 volume whose outer `shell` voxels sit at -1024 (transparent in every preset, smoothing included)"""
+    """A CT-like int16 volume whose outer `shell` voxels sit at -1024 (transparent in every preset, smoothing included);
+    `shell` 0 leaves the faces as generated"""
     rng = np.random.default_rng(seed)
     nz, ny, nx = shape
     z, y, x = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
@@ -188,7 +189,37 @@ def synth_volume(shape, seed=0, shell=3):
     f += 1100.0 * ((r > 0.55) & (r < 0.7))  # a skin-like shell
     f += rng.normal(0, 20, shape)
     img = np.clip(f, -1024, 3071).astype(np.int16)
-    img[:shell], img[-shell:], img[:, :shell], img[:, -shell:], img[:, :, :shell], img[:, :, -shell:] = (-1024,) * 6
+    if shell > 0:  # img[-0:] would be the whole array
+        img[:shell], img[-shell:], img[:, :shell], img[:, -shell:], img[:, :, :shell], img[:, :, -shell:] = (-1024,) * 6
     img[nz // 2, ny // 2, nx // 2] = 3071  # the range's top
     img[shell, shell, shell] = -1024
+    return img
+
+
+def cropped_ct(shape, seed=0):
+    """An int16 CT cut through the patient, with material on the box's faces, for any shape down to one voxel per axis
+    (voxel centres at (i + 0.5) / n of each axis): a body along z (skin, fat, soft tissue, lungs, two bones, a contrast
+    vessel, noise) that runs through the z = 0 and z = nz - 1 slices, and (ny >= 2) a dense table slab in the last rows
+    that touches the y = ny - 1 face and both x faces.  Values -1024 .. 3071, both present."""
+    rng = np.random.default_rng(seed)
+    nz, ny, nx = shape
+    z, y, x = np.meshgrid(*[(np.arange(n) + 0.5) / n for n in shape], indexing="ij")
+    f = np.full(shape, -1000.0)
+    r = np.hypot((x - 0.5) / 0.44, (y - 0.42) / 0.36)
+    f[r < 1.0] = 40.0                                         # soft tissue
+    f[(r >= 0.80) & (r < 0.92)] = -90.0                       # fat
+    f[(r >= 0.92) & (r < 1.0)] = 70.0                         # skin
+    for cx in (0.3, 0.7):
+        f[np.hypot((x - cx) / 0.13, (y - 0.34) / 0.12) < 1.0] = -550.0  # lungs (partial volume)
+    for cx, cy, rad in ((0.32, 0.5, 0.1), (0.7, 0.52, 0.08)):  # bones drifting with z: cortex, marrow
+        d = np.hypot(x - cx - 0.06 * np.sin(5.0 * z), y - cy) / rad
+        f[d < 1.0] = 1500.0 + 500.0 * z[d < 1.0]
+        f[d < 0.55] = 280.0
+    f[np.hypot(x - 0.45 - 0.1 * z, y - 0.3) < 0.05] = 330.0  # an oblique contrast vessel
+    f += rng.normal(0.0, 25.0, shape)
+    if ny >= 2:
+        t = ny - max(1, ny // 8)
+        f[:, t:, :] = 1400.0 + 300.0 * z[:, t:, :]  # the table
+    img = np.clip(f, -1024, 3071).astype(np.int16)
+    img.reshape(-1)[0], img.reshape(-1)[-1] = -1024, 3071  # the range's ends
     return img

@@ -192,6 +192,101 @@ def test_oracle_uniform_slab_closed_form():
     assert np.allclose(inside, expect, rtol=0, atol=1e-12)
 
 
+def _voxel_top_camera(shape, pitch):
+    """the top view with pixel pitch = the x / y spacing and one pixel of margin around odd x / y axes: every pixel
+    centre sits on a voxel column, the rim ones inside the x / y faces, the ring around them just outside the box"""
+    size = (shape[2] + 2, shape[1] + 2)
+    return dict(V.camera_for_view("top", shape, (pitch, pitch, 1.0), size), parallel_scale=size[1] * pitch / 2.0)
+
+
+def _ring(img):
+    r = np.ones(img.shape[:2], bool)
+    r[1:-1, 1:-1] = False
+    return r
+
+
+def _value_with_opacity(target):
+    """the field value whose baked a' (Standard at scale (-1024, 3071)) is nearest `target`"""
+    s = V.render_setup(PRESETS["Standard"], (-1024, 3071), _voxel_top_camera((3, 9, 11), 0.75), color_lists=CLUTS)
+    return int(np.argmin(np.abs(s["rgba"][:4096, 3] - target)))
+
+
+def _uniform_top(value, nz, **kw):
+    shape, spacing = (nz, 9, 11), (0.75, 0.75, 1.0)
+    s = V.render_setup(PRESETS["Standard"], (-1024, 3071), _voxel_top_camera(shape, 0.75), color_lists=CLUTS, **kw)
+    s["shade"] = False
+    w, h = s["viewport"]
+    py, px = np.mgrid[0:h, 0:w]
+    p = s["origin"] + px[..., None] * s["du"] + py[..., None] * s["dv"]
+    assert np.array_equal(np.unique(p[..., 0] / 0.75), np.arange(-1.0, 12.0))  # A_x: -1, 0 .. 10, 11
+    assert np.array_equal(np.unique(-p[..., 1] / 0.75), np.arange(-1.0, 10.0))  # A_y: -1, 0 .. 8, 9
+    return R.render(np.full(shape, value, np.uint16), spacing, s), s
+
+
+@pytest.mark.parametrize("nz", [20, 2, 1])
+def test_oracle_uniform_box_every_ray_closed_form(nz):
+    """every ray that hits the uniform box, the rim in the faces included, composites its n = floor((nz - 1) / dt) + 1
+    samples to 1 - (1 - a')^n (one sample for a one-voxel axis); the ring outside is background"""
+    v = _value_with_opacity(0.02)
+    img, s = _uniform_top(v, nz)
+    n = int(np.floor((nz - 1) / s["dt"])) + 1
+    assert n == {20: 48, 2: 3, 1: 1}[nz]
+    ap, c, bg = s["rgba"][v, 3], s["rgba"][v, :3], np.array(s["background"])
+    expect = 1 - (1 - ap) ** n
+    assert 0.01 < ap < 0.03 and expect < R.OPAQUE
+    inside = img[1:-1, 1:-1]
+    assert np.allclose(inside[..., 3], expect, rtol=0, atol=1e-12)
+    assert np.allclose(inside[..., :3], c * expect + (1 - expect) * bg, rtol=0, atol=1e-12)
+    ring = img[_ring(img)]
+    assert np.all(ring[:, 3] == 0) and np.all(ring[:, :3] == bg)
+
+
+def test_oracle_clip_plane_sample_count():
+    """the uniform box from the top, cut by the plane z = 2.9 (kept: z <= 2.9): the samples start on the plane, so a ray
+    takes floor(2.9 / dt) + 1 = 8 of them"""
+    v = _value_with_opacity(0.02)
+    img, s = _uniform_top(v, 20, clip_plane=((0.0, 0.0, -1.0), (0.0, 0.0, 2.9)))
+    ap = s["rgba"][v, 3]
+    assert ap > 0.01 and np.allclose(img[1:-1, 1:-1, 3], 1 - (1 - ap) ** 8, rtol=0, atol=1e-12)
+    assert np.all(img[_ring(img)][:, 3] == 0)
+
+
+def test_oracle_early_termination_closed_form():
+    """a uniform box with a' near 0.5: a ray stops at the first sample m with 1 - (1 - a')^m >= 1 - 2^-12, well before
+    its 48 samples, so the pixel is 1 - (1 - a')^m and not 1 - (1 - a')^48"""
+    v = _value_with_opacity(0.5)
+    img, s = _uniform_top(v, 20)
+    ap, c, bg = s["rgba"][v, 3], s["rgba"][v, :3], np.array(s["background"])
+    m = next(k for k in range(1, 49) if 1 - (1 - ap) ** k >= R.OPAQUE)
+    expect = 1 - (1 - ap) ** m
+    assert 0.3 < ap < 0.7 and m < 48 and expect - (1 - (1 - ap) ** 48) < -1e-5
+    assert np.allclose(img[1:-1, 1:-1, 3], expect, rtol=0, atol=1e-12)
+    assert np.allclose(img[1:-1, 1:-1, :3], c * expect + (1 - expect) * bg, rtol=0, atol=1e-12)
+
+
+def test_synth_volume_shell():
+    def faces(v):
+        return (v[0], v[-1], v[:, 0], v[:, -1], v[:, :, 0], v[:, :, -1])
+
+    shell3, shell0 = R.synth_volume((20, 24, 28), seed=2), R.synth_volume((20, 24, 28), seed=2, shell=0)
+    assert all(np.all(f == -1024) for f in faces(shell3))
+    assert all(np.count_nonzero(f != -1024) > f.size // 2 for f in faces(shell0))  # shell 0 keeps the faces
+    inner0, inner3 = shell0[3:-3, 3:-3, 3:-3].copy(), shell3[3:-3, 3:-3, 3:-3]
+    inner0[0, 0, 0] = -1024  # shell 3's corner marker
+    assert np.array_equal(inner0, inner3)
+
+
+@pytest.mark.parametrize("shape", [(22, 30, 36), (1, 20, 23), (16, 1, 9), (12, 33, 1)], ids=str)
+def test_cropped_ct_has_material_on_its_faces(shape):
+    ct = R.cropped_ct(shape, seed=1)
+    assert ct.min() == -1024 and ct.max() == 3071
+    for z_face in (ct[0], ct[-1]):  # the body runs through the first and last slice
+        assert np.count_nonzero(z_face > -500) > z_face.size // 3
+    if shape[1] >= 2:  # the table: the whole y = ny - 1 face, and into both x faces
+        assert np.all(ct[:, -1] >= 1000)
+        assert np.count_nonzero(ct[:, :, 0] >= 1000) >= shape[0] and np.count_nonzero(ct[:, :, -1] >= 1000) >= shape[0]
+
+
 def test_oracle_mip_closed_form():
     """an axis-aligned MIP with dt = spacing gives the maximum along the axis"""
     rng = np.random.default_rng(3)
