@@ -852,6 +852,38 @@ int ivx_volume_render(const int16_t *img, const int64_t shape[3], const int64_t 
                       void *out);
 
 /* ------------------------------------------------------------------------------------------------
+ * mask 3-D preview: ray casting of the uint8 mask, read in place
+ *   replaces invesalius/data/volume_mask.py:36-119 (VolumeMask.create_volume: vtkFixedPointVolumeRayCastMapper, or
+ *   vtkGPUVolumeRayCastMapper with the iso-surface blend mode at 127).  The contract is DESIGN.md section 7e; the tables
+ *   and the camera come from invesalius3_amd/volume_mask.py.
+ * The field: `mask` with `shape` (z, y, x) and byte `strides` of any sign.  With apron = 1 it is extended by one leading
+ *   plane on every axis that holds the byte apron_value: logical index i reads array index i - 1, logical index 0 the
+ *   constant (the dense resident mask then counts positions like the padded matrix with its flag planes).  Logical voxel
+ *   (z, y, x) sits at world (x sx, -y sy, z sz) of ivx_volren_params, as for ivx_dev_volren_render: for the padded
+ *   matrix the caller moves `origin` by (sx, -sy, sz), a translation that leaves the distances along the rays as they are.
+ * ivx_dev_maskren_cells   per IVX_VOLREN_CELL^3 macro cell of the logical field the min and max byte over the cell's voxels
+ *                         plus one voxel on every side: cells[2 c], cells[2 c + 1].  z1 < 0: every cell; else only the
+ *                         cells that the logical slices [z0, z1) reach (a slab edit).
+ * ivx_dev_maskren_render  iso = 0: the composite loop of ivx_dev_volren_render on bytes (p->mip and p->clip must be 0,
+ *                         n_table >= 257; prefix counts as there, but READ MORE TIGHTLY: a cell is skipped when entries
+ *                         [min, max] of its bytes are all transparent, not [min - 1, max + 1].  A sample s of a byte
+ *                         field stays in [min, max] (every float32 lerp of the trilinear chain is monotone in its
+ *                         rounding, so it cannot leave the range of its two integer ends), it reads entries floor(s) and
+ *                         floor(s) + 1, and floor(s) + 1 > max only at s == max, where the fraction is 0 and that entry
+ *                         weighs nothing.  So the table must be exact at integer s: a' of entry i is the opacity AT i).  iso = 1: the first crossing of 127 along the ray, shaded, with
+ *                         alpha 1; `depth` (optional, height x width float32) receives the hit's distance from the pixel's
+ *                         plane, +inf without a hit.  stats as for ivx_dev_volren_render (early = rays with a hit).
+ * ivx_mask_preview        host form: a matrix of any strides in (no apron), cells + render, the image (and depth) out.
+ * ---------------------------------------------------------------------------------------------- */
+int ivx_dev_maskren_cells(const uint8_t *mask, const int64_t shape[3], const int64_t strides[3], int apron,
+                          int apron_value, int64_t z0, int64_t z1, uint8_t *cells, void *stream);
+int ivx_dev_maskren_render(const uint8_t *mask, const uint8_t *cells, const int64_t shape[3], const int64_t strides[3],
+                           int apron, int apron_value, int iso, const float *table, const uint32_t *prefix,
+                           const ivx_volren_params *p, void *out, float *depth, uint64_t *stats, void *stream);
+int ivx_mask_preview(const uint8_t *matrix, const int64_t shape[3], const int64_t strides[3], int iso, const float *table,
+                     const uint32_t *prefix, const ivx_volren_params *p, void *out, float *depth);
+
+/* ------------------------------------------------------------------------------------------------
  * bench / test input made in HBM (no reference counterpart): a CT-like int16 phantom -- six Gaussian blobs + sinusoid +
  * hashed N(0,25) noise, clipped to [-1024, 3071] -- for the slices [z0, z0 + dz) of a z_total-slice volume; deterministic
  * in (seed, global voxel index), so slabs made by different ranks tile the whole volume.  centres_zyx_sigma: 6 x (cz, cy,

@@ -225,6 +225,7 @@ class DeviceVolume:
         self._drop_volren()
 
     def _mask_touched(self):
+        self._mp_cells_valid = False
         self._mbits_valid = False
         self._mbits_range = None
         self._mask_levels = None
@@ -275,6 +276,7 @@ class DeviceVolume:
         for b in (self.image, self.mask, self.out_mask):
             b._on_touch = None  # freeing is not "somebody looked at the contents"
         self._drop_volren(all_buffers=True)
+        self._drop_maskren()
         for b in (self.image, self.mask, self.out_mask, self.cand, self.reached, self._mbits, self.flood_scratch,
                   self._mc_scratch, self._tris, self._verts, self._faces, self._gate, getattr(self, "_range_buf", None),
                   getattr(self, "prob", None)):
@@ -315,6 +317,7 @@ class DeviceVolume:
         self._join_prefetch()  # a count still reading the plane must not see it change
         if self._fuse and not preserve and self.dx % 64 == 0:
             self._mbits_version += 1
+            self._mp_cells_valid = False
             L.check(lib.ivx_dev_threshold_i16_bits(self.image.raw, c64(self.dz), c64(self.dy), c64(self.dx), int(lo), int(hi),
                                                    self.mask.raw, self._mbits.ptr, self.stream), "threshold")
             self._mbits_valid, self._mbits_range = True, (int(lo), int(hi))
@@ -391,6 +394,8 @@ class DeviceVolume:
     def _apply_reached(self, fill, select_value, shared):
         """out_mask[reached] = fill and, when asked, mask[reached] = select_value; keeps the notes in step."""
         lib, p, st = L.lib(), ctypes.byref(self.plan), self.stream
+        if select_value is not None:
+            self._mp_cells_valid = False
         defer = self._out_logically_zero() and int(fill) != 0
         if defer:
             self._out_pending = int(fill)  # bytes stay zero; self.reached carries the result until it is needed
@@ -1003,6 +1008,79 @@ class DeviceVolume:
         self.last_render_stats = {"samples": int(st[0]), "skipped": int(st[1]), "early": int(st[2]), "rays_hit": int(st[3]),
                                   "rays": w * h}
         return out.download((h, w, 4), np.uint8 if rgba8 else np.float32)
+
+    # -- mask 3-D preview (VolumeMask.create_volume, volume_mask.py:36-119) ----------------------------------------------
+    def _drop_maskren(self):
+        for name in ("_mp_cells", "_mp_table", "_mp_out", "_mp_depth", "_mp_stats"):
+            b = getattr(self, name, None)
+            if b is not None:
+                b.close()
+            setattr(self, name, None)
+        self._mp_cells_valid = False
+        self._mp_table_key = None
+
+    def _maskren_cells(self, apron_value: int) -> DeviceBuffer:
+        """The macro cells of the resident mask with its virtual flag planes, kept until the mask's bytes change
+        (``_mp_cells_valid`` is dropped by everything that writes them) or another apron value is asked for."""
+        from . import volume as V
+
+        key = int(apron_value)
+        if getattr(self, "_mp_cells_valid", False) and self._mp_cells_key == key:
+            return self._mp_cells
+        ncell = int(np.prod([-(-(s + 1) // V.CELL) for s in self.shape]))
+        cells = self._grow(self, "_mp_cells", ncell * 2)
+        L.check(L.lib().ivx_dev_maskren_cells(self.mask.raw, L.i64(self.shape), L.i64([self.dy * self.dx, self.dx, 1]), 1,
+                                              key, c64(0), c64(-1), cells.ptr, self.stream), "maskren_cells")
+        self._mp_cells_valid, self._mp_cells_key = True, key
+        return cells
+
+    def render_mask_preview(self, colour, camera, size, mode: str = "composite", apron_value: int = 1,
+                            download: bool = True, rgba8: bool = False, depth: bool = False, background=(0.0, 0.0, 0.0),
+                            sample_distance=None):
+        """The 3-D preview of the resident mask (volume_mask.render_setup: `mode` "composite" or "iso", `colour` r, g, b in
+        0..1), read in place.  The mask is dense, so the index-0 flag planes of the reference's matrix are a virtual apron
+        of `apron_value` (1 is what a whole-volume threshold leaves there).  `camera`: a standard view name or a dict from
+        volume.camera_for_view; `size` (width, height).  Returns (height, width, 4) float32 RGBA (uint8 with `rgba8`),
+        with `depth` (iso mode) also the (height, width) float32 distance of the hit, or the device buffer(s) when not
+        `download`.  The sample counts are left in ``last_render_stats`` by a downloading render; without `download`
+        nothing is waited for, so they stay those of the last render that did."""
+        from . import volume as V
+        from . import volume_mask as VM
+
+        if depth and mode != "iso":
+            raise ValueError("depth is an output of the iso mode")
+        w, h = int(size[0]), int(size[1])
+        if isinstance(camera, str):
+            cam = V.camera_for_view(camera, self.shape, self.spacing, (w, h))
+        else:
+            cam = dict(camera, viewport=(w, h))
+        setup = VM.render_setup(colour, mode, cam, self.spacing, background, sample_distance)
+        rgba, prefix = VM.device_tables(setup)
+        cells = self._maskren_cells(apron_value)
+        tb = self._grow(self, "_mp_table", rgba.nbytes + prefix.nbytes)
+        key = (tuple(float(c) for c in colour), mode, setup["dt"])
+        if getattr(self, "_mp_table_key", None) != key:  # a slider step or a camera move keeps the table: no stall
+            self.sync()  # the table buffer may still be read by the previous render
+            tb.upload(np.concatenate([rgba.view(np.uint8).ravel(), prefix.view(np.uint8).ravel()]))
+            self._mp_table_key = key
+        p = V.volren_params(setup, self.spacing, rgba8)
+        out = self._grow(self, "_mp_out", w * h * 4 * (1 if rgba8 else 4))
+        dep = self._grow(self, "_mp_depth", w * h * 4) if depth else None
+        stats = self._grow(self, "_mp_stats", 32)
+        stats.zero(self.stream, 32)
+        L.check(L.lib().ivx_dev_maskren_render(self.mask.raw, cells.ptr, L.i64(self.shape),
+                                               L.i64([self.dy * self.dx, self.dx, 1]), 1, int(apron_value), int(setup["iso"]),
+                                               tb.ptr, tb.at(rgba.nbytes), ctypes.byref(p), out.ptr,
+                                               None if dep is None else dep.ptr, stats.ptr, self.stream),
+                "render_mask_preview")
+        if not download:
+            return (out, dep) if depth else out
+        self.sync()
+        st = stats.download((4,), np.uint64)
+        self.last_render_stats = {"samples": int(st[0]), "skipped": int(st[1]), "early": int(st[2]), "rays_hit": int(st[3]),
+                                  "rays": w * h}
+        img = out.download((h, w, 4), np.uint8 if rgba8 else np.float32)
+        return (img, dep.download((h, w), np.float32)) if depth else img
 
     def volume_histogram(self) -> np.ndarray:
         """CalculateHistogram (volume.py:723-735) of the resident image: uint64 counts of the int(max - min) unit bins

@@ -5,6 +5,7 @@
     python -m invesalius3_amd.headless CASE.inv3 --filter median 3 --threshold 226 3071 --stl bone.stl
     python -m invesalius3_amd.headless CASE.inv3 --segment brain --weights brain_mri_t1.pt --stl brain.stl
     python -m invesalius3_amd.headless CASE.inv3 --render "Bone + Skin" --presets-dir DIR --view iso --png out.png
+    python -m invesalius3_amd.headless CASE.inv3 --threshold 226 3071 --mask-preview iso --mask-colour 0 1 0 --png mask.png
 
 What the reference does through its GUI for the same result: Slice.SetMaskThreshold / do_threshold_to_all_slices
 (invesalius/data/slice_.py:1240-1247, 1739-1769), the Image Filters dialog (slice_.py:2330-2539), the deep-learning segmentation (segmentation/deep_learning/segment.py), the 3-D view's volume rendering (data/volume.py:575-707), the region-growing tool (styles.py:3151-3216),
@@ -112,6 +113,17 @@ def run(args) -> dict:
             vol.mask.zero(vol.stream)  # keep only the grown region
             L.check(lib.ivx_dev_flood_apply_where(vol.mask.ptr, vol.out_mask.ptr, c64(vol.n), 1, 255, vol.stream))
             out["region_grow"] = {"seeds": [list(s) for s in seeds], "rounds": rounds, "voxels": vol.reached_count()}
+        if args.mask_preview is not None:
+            # "Mask 3D preview" (Mask.create_3d_preview -> VolumeMask.create_volume, volume_mask.py:36-119) of the resident mask
+            from . import volume as V
+            w, h = args.size
+            with vol.timer.span("mask_preview"):
+                rgba8 = vol.render_mask_preview(args.mask_colour, args.view, (w, h), mode=args.mask_preview, rgba8=True)
+            out["mask_preview"] = {"mode": args.mask_preview, "colour": list(args.mask_colour), "view": args.view,
+                                   "size": [w, h], **vol.last_render_stats}
+            if args.png:
+                V.write_png(args.png, rgba8)
+                out["mask_preview"]["png"] = args.png
         mask = vol.download_mask()
         out["mask_voxels"] = int(np.count_nonzero(mask >= 127))
         with vol.timer.span("surface"):
@@ -215,6 +227,11 @@ def main(argv=None) -> int:
     ap.add_argument("--render", metavar="PRESET", default=None,
                     help="volume-render the image (after --filter) with a raycasting preset: a .plist file, or a preset "
                          "name looked up in --presets-dir")
+    ap.add_argument("--mask-preview", choices=("composite", "iso"), default=None,
+                    help="ray-cast the mask (after --threshold / --seed / --segment, or the project's --mask) as a shaded solid: "
+                         "the reference's Mask 3D preview with rendering 0 (composite) or 1 (iso-surface at 127)")
+    ap.add_argument("--mask-colour", nargs=3, type=float, metavar=("R", "G", "B"), default=(0.0, 1.0, 0.0),
+                    help="the mask's colour, 0..1 each (default 0 1 0)")
     ap.add_argument("--presets-dir", metavar="DIR", default=None, help="the raycasting presets directory (with color_list/)")
     ap.add_argument("--view", choices=("front", "back", "left", "right", "top", "bottom", "iso"), default="iso")
     ap.add_argument("--size", nargs=2, type=int, metavar=("W", "H"), default=(512, 512), help="image size (default 512 512)")
@@ -254,8 +271,15 @@ def main(argv=None) -> int:
             ap.error("--render NAME needs --presets-dir DIR (or give the .plist file)")
         if args.size[0] <= 0 or args.size[1] <= 0:
             ap.error("--size W H must be positive")
+        if args.mask_preview is not None:
+            ap.error("--render and --mask-preview make one picture each: name one of them")
+    elif args.mask_preview is not None:
+        if args.size[0] <= 0 or args.size[1] <= 0:
+            ap.error("--size W H must be positive")
+        if not all(0.0 <= c <= 1.0 for c in args.mask_colour):
+            ap.error("--mask-colour R G B must lie in 0..1")
     elif args.png is not None:
-        ap.error("--png needs --render")
+        ap.error("--png needs --render or --mask-preview")
     print(json.dumps(run(args)))
     return 0
 
