@@ -330,6 +330,54 @@ int ivx_mesh_fill_holes(const float *verts, int64_t nverts, const int32_t *faces
 int ivx_mesh_point_normals(const float *verts, int64_t nverts, const int32_t *faces, int64_t ntris, double cos_feature_angle,
                            int splitting, int auto_orient, float *out_verts, int32_t *out_faces, float *point_normals,
                            float *cell_normals /* may be NULL */, int64_t *out_nverts);
+/* Surface visibility: "Remove non-visible faces" (pu.RemoveNonVisibleFaces / pu.HasNonVisibleFaces,
+ * invesalius/data/polydata_utils.py:281-455: off-screen renders of the mesh + vtkSelectVisiblePoints) as a depth-only
+ * software rasteriser.  A view is plain numbers, built on the host from the mesh's bounds
+ * (polydata_utils.views_for_positions); the kernels use + - * / in float64 only:
+ *   d = v - eye;  xe = (d.x r.x + d.y r.y) + d.z r.z  (ye with `up`, ze with `fwd`);
+ *   xs = (xe / (ze tan_half aspect) + 1) 0.5 width;  ys = (ye / (ze tan_half) + 1) 0.5 height;
+ *   zw = (zfar (ze - znear)) / (ze (zfar - znear)).   A vertex with ze <= 0 is behind the eye: its triangles draw nothing
+ *   and the point is not visible (never the case for a view made from the bounds).
+ *   ivx_*_mesh_bounds          {xmin, xmax, ymin, ymax, zmin, zmax} over ALL points (zeros for an empty mesh).
+ *   ivx_*_mesh_depth_raster    float32 depth[height][width] of one view, cleared to 1.0; pixel centre (i + .5, j + .5) on or
+ *                              inside a triangle (either winding, edge functions evaluated from the smaller vertex id) gets
+ *                              the float32-rounded screen-barycentric zw, minimum kept.  `stages`: IVX_RASTER_* bits (the
+ *                              three stages can be run, and timed, in separate calls on one stream, in this order).
+ *   ivx_*_mesh_visible_points  flags[v] = 1 when any view sees point v: inside the viewport and
+ *                              zw < depth[(int)ys][(int)xs] + 0.01 (vtkSelectVisiblePoints' default tolerance).
+ *   ivx_*_mesh_select_points   keeps the triangles with ANY corner flagged (`invert`: any corner NOT flagged), in order, and
+ *                              compacts the points they use, in order.  out_verts / out_faces == NULL -> sizes only.
+ *   ivx_mesh_remove_nonvisible the whole tool on host arrays: flags over `views`, then the selection (remove_visible -> invert).
+ * PARITY UNPINNED vs VTK's OpenGL rasteriser (third party, not installable here). */
+typedef struct ivx_mesh_view {
+    double eye[3], right[3], up[3], fwd[3]; /* orthonormal camera frame; fwd looks from the eye at the focal point */
+    double znear, zfar;                     /* clipping range along fwd */
+    double tan_half, aspect;                /* tan(view angle / 2), width / height */
+    int32_t width, height;
+} ivx_mesh_view;
+#define IVX_RASTER_CLEAR 1 /* depth <- 1.0, queue of big triangles <- empty */
+#define IVX_RASTER_SMALL 2 /* lane per triangle; boxes of more than IVX_RASTER_SMALL_BOX pixels are queued */
+#define IVX_RASTER_BIG 4   /* workgroup per queued triangle */
+#define IVX_RASTER_ALL 7
+#define IVX_RASTER_SMALL_BOX 64
+int ivx_dev_mesh_bounds(const float *verts, int64_t nverts, float *bounds6, void *stream);
+int ivx_dev_mesh_depth_raster(const float *verts, int64_t nverts, const int32_t *faces, int64_t ntris,
+                              const ivx_mesh_view *view /* host */, int stages, float *depth, void *stream);
+int ivx_dev_mesh_visible_points(const float *verts, int64_t nverts, const int32_t *faces, int64_t ntris,
+                                const ivx_mesh_view *views /* host */, int nviews, uint8_t *flags, void *stream);
+int ivx_dev_mesh_select_points(const float *verts, int64_t nverts, const int32_t *faces, int64_t ntris, const uint8_t *flags,
+                               int invert, float *out_verts, int64_t max_verts, int32_t *out_faces, int64_t max_tris,
+                               int64_t *out_nverts, int64_t *out_ntris, void *stream);
+int ivx_mesh_bounds(const float *verts, int64_t nverts, float *bounds6);
+int ivx_mesh_depth_raster(const float *verts, int64_t nverts, const int32_t *faces, int64_t ntris, const ivx_mesh_view *view,
+                          float *depth);
+int ivx_mesh_visible_points(const float *verts, int64_t nverts, const int32_t *faces, int64_t ntris,
+                            const ivx_mesh_view *views, int nviews, uint8_t *flags);
+int ivx_mesh_select_points(const float *verts, int64_t nverts, const int32_t *faces, int64_t ntris, const uint8_t *flags,
+                           int invert, float *out_verts, int32_t *out_faces, int64_t *out_nverts, int64_t *out_ntris);
+int ivx_mesh_remove_nonvisible(const float *verts, int64_t nverts, const int32_t *faces, int64_t ntris,
+                               const ivx_mesh_view *views, int nviews, int remove_visible, float *out_verts,
+                               int32_t *out_faces, int64_t *out_nverts, int64_t *out_ntris);
 
 /* ------------------------------------------------------------------------------------------------
  * context-aware smoothing of the indexed surface

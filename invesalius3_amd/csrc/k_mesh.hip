@@ -16,6 +16,7 @@
 #include <algorithm>
 
 #include "ivx_internal.h"
+#include "mesh_compact.h"
 #include "scan_u32.h"
 
 namespace {
@@ -190,29 +191,6 @@ __global__ __launch_bounds__(256) void k_mesh_mark(const int32_t *__restrict__ f
         usedv[b] = 1u;
         usedv[c] = 1u;
     }
-}
-
-__global__ __launch_bounds__(256) void k_mesh_compact_faces(const int32_t *__restrict__ faces, int64_t nt,
-                                                            const uint32_t *__restrict__ koff,
-                                                            const uint32_t *__restrict__ voff, int32_t *__restrict__ out,
-                                                            int64_t max_out) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= nt) return;
-    const uint32_t o = koff[t];
-    if (koff[t + 1] == o || (int64_t)o >= max_out) return;
-#pragma unroll
-    for (int q = 0; q < 3; q++) out[3 * (int64_t)o + q] = (int32_t)voff[(uint32_t)faces[3 * t + q]];
-}
-
-__global__ __launch_bounds__(256) void k_mesh_compact_verts(const float *__restrict__ verts, int64_t nv,
-                                                            const uint32_t *__restrict__ voff, float *__restrict__ out,
-                                                            int64_t max_out) {
-    const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= nv) return;
-    const uint32_t o = voff[v];
-    if (voff[v + 1] == o || (int64_t)o >= max_out) return;
-#pragma unroll
-    for (int q = 0; q < 3; q++) out[3 * (int64_t)o + q] = verts[3 * v + q];
 }
 
 // ---- mass properties ------------------------------------------------------------------------------------------------

@@ -2,6 +2,7 @@
 
     python -m invesalius3_amd.headless CASE.inv3 --threshold 226 3071 --seed 250 260 100 --largest --smooth \\
         --stl bone.stl --save CASE_out.inv3
+    python -m invesalius3_amd.headless CASE.inv3 --threshold 226 3071 --largest --remove-nonvisible --stl shell.stl
     python -m invesalius3_amd.headless CASE.inv3 --filter median 3 --threshold 226 3071 --stl bone.stl
     python -m invesalius3_amd.headless CASE.inv3 --segment brain --weights brain_mri_t1.pt --stl brain.stl
     python -m invesalius3_amd.headless CASE.inv3 --render "Bone + Skin" --presets-dir DIR --view iso --png out.png
@@ -10,7 +11,7 @@
 What the reference does through its GUI for the same result: Slice.SetMaskThreshold / do_threshold_to_all_slices
 (invesalius/data/slice_.py:1240-1247, 1739-1769), the Image Filters dialog (slice_.py:2330-2539), the deep-learning segmentation (segmentation/deep_learning/segment.py), the 3-D view's volume rendering (data/volume.py:575-707), the region-growing tool (styles.py:3151-3216),
 SurfaceManager.AddNewActor -> create_surface_piece / join_process_surface (surface.py:1362-1380,
-surface_process.py:71-472) and vtkSTLWriter (surface.py:1827-1829).  No wx, no VTK here; one JSON line on stdout."""
+surface_process.py:71-472), Remove non-visible faces (polydata_utils.py:363-455) and vtkSTLWriter (surface.py:1827-1829).  No wx, no VTK here; one JSON line on stdout."""
 from __future__ import annotations
 
 import argparse
@@ -141,6 +142,14 @@ def run(args) -> dict:
                                                       ctypes.byref(nr), vol.stream), "keep_largest")
             verts_buf, faces_buf, nv, nt = keep_v, keep_f, n1.value, n2.value
             out["largest"] = {"regions": nr.value, "vertices": nv, "triangles": nt}
+        shell = None
+        if args.remove_nonvisible and nt:
+            # Surface.OnRemoveNonVisibleFaces -> pu.RemoveNonVisibleFaces (surface.py:413-435) on the resident mesh
+            from . import polydata_utils as pu
+            with vol.timer.span("remove_nonvisible"):
+                shell = pu.RemoveNonVisibleFaces(pu.DeviceMesh(verts_buf, nv, faces_buf, nt, vol.stream))
+            out["remove_nonvisible"] = {"vertices": shell.nverts, "triangles": shell.ntris, "removed_triangles": nt - shell.ntris}
+            verts_buf, faces_buf, nv, nt = shell.verts, shell.faces, shell.nverts, shell.ntris
         if args.smooth and nt:
             from .device import DeviceBuffer
             nrm = DeviceBuffer(nt * 24 + 16)
@@ -186,6 +195,8 @@ def run(args) -> dict:
         for b in (keep_v, keep_f):
             if b is not None:
                 b.close()
+        if shell is not None:
+            shell.close()
     finally:
         vol.close()
         proj.close()
@@ -196,7 +207,7 @@ def run(args) -> dict:
 def _render_only(args) -> bool:
     """--render without anything that asks for a mask or a surface: the image is all there is to make"""
     return (args.threshold is None and args.segment is None and not args.seed and not args.stl and not args.save
-            and not args.largest and not args.smooth and "--mask" not in (args.argv or []))
+            and not args.largest and not args.smooth and not args.remove_nonvisible and "--mask" not in (args.argv or []))
 
 
 def _strct(conn: int) -> np.ndarray:
@@ -238,6 +249,9 @@ def main(argv=None) -> int:
     ap.add_argument("--png", metavar="OUT", default=None, help="write the rendered image as an RGBA PNG")
     ap.add_argument("--connectivity", type=int, choices=(6, 18, 26), default=26)
     ap.add_argument("--largest", action="store_true", help="keep the largest connected surface")
+    ap.add_argument("--remove-nonvisible", action="store_true",
+                    help="remove the faces that cannot be seen from outside (the six axis views at 800 x 800 of the reference's "
+                         "Remove non-visible faces), after --largest and before --smooth / --stl")
     ap.add_argument("--smooth", action="store_true", help="context-aware smoothing")
     ap.add_argument("--angle", type=float, default=0.7)
     ap.add_argument("--max-distance", type=float, default=3.0)

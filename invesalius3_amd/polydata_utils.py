@@ -1,0 +1,258 @@
+"""``invesalius.data.polydata_utils`` -- the surface visibility tools on the GPU (csrc/k_meshvis.hip).
+
+``RemoveNonVisibleFaces`` (polydata_utils.py:363-455) and ``HasNonVisibleFaces`` (:281-360) render the surface off screen
+from six sides and ask vtkSelectVisiblePoints which points the z-buffer lets through.  Here the renders are a depth-only
+software rasteriser in HIP, and arrays stand in for ``vtkPolyData``: ``verts`` float32 (N, 3), ``faces`` int32 (T, 3).
+The cameras are built here, on the host, in float64 and handed to the kernels as plain numbers.  `DeviceMesh` is the
+same mesh resident in HBM (what ``DeviceVolume.marching_cubes_indexed(download=False)`` leaves behind): with it
+threshold -> mesh -> keep largest -> remove non-visible never leaves the device.
+
+PARITY UNPINNED: VTK and its OpenGL rasteriser are not installed; the rules of DESIGN 7f are pinned bit for bit against
+their numpy restatement (tests/_meshvis_ref.py).  vtkCleanPolyData's merge of coincident points is not done."""
+from __future__ import annotations
+
+import ctypes
+import math
+
+import numpy as np
+
+from . import _lib as L
+
+POSITIONS = ((1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1))  # the reference's six, in its order
+SIZE = (800, 800)                                                                  # render_window.SetSize(800, 800)
+VIEW_ANGLE = 30.0                                                                  # vtkCamera's default
+
+
+class MeshView(ctypes.Structure):
+    """struct ivx_mesh_view (include/ivx.h)."""
+    _fields_ = [("eye", ctypes.c_double * 3), ("right", ctypes.c_double * 3), ("up", ctypes.c_double * 3),
+                ("fwd", ctypes.c_double * 3), ("znear", ctypes.c_double), ("zfar", ctypes.c_double),
+                ("tan_half", ctypes.c_double), ("aspect", ctypes.c_double), ("width", ctypes.c_int32),
+                ("height", ctypes.c_int32)]
+
+
+def _cross(a, b):
+    return [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
+
+
+def _unit(a):
+    ln = math.sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2])
+    return [a[0] / ln, a[1] / ln, a[2] / ln]
+
+
+def views_for_positions(bounds, positions=POSITIONS, size=SIZE) -> list:
+    """The cameras of the tool for a mesh with these bounds ``(xmin, xmax, ymin, ymax, zmin, zmax)``: per position the eye at
+    ``centre + unit(position) * dist``, looking at the centre, with ``dist = radius / sin(15 deg)`` (ResetCamera, as
+    `volume.camera_for_view`), a perspective of 30 degrees, the view up carried along the list the way vtkCamera carries it
+    (turned when it gets parallel to the view direction) and ResetCameraClippingRange's near / far from the bounds' corners.
+    Each view is a dict of floats: eye, right, up, fwd, near, far, tan_half, aspect, size (+ view_up, dist, centre)."""
+    w_px, h_px = int(size[0]), int(size[1])
+    if w_px <= 0 or h_px <= 0:
+        raise ValueError("size %r must be positive" % (size,))
+    b = [float(x) for x in bounds]
+    c = [(b[0] + b[1]) / 2, (b[2] + b[3]) / 2, (b[4] + b[5]) / 2]
+    w = [b[1] - b[0], b[3] - b[2], b[5] - b[4]]
+    radius = math.sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]) * 0.5
+    if radius == 0.0:
+        radius = 1.0
+    half = math.radians(VIEW_ANGLE) * 0.5
+    dist = radius / math.sin(half)
+    up = [0.0, 1.0, 0.0]
+    out = []
+    for p in positions:
+        n = _unit([float(x) for x in p])
+        eye = [c[0] + n[0] * dist, c[1] + n[1] * dist, c[2] + n[2] * dist]
+        if abs(up[0] * n[0] + up[1] * n[1] + up[2] * n[2]) > 0.999:
+            up = [-up[2], up[0], up[1]]  # (and it stays turned for the views that follow)
+        fwd = [-n[0], -n[1], -n[2]]
+        right = _unit(_cross(fwd, up))
+        upv = _cross(right, fwd)
+        n0, f0 = math.inf, -math.inf
+        for x in (b[0], b[1]):
+            for y in (b[2], b[3]):
+                for z in (b[4], b[5]):
+                    d = ((x - eye[0]) * fwd[0] + (y - eye[1]) * fwd[1]) + (z - eye[2]) * fwd[2]
+                    n0, f0 = min(n0, d), max(f0, d)
+        near = 0.99 * n0 - 0.5 * (f0 - n0)
+        far = 1.01 * f0 + 0.5 * (f0 - near)
+        if near >= far:
+            near = 0.01 * far
+        near = max(near, 0.001 * far)
+        out.append({"eye": eye, "right": right, "up": upv, "fwd": fwd, "near": near, "far": far, "tan_half": math.tan(half),
+                    "aspect": w_px / h_px, "size": (w_px, h_px), "view_up": list(up), "dist": dist, "centre": c})
+    return out
+
+
+def _c_views(views):
+    arr = (MeshView * max(len(views), 1))()
+    for q, v in enumerate(views):
+        m = arr[q]
+        m.eye[:], m.right[:], m.up[:], m.fwd[:] = v["eye"], v["right"], v["up"], v["fwd"]
+        m.znear, m.zfar, m.tan_half, m.aspect = v["near"], v["far"], v["tan_half"], v["aspect"]
+        m.width, m.height = v["size"]
+    return arr
+
+
+def _mesh(verts, faces):
+    v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+    return v, f
+
+
+class DeviceMesh:
+    """An indexed mesh resident on the GPU: two `DeviceBuffer`s, the counts and the stream its kernels run on."""
+
+    def __init__(self, verts_buf, nverts: int, faces_buf, ntris: int, stream=None, owns: bool = False):
+        self.verts, self.nverts, self.faces, self.ntris, self.stream, self._owns = verts_buf, int(nverts), faces_buf, int(ntris), stream, owns
+
+    @classmethod
+    def from_volume(cls, vol, counts=None):
+        """The mesh ``vol.marching_cubes_indexed(download=False)`` made; `counts` is what that call returned."""
+        nv, nt = counts if counts is not None else vol.marching_cubes_indexed()
+        return cls(vol._verts, nv, vol._faces, nt, vol.stream)
+
+    @classmethod
+    def upload(cls, verts, faces, stream=None):
+        from .device import DeviceBuffer
+        v, f = _mesh(verts, faces)
+        if len(f) and (f.min() < 0 or f.max() >= len(v)):
+            raise ValueError("mesh: face index outside [0, %d)" % len(v))
+        m = cls(DeviceBuffer(v.nbytes + 16), len(v), DeviceBuffer(f.nbytes + 16), len(f), stream, owns=True)
+        if len(v):
+            m.verts.upload(v)
+        if len(f):
+            m.faces.upload(f)
+        return m
+
+    def sync(self):
+        L.check(L.lib().ivx_stream_synchronize(self.stream) if self.stream else L.lib().ivx_device_synchronize())
+
+    def download(self):
+        self.sync()
+        return self.verts.download((self.nverts, 3), np.float32), self.faces.download((self.ntris, 3), np.int32)
+
+    def bounds(self):
+        from .device import DeviceBuffer
+        out = DeviceBuffer(64)
+        try:
+            L.check(L.lib().ivx_dev_mesh_bounds(self.verts.ptr, ctypes.c_int64(self.nverts), out.ptr, self.stream), "mesh_bounds")
+            self.sync()  # (the stream does not block the copy below)
+            return tuple(float(x) for x in out.download((6,), np.float32))
+        finally:
+            out.close()
+
+    def visible_flags(self, views):
+        """device buffer of one uint8 per point (the caller closes it)"""
+        from .device import DeviceBuffer
+        flags = DeviceBuffer(self.nverts + 16)
+        L.check(L.lib().ivx_dev_mesh_visible_points(self.verts.ptr, ctypes.c_int64(self.nverts), self.faces.ptr, ctypes.c_int64(self.ntris),
+                                                    _c_views(views), len(views), flags.ptr, self.stream), "mesh_visible_points")
+        return flags
+
+    def select(self, flags, invert: bool = False) -> "DeviceMesh":
+        from .device import DeviceBuffer
+        ov, of = DeviceBuffer(self.nverts * 12 + 16), DeviceBuffer(self.ntris * 12 + 16)
+        nv, nt = ctypes.c_int64(0), ctypes.c_int64(0)
+        L.check(L.lib().ivx_dev_mesh_select_points(self.verts.ptr, ctypes.c_int64(self.nverts), self.faces.ptr, ctypes.c_int64(self.ntris),
+                                                   flags.ptr, int(bool(invert)), ov.ptr, ctypes.c_int64(self.nverts), of.ptr,
+                                                   ctypes.c_int64(self.ntris), ctypes.byref(nv), ctypes.byref(nt), self.stream),
+                "mesh_select_points")
+        return DeviceMesh(ov, nv.value, of, nt.value, self.stream, owns=True)
+
+    def close(self):
+        if self._owns:
+            self.verts.close()
+            self.faces.close()
+        self._owns = False
+
+
+def bounds(verts) -> tuple:
+    """``(xmin, xmax, ymin, ymax, zmin, zmax)`` over ALL points, used by a triangle or not (vtkPolyData.GetBounds); zeros for
+    an empty mesh."""
+    if isinstance(verts, DeviceMesh):
+        return verts.bounds()
+    v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    out = np.zeros(6, np.float32)
+    L.check(L.lib().ivx_mesh_bounds(L.ptr(v), ctypes.c_int64(len(v)), L.ptr(out)), "mesh_bounds")
+    return tuple(float(x) for x in out)
+
+
+def depth_buffer(verts, faces, view, size=None) -> np.ndarray:
+    """The float32 z-buffer ``(H, W)`` of one view (a dict as `views_for_positions` makes them; `size`, when given, must be the
+    view's): 1.0 where nothing is drawn, row 0 at the bottom of the viewport."""
+    v, f = _mesh(verts, faces)
+    w_px, h_px = view["size"]
+    if size is not None and (int(size[0]), int(size[1])) != (w_px, h_px):
+        raise ValueError("size %r is not the view's %r" % (tuple(size), (w_px, h_px)))
+    out = np.empty((h_px, w_px), np.float32)
+    L.check(L.lib().ivx_mesh_depth_raster(L.ptr(v), ctypes.c_int64(len(v)), L.ptr(f), ctypes.c_int64(len(f)), _c_views([view]),
+                                          L.ptr(out)), "mesh_depth_raster")
+    return out
+
+
+def visible_points(verts, faces=None, positions=POSITIONS, size=SIZE, views=None) -> np.ndarray:
+    """uint8 flag per point: 1 when any of the views sees it (inside the viewport and no deeper than the z-buffer + 0.01, the
+    default tolerance of vtkSelectVisiblePoints).  `views` overrides the cameras made from the bounds and `positions`."""
+    if isinstance(verts, DeviceMesh):
+        m = verts
+        if views is None:
+            views = views_for_positions(m.bounds(), positions, size)
+        flags = m.visible_flags(views)
+        try:
+            m.sync()
+            return flags.download((m.nverts,), np.uint8)
+        finally:
+            flags.close()
+    v, f = _mesh(verts, faces)
+    if views is None:
+        views = views_for_positions(bounds(v), positions, size)
+    out = np.zeros(len(v), np.uint8)
+    L.check(L.lib().ivx_mesh_visible_points(L.ptr(v), ctypes.c_int64(len(v)), L.ptr(f), ctypes.c_int64(len(f)), _c_views(views),
+                                            len(views), L.ptr(out)), "mesh_visible_points")
+    return out
+
+
+def select_by_point_flags(verts, faces, flags, invert=False):
+    """The triangles with ANY corner flagged (`invert`: any corner not flagged), in order, on the points they use, compacted in
+    order (the ``GetPointCells`` union + vtkExtractSelection of polydata_utils.py:420-449)."""
+    v, f = _mesh(verts, faces)
+    fl = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+    if len(fl) != len(v):
+        raise ValueError("one flag per point")
+    ov, of = np.empty_like(v), np.empty_like(f)
+    nv, nt = ctypes.c_int64(0), ctypes.c_int64(0)
+    L.check(L.lib().ivx_mesh_select_points(L.ptr(v), ctypes.c_int64(len(v)), L.ptr(f), ctypes.c_int64(len(f)), L.ptr(fl),
+                                           int(bool(invert)), L.ptr(ov), L.ptr(of), ctypes.byref(nv), ctypes.byref(nt)),
+            "mesh_select_points")
+    return ov[: nv.value].copy(), of[: nt.value].copy()
+
+
+def RemoveNonVisibleFaces(verts, faces=None, positions=POSITIONS, remove_visible=False, size=SIZE):
+    """``pu.RemoveNonVisibleFaces`` (:363-455): keeps the triangles that touch a visible point -- or, with `remove_visible`,
+    those that touch a hidden one (the reference's naming: a triangle with corners of both kinds is in both results).
+    Arrays in -> ``(verts', faces')``; a `DeviceMesh` in (``faces=None``) -> a `DeviceMesh` out, nothing downloaded."""
+    if isinstance(verts, DeviceMesh):
+        m = verts
+        views = views_for_positions(m.bounds(), positions, size)
+        flags = m.visible_flags(views)
+        try:
+            return m.select(flags, remove_visible)
+        finally:
+            flags.close()
+    v, f = _mesh(verts, faces)
+    views = views_for_positions(bounds(v), positions, size)
+    ov, of = np.empty_like(v), np.empty_like(f)
+    nv, nt = ctypes.c_int64(0), ctypes.c_int64(0)
+    L.check(L.lib().ivx_mesh_remove_nonvisible(L.ptr(v), ctypes.c_int64(len(v)), L.ptr(f), ctypes.c_int64(len(f)), _c_views(views),
+                                               len(views), int(bool(remove_visible)), L.ptr(ov), L.ptr(of), ctypes.byref(nv),
+                                               ctypes.byref(nt)), "mesh_remove_nonvisible")
+    return ov[: nv.value].copy(), of[: nt.value].copy()
+
+
+def HasNonVisibleFaces(verts, faces=None, threshold=0.7, positions=POSITIONS, size=SIZE) -> bool:
+    """``pu.HasNonVisibleFaces`` (:281-360): True when fewer than `threshold` of the points are visible; False for an empty
+    mesh."""
+    n = verts.nverts if isinstance(verts, DeviceMesh) else len(np.asarray(verts).reshape(-1, 3))
+    if n == 0:
+        return False
+    return int(np.count_nonzero(visible_points(verts, faces, positions, size))) / n < threshold
