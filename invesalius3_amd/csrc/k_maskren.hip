@@ -6,10 +6,11 @@
 //         positions count as for the padded matrix while DeviceVolume keeps the mask dense.
 // cells:  min / max bytes per 8^3 macro cell, one voxel of apron on every side; a z range rebuilds only the cells that a
 //         slab edit touched.
-// render: one lane per ray, 8x8 pixel tiles per wave, the rays and samples of k_volren.hip (volren_ray.h).
-//         composite: k_volren.hip's loop on bytes (the same arithmetic, so the same bits on the same values).  A cell is
-//                    skipped when the table entries [min, max] are all transparent: a byte field sampled at an integer s
-//                    has fraction 0, so entry floor(s) + 1 weighs nothing at s == max.
+// render: one lane per ray, 8x8 pixel tiles per wave; the rays, samples, headlight, pixel write and counters are
+//         volren_ray.h's, read through its Field, as is the cells kernel.
+//         composite: volren_ray.h's composite_ray, the one loop k_volren.hip runs too (so the same bits on the same
+//                    values).  A cell is skipped when the table entries [min, max] are all transparent: a byte field
+//                    sampled at an integer s has fraction 0, so entry floor(s) + 1 weighs nothing at s == max.
 //         iso:       the first sample k >= 1 with (f[k-1] - 127)(f[k] - 127) < 0 or f[k] == 127; one linear step to the
 //                    hit, the gradient and the headlight there, alpha 1, and the hit's distance as depth.  A cell whose
 //                    bytes lie all below or all above 127 holds no crossing; it is jumped when the predecessor lies on the
@@ -23,83 +24,6 @@ using namespace ivx;
 namespace {
 
 constexpr float ISO = 127.0f; // SetValue(0, 127), volume_mask.py:103
-
-struct Field {
-    const uint8_t *base;
-    int64_t sz, sy, sx; // byte strides of the array
-    int apron;          // 1: logical index 0 of every axis is a virtual plane of `av`, array index = logical index - 1
-    unsigned av;
-};
-
-__device__ __forceinline__ float fetch(const Field &f, int z, int y, int x) {
-    if (f.apron) {
-        if (z == 0 || y == 0 || x == 0) return (float)f.av;
-        z--, y--, x--;
-    }
-    return (float)f.base[z * f.sz + y * f.sy + x * f.sx];
-}
-
-// trilinear interpolation at the logical index position (x, y, z), already clamped to the field; k_volren.hip's order
-__device__ __forceinline__ float tri(const Field &v, const Dims &d, float x, float y, float z) {
-    int x0 = (int)x, y0 = (int)y, z0 = (int)z;
-    x0 = min(x0, max(d.nx - 2, 0));
-    y0 = min(y0, max(d.ny - 2, 0));
-    z0 = min(z0, max(d.nz - 2, 0));
-    const float fx = x - (float)x0, fy = y - (float)y0, fz = z - (float)z0;
-    const int x1 = min(x0 + 1, d.nx - 1), y1 = min(y0 + 1, d.ny - 1), z1 = min(z0 + 1, d.nz - 1);
-    const float c00 = lerpf(fetch(v, z0, y0, x0), fetch(v, z0, y0, x1), fx);
-    const float c01 = lerpf(fetch(v, z0, y1, x0), fetch(v, z0, y1, x1), fx);
-    const float c10 = lerpf(fetch(v, z1, y0, x0), fetch(v, z1, y0, x1), fx);
-    const float c11 = lerpf(fetch(v, z1, y1, x0), fetch(v, z1, y1, x1), fx);
-    return lerpf(lerpf(c00, c01, fy), lerpf(c10, c11, fy), fz);
-}
-
-// cells cz0 .. of the logical field d: one thread per cell
-__global__ __launch_bounds__(256) void k_mr_cells(Field v, Dims d, Dims c, int cz0, int64_t ncell,
-                                                 uint8_t *__restrict__ cells) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= ncell) return;
-    const int64_t ci = i + (int64_t)cz0 * c.ny * c.nx;
-    const int cx = (int)(ci % c.nx), cy = (int)((ci / c.nx) % c.ny), cz = (int)(ci / ((int64_t)c.nx * c.ny));
-    const int x0 = max(cx * CELL - 1, 0), x1 = min(cx * CELL + CELL, d.nx - 1);
-    const int y0 = max(cy * CELL - 1, 0), y1 = min(cy * CELL + CELL, d.ny - 1);
-    const int z0 = max(cz * CELL - 1, 0), z1 = min(cz * CELL + CELL, d.nz - 1);
-    unsigned lo = 0xffu, hi = 0;
-    if (v.apron && (x0 == 0 || y0 == 0 || z0 == 0)) lo = hi = v.av;
-    const int a = v.apron;
-    for (int z = max(z0, a); z <= z1; z++)
-        for (int y = max(y0, a); y <= y1; y++) {
-            const uint8_t *row = v.base + (z - a) * v.sz + (y - a) * v.sy;
-            for (int x = max(x0, a); x <= x1; x++) {
-                const unsigned s = row[(x - a) * v.sx];
-                lo = min(lo, s);
-                hi = max(hi, s);
-            }
-        }
-    cells[2 * ci] = (uint8_t)lo;
-    cells[2 * ci + 1] = (uint8_t)hi;
-}
-
-struct Light {
-    float ka, kd, ks, pw, dx, dy, dz, isx, isy, isz, hx, hy, hz;
-};
-
-// the headlight of DESIGN.md section 7d at (x, y, z) on colour (cr, cg, cb)
-__device__ __forceinline__ void shade_at(const Field &v, const Dims &d, const Light &l, float x, float y, float z, float &cr,
-                                         float &cg, float &cb) {
-    // gradient in world axes: world y = -index y
-    const float gx = (tri(v, d, fminf(x + 1.0f, l.hx), y, z) - tri(v, d, fmaxf(x - 1.0f, 0.0f), y, z)) * l.isx;
-    const float gy = (tri(v, d, x, fmaxf(y - 1.0f, 0.0f), z) - tri(v, d, x, fminf(y + 1.0f, l.hy), z)) * l.isy;
-    const float gz = (tri(v, d, x, y, fminf(z + 1.0f, l.hz)) - tri(v, d, x, y, fmaxf(z - 1.0f, 0.0f))) * l.isz;
-    const float gn = sqrtf(gx * gx + gy * gy + gz * gz);
-    float ndl = 0.0f;
-    if (gn > 0.0f) ndl = fabsf(gx * l.dx + gy * l.dy + gz * l.dz) / gn;
-    const float diff = l.ka + l.kd * ndl;
-    const float spec = ndl > 0.0f ? l.ks * powf(ndl, l.pw) : 0.0f;
-    cr = clampf(cr * diff + spec, 0.0f, 1.0f);
-    cg = clampf(cg * diff + spec, 0.0f, 1.0f);
-    cb = clampf(cb * diff + spec, 0.0f, 1.0f);
-}
 
 template <bool ISOMODE>
 __global__ __launch_bounds__(64) void k_mr_render(Field v, const uint8_t *__restrict__ cells, Dims d, Dims c,
@@ -115,13 +39,8 @@ __global__ __launch_bounds__(64) void k_mr_render(Field v, const uint8_t *__rest
     RayCtx ray;
     if (active && setup_ray(p, d, px, py, ray)) {
         n_hit = 1;
-        const int nt = p.n_table;
-        Light l;
-        l.ka = (float)p.ambient, l.kd = (float)p.diffuse, l.ks = (float)p.specular, l.pw = (float)p.specular_power;
-        l.dx = (float)p.dir[0], l.dy = (float)p.dir[1], l.dz = (float)p.dir[2];
-        l.isx = (float)(0.5 / p.spacing[0]), l.isy = (float)(0.5 / p.spacing[1]), l.isz = (float)(0.5 / p.spacing[2]);
-        l.hx = (float)(d.nx - 1), l.hy = (float)(d.ny - 1), l.hz = (float)(d.nz - 1);
         if (ISOMODE) {
+            const Light l = make_light(p, d);
             // side: that of f[k - 1] - 127 (-1 / 0 / +1); f_prev is its value while have_prev
             int side = 0;
             bool have_prev = false;
@@ -173,73 +92,14 @@ __global__ __launch_bounds__(64) void k_mr_render(Field v, const uint8_t *__rest
                 k++;
             }
         } else {
-            float ar = 0.0f, ag = 0.0f, ab = 0.0f;
-            for (long long k = 0; k <= ray.kmax;) {
-                float x, y, z;
-                sample_pos(ray, d, k, x, y, z);
-                if (p.skip) {
-                    const int cx = (int)x / CELL, cy = (int)y / CELL, cz = (int)z / CELL;
-                    const int64_t ci = ((int64_t)cz * c.ny + cy) * c.nx + cx;
-                    if (prefix[(int)cells[2 * ci + 1] + 1] == prefix[(int)cells[2 * ci]]) {
-                        const long long kn = cell_exit(ray, d, k, cx, cy, cz);
-                        n_skipped += (unsigned long long)(kn - k);
-                        k = kn;
-                        continue;
-                    }
-                }
-                const float s = tri(v, d, x, y, z);
-                n_taken++;
-                const int i0 = min((int)s, nt - 2);
-                const float f = s - (float)i0;
-                const float4 e0 = table[i0], e1 = table[i0 + 1];
-                const float a = lerpf(e0.w, e1.w, f);
-                if (a > 0.0f) {
-                    float cr = lerpf(e0.x, e1.x, f), cg = lerpf(e0.y, e1.y, f), cb = lerpf(e0.z, e1.z, f);
-                    if (p.shade) shade_at(v, d, l, x, y, z, cr, cg, cb);
-                    const float w = (1.0f - A) * a;
-                    ar += w * cr;
-                    ag += w * cg;
-                    ab += w * cb;
-                    A += w;
-                    if (A >= OPAQUE) {
-                        n_early = 1;
-                        break;
-                    }
-                }
-                k++;
-            }
-            r = ar + (1.0f - A) * r;
-            g = ag + (1.0f - A) * g;
-            b = ab + (1.0f - A) * b;
+            composite_ray(v, cells, d, c, table, prefix, p, ray, r, g, b, A, n_taken, n_skipped, n_early);
         }
     }
     if (active) {
-        const int64_t o = ((int64_t)py * p.width + px) * 4;
-        if (p.out_u8) {
-            uint8_t *q = (uint8_t *)out + o;
-            const float vals[4] = {r, g, b, A};
-            for (int i = 0; i < 4; i++) q[i] = (uint8_t)clampf(floorf(255.0f * vals[i] + 0.5f), 0.0f, 255.0f);
-        } else {
-            float *q = (float *)out + o;
-            q[0] = r;
-            q[1] = g;
-            q[2] = b;
-            q[3] = A;
-        }
+        write_pixel(out, p, px, py, r, g, b, A);
         if (ISOMODE && depth) depth[(int64_t)py * p.width + px] = t_hit;
     }
-    if (stats) {
-        n_taken = wave_sum(n_taken);
-        n_skipped = wave_sum(n_skipped);
-        n_early = wave_sum(n_early);
-        n_hit = wave_sum(n_hit);
-        if (threadIdx.x == 0) {
-            atomicAdd(stats + 0, n_taken);
-            atomicAdd(stats + 1, n_skipped);
-            atomicAdd(stats + 2, n_early);
-            atomicAdd(stats + 3, n_hit);
-        }
-    }
+    add_stats(stats, n_taken, n_skipped, n_early, n_hit);
 }
 
 // the array's shape and strides with the apron as the logical field
@@ -278,7 +138,7 @@ extern "C" int ivx_dev_maskren_cells(const uint8_t *mask, const int64_t shape[3]
         cz1 = (int)((z1 / CELL) < c.nz - 1 ? (z1 / CELL) : c.nz - 1);
     }
     const int64_t nc = (int64_t)(cz1 - cz0 + 1) * c.ny * c.nx;
-    hipLaunchKernelGGL(k_mr_cells, dim3((unsigned)cdiv(nc, 256)), dim3(256), 0, S(stream), f, d, c, cz0, nc, cells);
+    hipLaunchKernelGGL(k_cells<Field>, dim3((unsigned)cdiv(nc, 256)), dim3(256), 0, S(stream), f, d, c, cz0, nc, cells);
     IVX_LAUNCH_CHECK();
     return IVX_OK;
 }

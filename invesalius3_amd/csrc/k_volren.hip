@@ -9,7 +9,9 @@
 //          shading from central differences, front-to-back compositing with early termination at A >= 1 - 2^-12, or the
 //          maximum intensity.  Empty-space skipping jumps over macro cells whose table entries [min - 1, max + 1] are all
 //          transparent (MIP: whose max cannot raise the running maximum); a jump lands only where every skipped sample
-//          lies in the cell, so skipping changes no bit.
+//          lies in the cell, so skipping changes no bit.  The rays, the trilinear sample, the
+//          headlight, the composite loop, the pixel write, the counters and the cells kernel are volren_ray.h's, read
+//          here through its DenseField; the maximum-intensity loop is this file's.
 // histogram: uint64 counts, privatised in LDS where the bins fit; integer atomics only.
 #include "ivx_internal.h"
 #include "volren_ray.h"
@@ -52,47 +54,6 @@ __global__ __launch_bounds__(256) void k_vr_smooth(const uint16_t *__restrict__ 
     out[((int64_t)z * d.ny + y) * d.nx + x] = (uint16_t)acc;
 }
 
-__global__ __launch_bounds__(256) void k_vr_cells(const uint16_t *__restrict__ v, Dims d, Dims c,
-                                                 uint16_t *__restrict__ cells) {
-    const int64_t ci = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t ncell = (int64_t)c.nz * c.ny * c.nx;
-    if (ci >= ncell) return;
-    const int cx = (int)(ci % c.nx), cy = (int)((ci / c.nx) % c.ny), cz = (int)(ci / ((int64_t)c.nx * c.ny));
-    const int x0 = max(cx * CELL - 1, 0), x1 = min(cx * CELL + CELL, d.nx - 1);
-    const int y0 = max(cy * CELL - 1, 0), y1 = min(cy * CELL + CELL, d.ny - 1);
-    const int z0 = max(cz * CELL - 1, 0), z1 = min(cz * CELL + CELL, d.nz - 1);
-    unsigned lo = 0xffffu, hi = 0;
-    for (int z = z0; z <= z1; z++)
-        for (int y = y0; y <= y1; y++) {
-            const uint16_t *row = v + ((int64_t)z * d.ny + y) * d.nx;
-            for (int x = x0; x <= x1; x++) {
-                const unsigned s = row[x];
-                lo = min(lo, s);
-                hi = max(hi, s);
-            }
-        }
-    cells[2 * ci] = (uint16_t)lo;
-    cells[2 * ci + 1] = (uint16_t)hi;
-}
-
-// trilinear interpolation at index position (x, y, z), already clamped to the volume
-__device__ __forceinline__ float tri(const uint16_t *__restrict__ v, const Dims &d, float x, float y, float z) {
-    int x0 = (int)x, y0 = (int)y, z0 = (int)z;
-    x0 = min(x0, max(d.nx - 2, 0));
-    y0 = min(y0, max(d.ny - 2, 0));
-    z0 = min(z0, max(d.nz - 2, 0));
-    const float fx = x - (float)x0, fy = y - (float)y0, fz = z - (float)z0;
-    const int x1 = min(x0 + 1, d.nx - 1), y1 = min(y0 + 1, d.ny - 1), z1 = min(z0 + 1, d.nz - 1);
-    const int64_t sy = d.nx, sz = (int64_t)d.ny * d.nx;
-    const uint16_t *p00 = v + z0 * sz + y0 * sy, *p01 = v + z0 * sz + y1 * sy;
-    const uint16_t *p10 = v + z1 * sz + y0 * sy, *p11 = v + z1 * sz + y1 * sy;
-    const float c00 = lerpf((float)p00[x0], (float)p00[x1], fx);
-    const float c01 = lerpf((float)p01[x0], (float)p01[x1], fx);
-    const float c10 = lerpf((float)p10[x0], (float)p10[x1], fx);
-    const float c11 = lerpf((float)p11[x0], (float)p11[x1], fx);
-    return lerpf(lerpf(c00, c01, fy), lerpf(c10, c11, fy), fz);
-}
-
 __global__ __launch_bounds__(64) void k_vr_render(const uint16_t *__restrict__ v, const uint16_t *__restrict__ cells, Dims d,
                                                  Dims c, const float4 *__restrict__ table, const float *__restrict__ alpha,
                                                  const uint32_t *__restrict__ prefix, ivx_volren_params p, void *out,
@@ -102,6 +63,7 @@ __global__ __launch_bounds__(64) void k_vr_render(const uint16_t *__restrict__ v
     const bool active = px < p.width && py < p.height;
     unsigned long long n_taken = 0, n_skipped = 0, n_early = 0, n_hit = 0;
     float r = (float)p.background[0], g = (float)p.background[1], b = (float)p.background[2], A = 0.0f;
+    const DenseField fld{v, (int64_t)d.ny * d.nx, d.nx};
     RayCtx ray;
     if (active && setup_ray(p, d, px, py, ray)) {
         n_hit = 1;
@@ -122,7 +84,7 @@ __global__ __launch_bounds__(64) void k_vr_render(const uint16_t *__restrict__ v
                         continue;
                     }
                 }
-                const float s = tri(v, d, x, y, z);
+                const float s = tri(fld, d, x, y, z);
                 n_taken++;
                 if (s > vmax) vmax = s;
                 k++;
@@ -139,90 +101,11 @@ __global__ __launch_bounds__(64) void k_vr_render(const uint16_t *__restrict__ v
                 A = a;
             }
         } else {
-            const float ka = (float)p.ambient, kd = (float)p.diffuse, ks = (float)p.specular, pw = (float)p.specular_power;
-            const float dx = (float)p.dir[0], dy = (float)p.dir[1], dz = (float)p.dir[2];
-            const float isx = (float)(0.5 / p.spacing[0]), isy = (float)(0.5 / p.spacing[1]), isz = (float)(0.5 / p.spacing[2]);
-            const float hx = (float)(d.nx - 1), hy = (float)(d.ny - 1), hz = (float)(d.nz - 1);
-            float ar = 0.0f, ag = 0.0f, ab = 0.0f;
-            for (long long k = 0; k <= ray.kmax;) {
-                float x, y, z;
-                sample_pos(ray, d, k, x, y, z);
-                if (p.skip) {
-                    const int cx = (int)x / CELL, cy = (int)y / CELL, cz = (int)z / CELL;
-                    const int64_t ci = ((int64_t)cz * c.ny + cy) * c.nx + cx;
-                    const int lo = max((int)cells[2 * ci] - 1, 0), hi = min((int)cells[2 * ci + 1] + 1, nt - 1);
-                    if (prefix[hi + 1] == prefix[lo]) {
-                        const long long kn = cell_exit(ray, d, k, cx, cy, cz);
-                        n_skipped += (unsigned long long)(kn - k);
-                        k = kn;
-                        continue;
-                    }
-                }
-                const float s = tri(v, d, x, y, z);
-                n_taken++;
-                const int i0 = min((int)s, nt - 2);
-                const float f = s - (float)i0;
-                const float4 e0 = table[i0], e1 = table[i0 + 1];
-                const float a = lerpf(e0.w, e1.w, f);
-                if (a > 0.0f) {
-                    float cr = lerpf(e0.x, e1.x, f), cg = lerpf(e0.y, e1.y, f), cb = lerpf(e0.z, e1.z, f);
-                    if (p.shade) {
-                        // gradient in world axes: world y = -index y
-                        const float gx = (tri(v, d, fminf(x + 1.0f, hx), y, z) - tri(v, d, fmaxf(x - 1.0f, 0.0f), y, z)) * isx;
-                        const float gy = (tri(v, d, x, fmaxf(y - 1.0f, 0.0f), z) - tri(v, d, x, fminf(y + 1.0f, hy), z)) * isy;
-                        const float gz = (tri(v, d, x, y, fminf(z + 1.0f, hz)) - tri(v, d, x, y, fmaxf(z - 1.0f, 0.0f))) * isz;
-                        const float gn = sqrtf(gx * gx + gy * gy + gz * gz);
-                        float ndl = 0.0f;
-                        if (gn > 0.0f) ndl = fabsf(gx * dx + gy * dy + gz * dz) / gn;
-                        const float diff = ka + kd * ndl;
-                        const float spec = ndl > 0.0f ? ks * powf(ndl, pw) : 0.0f;
-                        cr = clampf(cr * diff + spec, 0.0f, 1.0f);
-                        cg = clampf(cg * diff + spec, 0.0f, 1.0f);
-                        cb = clampf(cb * diff + spec, 0.0f, 1.0f);
-                    }
-                    const float w = (1.0f - A) * a;
-                    ar += w * cr;
-                    ag += w * cg;
-                    ab += w * cb;
-                    A += w;
-                    if (A >= OPAQUE) {
-                        n_early = 1;
-                        break;
-                    }
-                }
-                k++;
-            }
-            r = ar + (1.0f - A) * r;
-            g = ag + (1.0f - A) * g;
-            b = ab + (1.0f - A) * b;
+            composite_ray(fld, cells, d, c, table, prefix, p, ray, r, g, b, A, n_taken, n_skipped, n_early);
         }
     }
-    if (active) {
-        const int64_t o = ((int64_t)py * p.width + px) * 4;
-        if (p.out_u8) {
-            uint8_t *q = (uint8_t *)out + o;
-            const float vals[4] = {r, g, b, A};
-            for (int i = 0; i < 4; i++) q[i] = (uint8_t)clampf(floorf(255.0f * vals[i] + 0.5f), 0.0f, 255.0f);
-        } else {
-            float *q = (float *)out + o;
-            q[0] = r;
-            q[1] = g;
-            q[2] = b;
-            q[3] = A;
-        }
-    }
-    if (stats) {
-        n_taken = wave_sum(n_taken);
-        n_skipped = wave_sum(n_skipped);
-        n_early = wave_sum(n_early);
-        n_hit = wave_sum(n_hit);
-        if (threadIdx.x == 0) {
-            atomicAdd(stats + 0, n_taken);
-            atomicAdd(stats + 1, n_skipped);
-            atomicAdd(stats + 2, n_early);
-            atomicAdd(stats + 3, n_hit);
-        }
-    }
+    if (active) write_pixel(out, p, px, py, r, g, b, A);
+    add_stats(stats, n_taken, n_skipped, n_early, n_hit);
 }
 
 __global__ __launch_bounds__(256) void k_vr_hist_lds(const int16_t *__restrict__ img, int64_t n, int lo, int nbins,
@@ -284,7 +167,8 @@ extern "C" int ivx_dev_volren_cells(const uint16_t *vol, const int64_t shape[3],
     IVX_REQUIRE(vol && cells, IVX_EINVAL, "volren: null buffer");
     const Dims c = cell_dims(d);
     const int64_t nc = (int64_t)c.nz * c.ny * c.nx;
-    hipLaunchKernelGGL(k_vr_cells, dim3((unsigned)cdiv(nc, 256)), dim3(256), 0, S(stream), vol, d, c, cells);
+    const DenseField f{vol, (int64_t)d.ny * d.nx, d.nx};
+    hipLaunchKernelGGL(k_cells<DenseField>, dim3((unsigned)cdiv(nc, 256)), dim3(256), 0, S(stream), f, d, c, 0, nc, cells);
     IVX_LAUNCH_CHECK();
     return IVX_OK;
 }

@@ -970,44 +970,53 @@ class DeviceVolume:
             setattr(owner, name, b)
         return b
 
+    def _render(self, bufs: str, size, rgba8: bool, depth: bool, download: bool, launch):
+        """What the two renders share: grow the `bufs`_out and _stats (with `depth` also _depth) buffers, zero the
+        counters and `launch(out, depth buffer or None, stats)`; then return the device buffer(s), or with `download`
+        sync, leave the sample counts in ``last_render_stats`` and return the arrays."""
+        w, h = size
+        out = self._grow(self, bufs + "_out", w * h * 4 * (1 if rgba8 else 4))
+        dep = self._grow(self, bufs + "_depth", w * h * 4) if depth else None
+        stats = self._grow(self, bufs + "_stats", 32)
+        stats.zero(self.stream, 32)
+        launch(out, dep, stats)
+        if download:
+            self.sync()
+            st = stats.download((4,), np.uint64)
+            self.last_render_stats = {"samples": int(st[0]), "skipped": int(st[1]), "early": int(st[2]),
+                                      "rays_hit": int(st[3]), "rays": w * h}
+            out = out.download((h, w, 4), np.uint8 if rgba8 else np.float32)
+            dep = dep.download((h, w), np.float32) if depth else None
+        return (out, dep) if depth else out
+
     def render_volume(self, preset, camera, size, clip_plane=None, shade=None, color_lists=None, download: bool = True,
                       rgba8: bool = False, presets_dir=None):
         """The 3-D view of the resident image with a raycasting preset (a dict, a .plist path, or a name in
         `presets_dir`).  `camera`: a standard view name ("front", "back", "left", "right", "top", "bottom", "iso") or a
         dict from volume.camera_for_view; `size` (width, height) in pixels.  `shade` None follows the preset's useShading
         (see volume.shading).  Returns (height, width, 4) float32 RGBA (uint8 with `rgba8`), or the device buffer when not
-        `download`.  The sample counts of the render are left in ``last_render_stats``."""
+        `download`.  The sample counts are left in ``last_render_stats`` by a downloading render; without `download`
+        nothing is waited for, so they stay those of the last render that did."""
         from . import volume as V
 
-        w, h = int(size[0]), int(size[1])
-        if isinstance(camera, str):
-            cam = V.camera_for_view(camera, self.shape, self.spacing, (w, h))
-        else:
-            cam = dict(camera, viewport=(w, h))
+        cam = V.resolve_camera(camera, self.shape, self.spacing, size)
         scale = self._image_scale()
         setup = V.render_setup(preset, scale, cam, clip_plane, shade, color_lists, presets_dir)
         vr = self._volren_field(setup["shift"], setup["kernels"])
         rgba, alpha, prefix = V.device_tables(setup)
         tb = self._grow(self, "_vr_table", rgba.nbytes + alpha.nbytes + prefix.nbytes)
-        lib = L.lib()
         self.sync()  # the table buffer may still be read by the previous render
         host = np.concatenate([rgba.view(np.uint8).ravel(), alpha.view(np.uint8).ravel(), prefix.view(np.uint8).ravel()])
         tb.upload(host)
         p = V.volren_params(setup, self.spacing, rgba8)
-        out = self._grow(self, "_vr_out", w * h * 4 * (1 if rgba8 else 4))
-        stats = self._grow(self, "_vr_stats", 32)
-        stats.zero(self.stream, 32)
-        L.check(lib.ivx_dev_volren_render(vr["vol"].ptr, vr["cells"].ptr, L.i64(self.shape), tb.ptr,
-                                          tb.at(rgba.nbytes), tb.at(rgba.nbytes + alpha.nbytes), ctypes.byref(p), out.ptr,
-                                          stats.ptr, self.stream), "render_volume")
-        self._vr_setup = setup
-        if not download:
-            return out
-        self.sync()
-        st = stats.download((4,), np.uint64)
-        self.last_render_stats = {"samples": int(st[0]), "skipped": int(st[1]), "early": int(st[2]), "rays_hit": int(st[3]),
-                                  "rays": w * h}
-        return out.download((h, w, 4), np.uint8 if rgba8 else np.float32)
+
+        def launch(out, dep, stats):
+            L.check(L.lib().ivx_dev_volren_render(vr["vol"].ptr, vr["cells"].ptr, L.i64(self.shape), tb.ptr,
+                                                  tb.at(rgba.nbytes), tb.at(rgba.nbytes + alpha.nbytes), ctypes.byref(p),
+                                                  out.ptr, stats.ptr, self.stream), "render_volume")
+            self._vr_setup = setup
+
+        return self._render("_vr", cam["viewport"], rgba8, False, download, launch)
 
     # -- mask 3-D preview (VolumeMask.create_volume, volume_mask.py:36-119) ----------------------------------------------
     def _drop_maskren(self):
@@ -1049,11 +1058,7 @@ class DeviceVolume:
 
         if depth and mode != "iso":
             raise ValueError("depth is an output of the iso mode")
-        w, h = int(size[0]), int(size[1])
-        if isinstance(camera, str):
-            cam = V.camera_for_view(camera, self.shape, self.spacing, (w, h))
-        else:
-            cam = dict(camera, viewport=(w, h))
+        cam = V.resolve_camera(camera, self.shape, self.spacing, size)
         setup = VM.render_setup(colour, mode, cam, self.spacing, background, sample_distance)
         rgba, prefix = VM.device_tables(setup)
         cells = self._maskren_cells(apron_value)
@@ -1064,23 +1069,15 @@ class DeviceVolume:
             tb.upload(np.concatenate([rgba.view(np.uint8).ravel(), prefix.view(np.uint8).ravel()]))
             self._mp_table_key = key
         p = V.volren_params(setup, self.spacing, rgba8)
-        out = self._grow(self, "_mp_out", w * h * 4 * (1 if rgba8 else 4))
-        dep = self._grow(self, "_mp_depth", w * h * 4) if depth else None
-        stats = self._grow(self, "_mp_stats", 32)
-        stats.zero(self.stream, 32)
-        L.check(L.lib().ivx_dev_maskren_render(self.mask.raw, cells.ptr, L.i64(self.shape),
-                                               L.i64([self.dy * self.dx, self.dx, 1]), 1, int(apron_value), int(setup["iso"]),
-                                               tb.ptr, tb.at(rgba.nbytes), ctypes.byref(p), out.ptr,
-                                               None if dep is None else dep.ptr, stats.ptr, self.stream),
-                "render_mask_preview")
-        if not download:
-            return (out, dep) if depth else out
-        self.sync()
-        st = stats.download((4,), np.uint64)
-        self.last_render_stats = {"samples": int(st[0]), "skipped": int(st[1]), "early": int(st[2]), "rays_hit": int(st[3]),
-                                  "rays": w * h}
-        img = out.download((h, w, 4), np.uint8 if rgba8 else np.float32)
-        return (img, dep.download((h, w), np.float32)) if depth else img
+
+        def launch(out, dep, stats):
+            L.check(L.lib().ivx_dev_maskren_render(self.mask.raw, cells.ptr, L.i64(self.shape),
+                                                   L.i64([self.dy * self.dx, self.dx, 1]), 1, int(apron_value),
+                                                   int(setup["iso"]), tb.ptr, tb.at(rgba.nbytes), ctypes.byref(p), out.ptr,
+                                                   None if dep is None else dep.ptr, stats.ptr, self.stream),
+                    "render_mask_preview")
+
+        return self._render("_mp", cam["viewport"], rgba8, depth, download, launch)
 
     def volume_histogram(self) -> np.ndarray:
         """CalculateHistogram (volume.py:723-735) of the resident image: uint64 counts of the int(max - min) unit bins

@@ -370,6 +370,15 @@ def camera_for_view(view: str, shape, spacing, viewport) -> dict:
             "parallel_scale": radius if scale is None else scale, "viewport": (w_px, h_px)}
 
 
+def resolve_camera(view, shape, spacing, size) -> dict:
+    """A standard view name as camera_for_view's camera of the image `shape`, or a camera dict as it is; either way
+    with the viewport `size` (width, height)."""
+    viewport = (int(size[0]), int(size[1]))
+    if isinstance(view, str):
+        return camera_for_view(view, shape, spacing, viewport)
+    return dict(view, viewport=viewport)
+
+
 def pixel_rays(cam: dict):
     """World position of pixel (0, 0)'s centre on the plane through the focal point, and the steps per column / row
     (row 0 is the top of the viewport)."""
@@ -490,12 +499,12 @@ def device_tables(setup: dict):
 def volume_render(image: np.ndarray, spacing, preset, view="iso", size=(512, 512), clip_plane=None, shade=None,
                   color_lists=None, presets_dir=None, rgba8: bool = False) -> np.ndarray:
     """Host form (ivx_volume_render): the int16 (z, y, x) image over PCIe, rendered with `preset` from a standard `view`
-    (or a camera dict from camera_for_view); returns (H, W, 4) float32 RGBA, or uint8 with `rgba8`."""
+    (or a camera dict from camera_for_view) at `size`; returns (H, W, 4) float32 RGBA, or uint8 with `rgba8`."""
     from . import _lib as L
 
     if image.dtype != np.int16 or image.ndim != 3:
         raise TypeError("image must be a 3-D int16 array")
-    cam = camera_for_view(view, image.shape, spacing, size) if isinstance(view, str) else view
+    cam = resolve_camera(view, image.shape, spacing, size)
     setup = render_setup(preset, (int(image.min()), int(image.max())), cam, clip_plane, shade, color_lists, presets_dir)
     rgba, alpha, prefix = device_tables(setup)
     p = volren_params(setup, spacing, rgba8)

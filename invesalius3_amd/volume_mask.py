@@ -128,8 +128,7 @@ def mask_preview(matrix: np.ndarray, spacing, colour, view="iso", size=(512, 512
     if depth and mode != "iso":
         raise ValueError("depth is an output of the iso mode")
     shape = tuple(int(s) - 1 for s in matrix.shape)
-    cam = V.camera_for_view(view, shape, spacing, size) if isinstance(view, str) else dict(
-        view, viewport=(int(size[0]), int(size[1])))
+    cam = V.resolve_camera(view, shape, spacing, size)
     setup = render_setup(colour, mode, cam, spacing, background, sample_distance)
     rgba, prefix = device_tables(setup)
     p = V.volren_params(setup, spacing, rgba8)

@@ -5,9 +5,10 @@ vectorised over rays.  Test infrastructure only: the product never imports it.
     cells(matrix)                      per 8^3 macro cell (min, max) with a one-voxel apron
     render(matrix, spacing, setup)     a dict: image (H, W, 4), depth, margin, in_box for a volume_mask.render_setup dict
 
-The composite mode is tests/_volren_ref.py's render on the byte field.  The iso mode is restated here; with
-``f32=True`` the sample positions and the interpolation run in emulated float32 (the kernel's number format), which is
-how a test checks, without a GPU, that its inputs keep the two formats' decisions apart only on the rays it leaves out.
+The composite mode is tests/_volren_ref.py's render on the byte field.  The iso mode is restated here on that file's
+rays, tri, gradient and headlight; with ``f32=True`` the sample positions and the interpolation run in emulated float32
+(the kernel's number format), which is how a test checks, without a GPU, that its inputs keep the two formats' decisions
+apart only on the rays it leaves out.
 """
 import numpy as np
 
@@ -27,72 +28,18 @@ def cells(matrix):
     return R.cells(matrix).astype(np.uint8)
 
 
-def _tri(v, x, y, z, ft):
-    nz, ny, nx = v.shape
-    x0 = np.minimum(np.floor(x).astype(np.int64), max(nx - 2, 0))
-    y0 = np.minimum(np.floor(y).astype(np.int64), max(ny - 2, 0))
-    z0 = np.minimum(np.floor(z).astype(np.int64), max(nz - 2, 0))
-    fx, fy, fz = x - x0.astype(ft), y - y0.astype(ft), z - z0.astype(ft)
-    x1, y1, z1 = np.minimum(x0 + 1, nx - 1), np.minimum(y0 + 1, ny - 1), np.minimum(z0 + 1, nz - 1)
-
-    def f(k, j, i):
-        return v[k, j, i].astype(ft)
-
-    def lerp(a, b, t):
-        return a + t * (b - a)
-
-    c00 = lerp(f(z0, y0, x0), f(z0, y0, x1), fx)
-    c01 = lerp(f(z0, y1, x0), f(z0, y1, x1), fx)
-    c10 = lerp(f(z1, y0, x0), f(z1, y0, x1), fx)
-    c11 = lerp(f(z1, y1, x0), f(z1, y1, x1), fx)
-    return lerp(lerp(c00, c01, fy), lerp(c10, c11, fy), fz)
-
-
-def rays(matrix_shape, spacing, setup, pixels=None):
-    """(px, py, A, B, tin, kmax, shape_out): the rays of volren_ray.h in float64 for the logical field `matrix_shape`"""
-    nz, ny, nx = matrix_shape
-    sx, sy, sz = [float(s) for s in spacing]
-    w, h = setup["viewport"]
-    if pixels is None:
-        py, px = np.mgrid[0:h, 0:w]
-    else:
-        py, px = np.asarray(pixels[0]), np.asarray(pixels[1])
-    px, py = px.ravel().astype(np.float64), py.ravel().astype(np.float64)
-    P0 = setup["origin"][None, :] + px[:, None] * setup["du"][None, :] + py[:, None] * setup["dv"][None, :]
-    d = np.asarray(setup["dir"], np.float64)
-    A = np.stack([P0[:, 0] / sx, -P0[:, 1] / sy, P0[:, 2] / sz], 1)
-    B = np.array([d[0] / sx, -d[1] / sy, d[2] / sz])
-    hi = np.array([nx - 1, ny - 1, nz - 1], np.float64)
-    tin = np.full(len(px), -1e300)
-    tout = np.full(len(px), 1e300)
-    hit = np.ones(len(px), bool)
-    for a in range(3):
-        if B[a] != 0.0:
-            t0, t1 = (0.0 - A[:, a]) / B[a], (hi[a] - A[:, a]) / B[a]
-            tin = np.maximum(tin, np.minimum(t0, t1))
-            tout = np.minimum(tout, np.maximum(t0, t1))
-        else:
-            hit &= (A[:, a] >= 0) & (A[:, a] <= hi[a])
-    hit &= tin <= tout
-    dt = setup["dt"]
-    kmax = np.where(hit, np.floor((tout - tin) / np.where(hit, dt, 1.0)), -1).astype(np.int64)
-    return A, B, hi, tin, kmax
-
-
 def render(matrix, spacing, setup, pixels=None, f32=False):
     """`matrix`: the padded uint8 matrix (flag planes included).  Returns {"image": (H, W, 4) float64 (or (len, 4) with
     `pixels`), "in_box": rays that meet the box, and in the iso mode "depth" (inf without a hit) and "margin", the
     smallest |f(t_k) - 127| over a ray's samples up to its hit (inf for a ray without samples)}."""
     w, h = setup["viewport"]
-    A, B, hi, tin, kmax = rays(matrix.shape, spacing, setup, pixels)
+    A, B, hi, tin, kmax = R.rays(matrix.shape, spacing, setup, pixels)
     n = len(tin)
     shape = (h, w) if pixels is None else (n,)
     if not setup["iso"]:
         assert not f32
         return {"image": R.render(matrix, spacing, setup, pixels), "in_box": (kmax >= 0).reshape(shape)}
     ft = np.float32 if f32 else np.float64
-    sx, sy, sz = [float(s) for s in spacing]
-    d = np.asarray(setup["dir"], np.float64)
     dt = setup["dt"]
     safe_tin = np.where(kmax >= 0, tin, 0.0)
     I0 = (A + safe_tin[:, None] * B[None, :]).astype(ft)  # the kernel's float32 ray: sample 0 and the step per sample
@@ -115,7 +62,7 @@ def render(matrix, spacing, setup, pixels=None, f32=False):
         if len(act) == 0:
             break
         p = pos(act, np.full(len(act), k))
-        f = _tri(matrix, p[:, 0], p[:, 1], p[:, 2], ft)
+        f = R.tri(matrix, p[:, 0], p[:, 1], p[:, 2], ft)
         margin[act] = np.minimum(margin[act], np.abs(f.astype(np.float64) - ISO))
         if k >= 1:
             fp = f_prev[act]
@@ -127,19 +74,9 @@ def render(matrix, spacing, setup, pixels=None, f32=False):
                 exact = fk == ft(ISO)
                 wgt = np.where(exact, ft(1), (ft(ISO) - fp) / np.where(exact, ft(1), fk - fp)).astype(ft)
                 ph = np.where(exact[:, None], pk, pp + wgt[:, None] * (pk - pp))
-                x, y, z = ph[:, 0], ph[:, 1], ph[:, 2]
-                one = ft(1)
-                gx = (_tri(matrix, np.minimum(x + one, hif[0]), y, z, ft) - _tri(matrix, np.maximum(x - one, 0), y, z, ft))
-                gy = (_tri(matrix, x, np.maximum(y - one, 0), z, ft) - _tri(matrix, x, np.minimum(y + one, hif[1]), z, ft))
-                gz = (_tri(matrix, x, y, np.minimum(z + one, hif[2]), ft) - _tri(matrix, x, y, np.maximum(z - one, 0), ft))
-                gx, gy, gz = gx.astype(np.float64) / (2 * sx), gy.astype(np.float64) / (2 * sy), gz.astype(np.float64) / (2 * sz)
                 c = np.repeat(colour[None, :], len(idx), 0)
                 if setup["shade"]:
-                    gn = np.sqrt(gx * gx + gy * gy + gz * gz)
-                    ndl = np.where(gn > 0, np.abs(gx * d[0] + gy * d[1] + gz * d[2]) / np.where(gn > 0, gn, 1.0), 0.0)
-                    diff = setup["ambient"] + setup["diffuse"] * ndl
-                    spec = np.where(ndl > 0, setup["specular"] * np.power(ndl, setup["specular_power"]), 0.0)
-                    c = np.clip(c * diff[:, None] + spec[:, None], 0.0, 1.0)
+                    c = R.headlight(matrix, ph[:, 0], ph[:, 1], ph[:, 2], hif, spacing, setup, c, ft)
                 out[idx, :3] = c
                 out[idx, 3] = 1.0
                 depth[idx] = tin[idx] + ((k - 1) + wgt.astype(np.float64)) * dt
@@ -207,11 +144,10 @@ def noise_gradients(matrix, spacing, setup, floor=1e-3):
     are not zero yet below `floor`: there the true gradient is zero and the shading's N = g / |g| is the direction of
     rounding noise, in float64 as much as in float32 (a difference of two bytes' interpolations is either 0 or far above
     1e-3 unless it is noise: the field's slopes are whole bytes per voxel).  An input for a colour comparison has none."""
-    A, B, hi, tin, kmax = rays(matrix.shape, spacing, setup)
+    A, B, hi, tin, kmax = R.rays(matrix.shape, spacing, setup)
     I0 = A + np.where(kmax >= 0, tin, 0.0)[:, None] * B[None, :]
     S = B * setup["dt"]
     live = kmax >= 0
-    ft = np.float64
     count = 0
     for k in range(int(kmax.max(initial=-1)) + 1):
         act = np.nonzero(live & (kmax >= k))[0]
@@ -219,11 +155,9 @@ def noise_gradients(matrix, spacing, setup, floor=1e-3):
             break
         p = np.clip(I0[act] + k * S[None, :], 0.0, hi[None, :])
         x, y, z = p[:, 0], p[:, 1], p[:, 2]
-        gx = _tri(matrix, np.minimum(x + 1, hi[0]), y, z, ft) - _tri(matrix, np.maximum(x - 1, 0), y, z, ft)
-        gy = _tri(matrix, x, np.maximum(y - 1, 0), z, ft) - _tri(matrix, x, np.minimum(y + 1, hi[1]), z, ft)
-        gz = _tri(matrix, x, y, np.minimum(z + 1, hi[2]), ft) - _tri(matrix, x, y, np.maximum(z - 1, 0), ft)
+        gx, gy, gz = R.gradient(matrix, x, y, z, hi)
         gn = np.sqrt(gx * gx + gy * gy + gz * gz)
-        f = _tri(matrix, x, y, z, ft)
+        f = R.tri(matrix, x, y, z)
         count += int(np.count_nonzero((gn > 0) & (gn < floor) & (f > 0)))
         live[act[f >= ISO]] = False  # opacity 1 from 127 on: the ray ends
     return count

@@ -4,6 +4,8 @@ vectorised over rays.  Test infrastructure only: the product never imports it.
     prepare(img, shift, kernels)          the uint16 field: shift, then each 5x5 pass in row-major tap order (bit for bit)
     cells(field)                          per 8^3 macro cell (min, max) with a one-voxel apron
     render(field, spacing, setup)         (H, W, 4) float64 RGBA for a volume.render_setup(...) dict
+    rays / tri / gradient / headlight     the pieces of render that tests/_maskren_ref.py shares; `ft` np.float32 runs
+                                          the interpolation in the kernels' number format
 """
 import numpy as np
 
@@ -43,16 +45,16 @@ def cells(field):
     return out
 
 
-def _tri(v, x, y, z):
+def tri(v, x, y, z, ft=np.float64):
     nz, ny, nx = v.shape
     x0 = np.minimum(np.floor(x).astype(np.int64), max(nx - 2, 0))
     y0 = np.minimum(np.floor(y).astype(np.int64), max(ny - 2, 0))
     z0 = np.minimum(np.floor(z).astype(np.int64), max(nz - 2, 0))
-    fx, fy, fz = x - x0, y - y0, z - z0
+    fx, fy, fz = x - x0.astype(ft), y - y0.astype(ft), z - z0.astype(ft)
     x1, y1, z1 = np.minimum(x0 + 1, nx - 1), np.minimum(y0 + 1, ny - 1), np.minimum(z0 + 1, nz - 1)
 
     def f(k, j, i):
-        return v[k, j, i].astype(np.float64)
+        return v[k, j, i].astype(ft)
 
     def lerp(a, b, t):
         return a + t * (b - a)
@@ -64,6 +66,27 @@ def _tri(v, x, y, z):
     return lerp(lerp(c00, c01, fy), lerp(c10, c11, fy), fz)
 
 
+def gradient(v, x, y, z, hi, ft=np.float64):
+    """central differences of the field per two index units, in world axes (world y = -index y)"""
+    one = ft(1)
+    gx = tri(v, np.minimum(x + one, hi[0]), y, z, ft) - tri(v, np.maximum(x - one, 0), y, z, ft)
+    gy = tri(v, x, np.maximum(y - one, 0), z, ft) - tri(v, x, np.minimum(y + one, hi[1]), z, ft)
+    gz = tri(v, x, y, np.minimum(z + one, hi[2]), ft) - tri(v, x, y, np.maximum(z - one, 0), ft)
+    return gx, gy, gz
+
+
+def headlight(v, x, y, z, hi, spacing, setup, c, ft=np.float64):
+    """the colours `c` (n, 3) at (x, y, z) under the headlight: ambient, diffuse and specular terms of |N . dir| with N
+    along the world gradient, in float64 from the gradient's differences on"""
+    d = np.asarray(setup["dir"], np.float64)
+    gx, gy, gz = [g.astype(np.float64) / (2 * float(s)) for g, s in zip(gradient(v, x, y, z, hi, ft), spacing)]
+    gn = np.sqrt(gx * gx + gy * gy + gz * gz)
+    ndl = np.where(gn > 0, np.abs(gx * d[0] + gy * d[1] + gz * d[2]) / np.where(gn > 0, gn, 1.0), 0.0)
+    diff = setup["ambient"] + setup["diffuse"] * ndl
+    spec = np.where(ndl > 0, setup["specular"] * np.power(ndl, setup["specular_power"]), 0.0)
+    return np.clip(c * diff[:, None] + spec[:, None], 0.0, 1.0)
+
+
 def _classify(setup, s, table):
     n = len(setup["alpha"])
     i0 = np.minimum(np.floor(s).astype(np.int64), n - 2)
@@ -71,9 +94,11 @@ def _classify(setup, s, table):
     return table[i0] + f * (table[i0 + 1] - table[i0])
 
 
-def render(field, spacing, setup, pixels=None):
-    """`pixels`: optional (rows, cols) index arrays; then the result is (len, 4) for those pixels only"""
-    nz, ny, nx = field.shape
+def rays(shape, spacing, setup, pixels=None):
+    """(A, B, hi, tin, kmax): the rays of volren_ray.h in float64 for the field `shape`, of every pixel or of `pixels`
+    (rows, cols): index position A + t B at world distance t, the last index per axis, the first sample's distance and
+    the last sample's number (-1: the ray misses the box or the clip plane's kept side)"""
+    nz, ny, nx = shape
     sx, sy, sz = [float(s) for s in spacing]
     w, h = setup["viewport"]
     if pixels is None:
@@ -81,7 +106,6 @@ def render(field, spacing, setup, pixels=None):
     else:
         py, px = np.asarray(pixels[0]), np.asarray(pixels[1])
     px, py = px.ravel().astype(np.float64), py.ravel().astype(np.float64)
-    shape_out = (h, w, 4) if pixels is None else (len(px), 4)
     P0 = setup["origin"][None, :] + px[:, None] * setup["du"][None, :] + py[:, None] * setup["dv"][None, :]
     d = np.asarray(setup["dir"], np.float64)
     A = np.stack([P0[:, 0] / sx, -P0[:, 1] / sy, P0[:, 2] / sz], 1)
@@ -108,19 +132,28 @@ def render(field, spacing, setup, pixels=None):
         else:
             hit &= c0 >= 0
     hit &= tin <= tout
+    kmax = np.where(hit, np.floor((tout - tin) / np.where(hit, setup["dt"], 1.0)), -1).astype(np.int64)
+    return A, B, hi, tin, kmax
+
+
+def render(field, spacing, setup, pixels=None):
+    """`pixels`: optional (rows, cols) index arrays; then the result is (len, 4) for those pixels only"""
+    w, h = setup["viewport"]
+    A, B, hi, tin, kmax = rays(field.shape, spacing, setup, pixels)
+    n = len(tin)
+    shape_out = (h, w, 4) if pixels is None else (n, 4)
     dt = setup["dt"]
-    kmax = np.where(hit, np.floor((tout - tin) / np.where(hit, dt, 1.0)), -1).astype(np.int64)
     bg = np.asarray(setup["background"], np.float64)
-    out = np.zeros((len(px), 4))
+    out = np.zeros((n, 4))
     out[:, :3] = bg
     table = np.concatenate([setup["rgba"][:, :3], setup["alpha"][:, None]], 1)
     if setup["mip"]:
-        vmax = np.full(len(px), -1.0)
+        vmax = np.full(n, -1.0)
         for k in range(int(kmax.max(initial=-1)) + 1):
             act = np.nonzero(kmax >= k)[0]
             pos = A[act] + (tin[act] + k * dt)[:, None] * B[None, :]
             pos = np.clip(pos, 0.0, hi[None, :])
-            s = _tri(field, pos[:, 0], pos[:, 1], pos[:, 2])
+            s = tri(field, pos[:, 0], pos[:, 1], pos[:, 2])
             vmax[act] = np.maximum(vmax[act], s)
         got = np.nonzero(vmax >= 0)[0]
         e = _classify(setup, vmax[got], table)
@@ -128,8 +161,8 @@ def render(field, spacing, setup, pixels=None):
         out[got, :3] = a * e[:, :3] + (1 - a) * bg[None, :]
         out[got, 3] = a[:, 0]
         return out.reshape(shape_out)
-    acc = np.zeros((len(px), 3))
-    alpha = np.zeros(len(px))
+    acc = np.zeros((n, 3))
+    alpha = np.zeros(n)
     live = kmax >= 0
     for k in range(int(kmax.max(initial=-1)) + 1):
         act = np.nonzero(live & (kmax >= k))[0]
@@ -138,21 +171,14 @@ def render(field, spacing, setup, pixels=None):
         pos = A[act] + (tin[act] + k * dt)[:, None] * B[None, :]
         pos = np.clip(pos, 0.0, hi[None, :])
         x, y, z = pos[:, 0], pos[:, 1], pos[:, 2]
-        s = _tri(field, x, y, z)
+        s = tri(field, x, y, z)
         e = _classify(setup, s, setup["rgba"])
         a = e[:, 3]
         m = a > 0
         act, e, a, x, y, z = act[m], e[m], a[m], x[m], y[m], z[m]
         c = e[:, :3]
         if setup["shade"] and len(act):
-            gx = (_tri(field, np.minimum(x + 1, hi[0]), y, z) - _tri(field, np.maximum(x - 1, 0), y, z)) / (2 * sx)
-            gy = (_tri(field, x, np.maximum(y - 1, 0), z) - _tri(field, x, np.minimum(y + 1, hi[1]), z)) / (2 * sy)
-            gz = (_tri(field, x, y, np.minimum(z + 1, hi[2])) - _tri(field, x, y, np.maximum(z - 1, 0))) / (2 * sz)
-            gn = np.sqrt(gx * gx + gy * gy + gz * gz)
-            ndl = np.where(gn > 0, np.abs(gx * d[0] + gy * d[1] + gz * d[2]) / np.where(gn > 0, gn, 1.0), 0.0)
-            diff = setup["ambient"] + setup["diffuse"] * ndl
-            spec = np.where(ndl > 0, setup["specular"] * np.power(ndl, setup["specular_power"]), 0.0)
-            c = np.clip(c * diff[:, None] + spec[:, None], 0.0, 1.0)
+            c = headlight(field, x, y, z, hi, spacing, setup, c)
         wgt = (1 - alpha[act]) * a
         acc[act] += wgt[:, None] * c
         alpha[act] += wgt

@@ -126,7 +126,9 @@ def _check(got, matrix, spacing, setup):
 @pytest.mark.parametrize("view", ["front", "iso"])
 def test_composite_equals_the_volume_renderer_on_the_same_bytes(ivxlib, name, shade, view):
     """the dense field without apron through ivx_dev_maskren_* and, widened to uint16, through ivx_dev_volren_*: the same
-    table and parameters, the same float bits"""
+    table and parameters, the same float bits, and the same sample counts: without skipping all four, with it the
+    samples met (taken + skipped), the rays ended early and the rays that hit (the two skip predicates differ, so the
+    split between taken and skipped may)"""
     from invesalius3_amd import _lib as L
     from invesalius3_amd import volume as V
     from invesalius3_amd import volume_mask as VM
@@ -142,8 +144,8 @@ def test_composite_equals_the_volume_renderer_on_the_same_bytes(ivxlib, name, sh
     ncell = int(np.prod([-(-s // V.CELL) for s in mask.shape]))
     bufs = [DeviceBuffer(mask.size), DeviceBuffer(mask.size * 2), DeviceBuffer(ncell * 2), DeviceBuffer(ncell * 4),
             DeviceBuffer(rgba.nbytes), DeviceBuffer(alpha.nbytes), DeviceBuffer(prefix.nbytes), DeviceBuffer(w * h * 16),
-            DeviceBuffer(w * h * 16)]
-    d8, d16, c8, c16, dt, da, dp, o8, o16 = bufs
+            DeviceBuffer(w * h * 16), DeviceBuffer(32), DeviceBuffer(32)]
+    d8, d16, c8, c16, dt, da, dp, o8, o16, s8, s16 = bufs
     try:
         d8.upload(mask)
         d16.upload(mask.astype(np.uint16))
@@ -152,16 +154,25 @@ def test_composite_equals_the_volume_renderer_on_the_same_bytes(ivxlib, name, sh
         dp.upload(prefix)
         for skip in (0, 1):
             p = V.volren_params(setup, SPACING, skip=bool(skip))
+            s8.zero()
+            s16.zero()
             L.check(lib.ivx_dev_maskren_cells(d8.ptr, shape, dense, 0, 0, ctypes.c_int64(0), ctypes.c_int64(-1), c8.ptr, None))
             L.check(lib.ivx_dev_maskren_render(d8.ptr, c8.ptr, shape, dense, 0, 0, 0, dt.ptr, dp.ptr, ctypes.byref(p), o8.ptr,
-                                               None, None, None), "maskren")
+                                               None, s8.ptr, None), "maskren")
             L.check(lib.ivx_dev_volren_cells(d16.ptr, shape, c16.ptr, None))
-            L.check(lib.ivx_dev_volren_render(d16.ptr, c16.ptr, shape, dt.ptr, da.ptr, dp.ptr, ctypes.byref(p), o16.ptr, None,
-                                              None), "volren")
+            L.check(lib.ivx_dev_volren_render(d16.ptr, c16.ptr, shape, dt.ptr, da.ptr, dp.ptr, ctypes.byref(p), o16.ptr,
+                                              s16.ptr, None), "volren")
             L.synchronize()
             a, b = o8.download((h, w, 4), np.float32), o16.download((h, w, 4), np.float32)
             assert np.array_equal(_bits(a), _bits(b)), "skip %d" % skip
             assert a[..., 3].max() > 0.5
+            n8, n16 = [[int(c) for c in st.download((4,), np.uint64)] for st in (s8, s16)]
+            print("skip %d: samples, skipped, early, rays_hit: mask %s image %s" % (skip, n8, n16))
+            if skip:
+                assert (n8[0] + n8[1], n8[2], n8[3]) == (n16[0] + n16[1], n16[2], n16[3])
+            else:
+                assert n8 == n16 and n8[1] == 0
+            assert n8[0] > 0 and n8[3] > 0
     finally:
         for b in bufs:
             b.close()
