@@ -841,6 +841,22 @@ int ivx_dev_unet3d_forward(const void *net, const float *in, int64_t n, int patc
  * conv1, conv2; decoder: upconv, conv1, conv2 per level; head); n patches must fit the workspace in one batch */
 int ivx_unet3d_layer_times(const void *net, const float *in, int64_t n, int patch, float *out, void *workspace,
                            size_t ws_bytes, void *stream, float *ms /* 27 */);
+/* diagnostic, for the tests: one layer of the network on its own, through the same weight packing and kernels the forward
+ * uses.  Activations are channels-last device arrays (nb, S, S, S, C); w and bias are HOST arrays in torch layout.
+ *   conv_layer: kind 0 = Conv3d(k 5, pad 2), w (cout, c0 + c1, 5, 5, 5), dst (nb, S, S, S, cout); kind 1 =
+ *     ConvTranspose3d(k 4, s 2, p 1), w (c0 + c1, cout, 4, 4, 4), dst (nb, 2S, 2S, 2S, cout).  src1 / c1 are the second
+ *     source of a torch.cat((src0, src1), 1) (NULL / 0 for none; then c0 must be a multiple of 4).  (mt, nt) forces
+ *     the wave's tile shape, 16 mt voxels x 16 nt channels, to one of 1x1, 2x1, 4x1, 8x1, 2x2, 4x2, 4x4; (0, 0) takes the
+ *     forward's own choice.  The shape used comes back in mt_used / nt_used.  IVX_EINVAL, before anything is launched,
+ *     for any other pair and for one the forward never chooses for this cout (nt = 2 needs cout > 16, 4x4 cout > 48,
+ *     8x1 cout <= 16).  Synchronises the stream.
+ *   pool_layer: MaxPool3d(2), (nb, S, S, S, C) -> (nb, S/2, S/2, S/2, C), S even.
+ *   head_layer: Conv3d(8 -> 1, k 1) + sigmoid, in (nvox, 8), w9 = 8 host weights then the bias, out (nvox). */
+int ivx_dev_unet3d_conv_layer(int kind, const float *src0, int c0, const float *src1, int c1, const float *w,
+                              const float *bias, int cout, int S, int nb, int relu, int mt, int nt, float *dst,
+                              int *mt_used, int *nt_used, void *stream);
+int ivx_dev_unet3d_pool_layer(const float *in, float *out, int S, int C, int nb, void *stream);
+int ivx_dev_unet3d_head_layer(const float *in, const float *w9, int64_t nvox, float *out, void *stream);
 int ivx_dev_unet3d_normalize(const int16_t *img, int64_t n, float *out, float *minmax2, void *stream);
 int ivx_segment_cut_count(const int64_t shape[3], int patch, int overlap, int64_t *ncuts);
 int ivx_dev_unet3d_segment(const void *net, const float *vol, const int64_t shape[3], int patch, int overlap, int batch,

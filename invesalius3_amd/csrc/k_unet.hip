@@ -318,20 +318,42 @@ template <int MT, int NT, int KIND> int launch_conv(const ConvArgs &a0, hipStrea
 }
 
 // tile shape per layer: the largest MT x NT that still leaves >= 2048 waves (8 per CU); small layers fall to 1 x 1
-template <int KIND> int run_conv(const ConvArgs &a, hipStream_t st) {
-    const int ntiles = (int)cdiv(a.cout, 16);
-    const int64_t mcount = (int64_t)a.nvox * (KIND == 1 ? 8 : 1);
-    auto waves = [&](int mt, int nt) { return cdiv(mcount, 16 * mt) * cdiv(ntiles, nt); };
-    if (ntiles >= 4 && waves(4, 4) >= 2048) return launch_conv<4, 4, KIND>(a, st);
-    if (ntiles >= 2 && waves(4, 2) >= 2048) return launch_conv<4, 2, KIND>(a, st);
-    if (ntiles == 1 && waves(8, 1) >= 2048) return launch_conv<8, 1, KIND>(a, st);
-    if (ntiles >= 2 && waves(2, 2) >= 2048) return launch_conv<2, 2, KIND>(a, st);
-    if (waves(4, 1) >= 2048) return launch_conv<4, 1, KIND>(a, st);
-    if (waves(2, 1) >= 2048) return launch_conv<2, 1, KIND>(a, st);
-    return launch_conv<1, 1, KIND>(a, st);
+void pick_tile(int kind, int64_t nvox, int cout, int *mt, int *nt) {
+    const int ntiles = (int)cdiv(cout, 16);
+    const int64_t mcount = nvox * (kind == 1 ? 8 : 1);
+    auto waves = [&](int m, int n) { return cdiv(mcount, 16 * m) * cdiv(ntiles, n); };
+    auto set = [&](int m, int n) { *mt = m, *nt = n; };
+    if (ntiles >= 4 && waves(4, 4) >= 2048) return set(4, 4);
+    if (ntiles >= 2 && waves(4, 2) >= 2048) return set(4, 2);
+    if (ntiles == 1 && waves(8, 1) >= 2048) return set(8, 1);
+    if (ntiles >= 2 && waves(2, 2) >= 2048) return set(2, 2);
+    if (waves(4, 1) >= 2048) return set(4, 1);
+    if (waves(2, 1) >= 2048) return set(2, 1);
+    return set(1, 1);
 }
 
-int conv(const Layer &L, const float *s0, int c0, const float *s1, int c1, float *dst, int S, int nb, hipStream_t st) {
+// the seven instantiated tile shapes; any other pair is an error
+template <int KIND> int launch_tile(int mt, int nt, const ConvArgs &a, hipStream_t st) {
+    switch (mt * 10 + nt) {
+    case 11: return launch_conv<1, 1, KIND>(a, st);
+    case 21: return launch_conv<2, 1, KIND>(a, st);
+    case 41: return launch_conv<4, 1, KIND>(a, st);
+    case 81: return launch_conv<8, 1, KIND>(a, st);
+    case 22: return launch_conv<2, 2, KIND>(a, st);
+    case 42: return launch_conv<4, 2, KIND>(a, st);
+    case 44: return launch_conv<4, 4, KIND>(a, st);
+    }
+    ivx::set_error("unet3d: no conv kernel of tile shape %d x %d", mt, nt);
+    return IVX_EINVAL;
+}
+
+template <int KIND> int run_conv(const ConvArgs &a, hipStream_t st) {
+    int mt, nt;
+    pick_tile(KIND, a.nvox, a.cout, &mt, &nt);
+    return launch_tile<KIND>(mt, nt, a, st);
+}
+
+ConvArgs conv_args(const Layer &L, const float *s0, int c0, const float *s1, int c1, float *dst, int S, int nb, int relu) {
     ConvArgs a{};
     a.src0 = s0;
     a.src1 = s1;
@@ -345,13 +367,26 @@ int conv(const Layer &L, const float *s0, int c0, const float *s1, int c1, float
     a.coutpad = L.coutpad;
     a.S = S;
     a.nvox = nb * S * S * S;
-    a.relu = L.kind == 0;
+    a.relu = relu;
+    return a;
+}
+
+int conv(const Layer &L, const float *s0, int c0, const float *s1, int c1, float *dst, int S, int nb, hipStream_t st) {
+    const ConvArgs a = conv_args(L, s0, c0, s1, c1, dst, S, nb, L.kind == 0);
     return L.kind == 0 ? run_conv<0>(a, st) : run_conv<1>(a, st);
 }
 
 int pool(const float *in, float *out, int S, int C, int nb, hipStream_t st) {
     const int64_t total = (int64_t)nb * (S / 2) * (S / 2) * (S / 2) * C;
     hipLaunchKernelGGL(k_pool, dim3(nblk(total)), dim3(256), 0, st, in, out, S, C, total);
+    IVX_LAUNCH_CHECK();
+    return IVX_OK;
+}
+
+int head(const float *w9, const float *in, float *out, int64_t nvox, hipStream_t st) {
+    Head h;
+    memcpy(h.w, w9, sizeof h.w);
+    hipLaunchKernelGGL(k_head, dim3(nblk(nvox)), dim3(256), 0, st, in, out, nvox, h);
     IVX_LAUNCH_CHECK();
     return IVX_OK;
 }
@@ -408,10 +443,7 @@ int forward_batch(const Net &N, const float *in, float *out, int nb, int P, floa
         if ((rc = conv(N.dec[l][1], d, FEAT[l], nullptr, 0, o, S, nb, st)) || (rc = rec(tm, st))) return rc;
         std::swap(d, o);
     }
-    Head h;
-    memcpy(h.w, N.head, sizeof h.w);
-    hipLaunchKernelGGL(k_head, dim3(nblk(P3 * nb)), dim3(256), 0, st, (const float *)d, out, P3 * nb, h);
-    IVX_LAUNCH_CHECK();
+    if ((rc = head(N.head, d, out, P3 * nb, st))) return rc;
     return rec(tm, st);
 }
 
@@ -429,6 +461,45 @@ void axis_starts(int n, int P, int ov, std::vector<int> &s) {
 
 int check_patch(int P) {
     IVX_REQUIRE(P >= 16 && P % 16 == 0 && P <= 512, IVX_EDOM, "unet3d: patch size %d is not a positive multiple of 16 (<= 512)", P);
+    return IVX_OK;
+}
+
+void free_layer(Layer &L) {
+    if (L.w) (void)hipFree(L.w);
+    if (L.b) (void)hipFree(L.b);
+    L.w = L.b = nullptr;
+}
+
+// one layer's host parameters in torch layout (w, then b) -> the device layouts of `Layer`
+int pack_layer(Layer &L, const float *p, const float *bias, int cin, int cout, int kind) {
+    L.cin = cin;
+    L.cinpad = (int)cdiv(cin, 4) * 4;
+    L.cout = cout;
+    L.coutpad = (int)cdiv(cout, 16) * 16;
+    L.kind = kind;
+    const int taps = kind == 0 ? 125 : 64;
+    std::vector<float> w((size_t)taps * L.cinpad * L.coutpad, 0.f), b(L.coutpad, 0.f);
+    if (kind == 0) { // torch (cout, cin, 5, 5, 5) -> [tap][cin][cout]
+        for (int co = 0; co < cout; co++)
+            for (int c = 0; c < cin; c++)
+                for (int t = 0; t < 125; t++) w[((size_t)t * L.cinpad + c) * L.coutpad + co] = p[((size_t)co * cin + c) * 125 + t];
+    } else { // torch (cin, cout, 4, 4, 4) -> [class][tap][cin][cout]; kernel index k = (1 - p) + 2 b per axis
+        for (int c = 0; c < cin; c++)
+            for (int co = 0; co < cout; co++)
+                for (int cls = 0; cls < 8; cls++)
+                    for (int tap = 0; tap < 8; tap++) {
+                        const int kz = (1 - ((cls >> 2) & 1)) + 2 * ((tap >> 2) & 1);
+                        const int ky = (1 - ((cls >> 1) & 1)) + 2 * ((tap >> 1) & 1);
+                        const int kx = (1 - (cls & 1)) + 2 * (tap & 1);
+                        w[(((size_t)cls * 8 + tap) * L.cinpad + c) * L.coutpad + co] =
+                            p[((size_t)c * cout + co) * 64 + (kz * 4 + ky) * 4 + kx];
+                    }
+    }
+    for (int co = 0; co < cout; co++) b[co] = bias[co];
+    IVX_HIP(hipMalloc(&L.w, w.size() * 4));
+    IVX_HIP(hipMalloc(&L.b, b.size() * 4));
+    IVX_HIP(hipMemcpy(L.w, w.data(), w.size() * 4, hipMemcpyHostToDevice));
+    IVX_HIP(hipMemcpy(L.b, b.data(), b.size() * 4, hipMemcpyHostToDevice));
     return IVX_OK;
 }
 
@@ -459,14 +530,9 @@ extern "C" int ivx_unet3d_param_count(int64_t *nfloats) {
 extern "C" int ivx_unet3d_free(void *net) {
     Net *N = (Net *)net;
     if (!N) return IVX_OK;
-    auto rel = [](Layer &L) {
-        if (L.w) (void)hipFree(L.w);
-        if (L.b) (void)hipFree(L.b);
-        L.w = L.b = nullptr;
-    };
-    for (auto &e : N->enc) rel(e[0]), rel(e[1]);
-    for (auto &u : N->up) rel(u);
-    for (auto &e : N->dec) rel(e[0]), rel(e[1]);
+    for (auto &e : N->enc) free_layer(e[0]), free_layer(e[1]);
+    for (auto &u : N->up) free_layer(u);
+    for (auto &e : N->dec) free_layer(e[0]), free_layer(e[1]);
     delete N;
     return IVX_OK;
 }
@@ -481,37 +547,9 @@ extern "C" int ivx_unet3d_load(const float *blob, int64_t nfloats, void **net_ou
     const float *p = blob;
     int rc = IVX_OK;
     auto put = [&](Layer &L, int cin, int cout, int kind) -> int {
-        L.cin = cin;
-        L.cinpad = (int)cdiv(cin, 4) * 4;
-        L.cout = cout;
-        L.coutpad = (int)cdiv(cout, 16) * 16;
-        L.kind = kind;
-        const int taps = kind == 0 ? 125 : 64;
-        std::vector<float> w((size_t)taps * L.cinpad * L.coutpad, 0.f), b(L.coutpad, 0.f);
-        if (kind == 0) { // torch (cout, cin, 5, 5, 5) -> [tap][cin][cout]
-            for (int co = 0; co < cout; co++)
-                for (int c = 0; c < cin; c++)
-                    for (int t = 0; t < 125; t++) w[((size_t)t * L.cinpad + c) * L.coutpad + co] = p[((size_t)co * cin + c) * 125 + t];
-        } else { // torch (cin, cout, 4, 4, 4) -> [class][tap][cin][cout]; kernel index k = (1 - p) + 2 b per axis
-            for (int c = 0; c < cin; c++)
-                for (int co = 0; co < cout; co++)
-                    for (int cls = 0; cls < 8; cls++)
-                        for (int tap = 0; tap < 8; tap++) {
-                            const int kz = (1 - ((cls >> 2) & 1)) + 2 * ((tap >> 2) & 1);
-                            const int ky = (1 - ((cls >> 1) & 1)) + 2 * ((tap >> 1) & 1);
-                            const int kx = (1 - (cls & 1)) + 2 * (tap & 1);
-                            w[(((size_t)cls * 8 + tap) * L.cinpad + c) * L.coutpad + co] =
-                                p[((size_t)c * cout + co) * 64 + (kz * 4 + ky) * 4 + kx];
-                        }
-        }
-        p += (size_t)cout * cin * (kind == 0 ? 125 : 64);
-        for (int co = 0; co < cout; co++) b[co] = p[co];
-        p += cout;
-        IVX_HIP(hipMalloc(&L.w, w.size() * 4));
-        IVX_HIP(hipMalloc(&L.b, b.size() * 4));
-        IVX_HIP(hipMemcpy(L.w, w.data(), w.size() * 4, hipMemcpyHostToDevice));
-        IVX_HIP(hipMemcpy(L.b, b.data(), b.size() * 4, hipMemcpyHostToDevice));
-        return IVX_OK;
+        const float *w = p;
+        p += (size_t)cout * cin * (kind == 0 ? 125 : 64) + cout;
+        return pack_layer(L, w, p - cout, cin, cout, kind);
     };
     int ci = 1;
     for (int l = 0; l < 5 && !rc; l++) {
@@ -717,4 +755,62 @@ extern "C" int ivx_segment_unet3d(const void *net, const int16_t *img, const int
         return rc;
     IVX_HIP(hipDeviceSynchronize());
     return copy_d2h(prob, d_prob, (size_t)n * 4);
+}
+
+/* ------------------------------------------------------------------- diagnostic: one layer at a time (tests) */
+
+// one conv (kind 0) or transposed conv (kind 1) through pack_layer and k_conv; (mt, nt) forces the tile shape,
+// (0, 0) leaves it to pick_tile.  Every refusal comes before the first device call.
+extern "C" int ivx_dev_unet3d_conv_layer(int kind, const float *src0, int c0, const float *src1, int c1, const float *w,
+                                         const float *bias, int cout, int S, int nb, int relu, int mt, int nt, float *dst,
+                                         int *mt_used, int *nt_used, void *stream) {
+    IVX_REQUIRE(src0 && w && bias && dst && mt_used && nt_used, IVX_EINVAL, "unet3d layer: null argument");
+    IVX_REQUIRE(kind == 0 || kind == 1, IVX_EINVAL, "unet3d layer: kind %d is neither 0 (conv) nor 1 (transposed conv)", kind);
+    IVX_REQUIRE(c0 >= 1 && c1 >= 0 && (c1 > 0) == (src1 != nullptr), IVX_EINVAL,
+                "unet3d layer: %d + %d input channels do not match the sources given", c0, c1);
+    IVX_REQUIRE(c1 == 0 || c0 % 4 == 0, IVX_EINVAL,
+                "unet3d layer: with a second source the first must have a multiple of 4 channels, got %d", c0);
+    IVX_REQUIRE(cout >= 1 && S >= 1 && nb >= 1, IVX_EINVAL, "unet3d layer: cout %d, edge %d, %d patches", cout, S, nb);
+    const int cin = c0 + c1;
+    const int64_t nvox = (int64_t)nb * S * S * S;
+    IVX_REQUIRE(nvox * (kind == 1 ? 8 : 1) * std::max(cin, cout) <= INT32_MAX, IVX_EDOM,
+                "unet3d layer: voxel * channel indices must fit int");
+    if (mt || nt) {
+        const int shape = mt * 10 + nt;
+        IVX_REQUIRE(mt >= 1 && nt >= 1 && nt <= 4 && (shape == 11 || shape == 21 || shape == 41 || shape == 81 || shape == 22 ||
+                                                     shape == 42 || shape == 44),
+                    IVX_EINVAL, "unet3d layer: no conv kernel of tile shape %d x %d", mt, nt);
+        // what pick_tile can choose: NT columns need NT column tiles, 8 x 1 is for a single column tile
+        IVX_REQUIRE((nt == 1 || cout > 16 * (nt - 1)) && (mt != 8 || cout <= 16), IVX_EINVAL,
+                    "unet3d layer: tile shape %d x %d is never used for %d output channels", mt, nt, cout);
+    } else {
+        pick_tile(kind, nvox, cout, &mt, &nt);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    Layer L{};
+    int rc = pack_layer(L, w, bias, cin, cout, kind);
+    if (!rc) {
+        const ConvArgs a = conv_args(L, src0, c0, src1, c1, dst, S, nb, relu ? 1 : 0);
+        rc = kind == 0 ? launch_tile<0>(mt, nt, a, st) : launch_tile<1>(mt, nt, a, st);
+    }
+    if (!rc && hipStreamSynchronize(st) != hipSuccess) { // the weights are freed below
+        ivx::set_error("unet3d layer: the kernel failed");
+        rc = IVX_EHIP;
+    }
+    free_layer(L);
+    if (!rc) *mt_used = mt, *nt_used = nt;
+    return rc;
+}
+
+extern "C" int ivx_dev_unet3d_pool_layer(const float *in, float *out, int S, int C, int nb, void *stream) {
+    IVX_REQUIRE(in && out, IVX_EINVAL, "unet3d layer: null argument");
+    IVX_REQUIRE(S >= 2 && S % 2 == 0 && C >= 1 && nb >= 1, IVX_EINVAL, "unet3d layer: pool of edge %d, %d channels, %d patches",
+                S, C, nb);
+    return pool(in, out, S, C, nb, (hipStream_t)stream);
+}
+
+extern "C" int ivx_dev_unet3d_head_layer(const float *in, const float *w9, int64_t nvox, float *out, void *stream) {
+    IVX_REQUIRE(in && w9 && out, IVX_EINVAL, "unet3d layer: null argument");
+    IVX_REQUIRE(nvox >= 1, IVX_EINVAL, "unet3d layer: head over %lld voxels", (long long)nvox);
+    return head(w9, in, out, nvox, (hipStream_t)stream);
 }

@@ -345,6 +345,83 @@ class Unet3D:
             pass
 
 
+# -- one layer at a time (diagnostic: the tests compare each kernel with a float64 reference) ------------------------
+def _run_layer(inputs, out_shape, call):
+    """upload `inputs` (None stays None), run call(*device pointers, dst pointer), download float32 `out_shape`"""
+    from .device import DeviceBuffer
+
+    L.require_device()
+    out_bytes = int(np.prod(out_shape)) * 4
+    bufs = [None if a is None else DeviceBuffer(a.nbytes) for a in inputs] + [DeviceBuffer(out_bytes)]
+    try:
+        for b, a in zip(bufs, inputs):
+            if b is not None:
+                b.upload(a)
+        bufs[-1].zero()
+        call(*[None if b is None else b.ptr for b in bufs])
+        L.synchronize()
+        return bufs[-1].download(out_shape, np.float32)
+    finally:
+        for b in bufs:
+            if b is not None:
+                b.close()
+
+
+def conv_layer(kind: int, x0: np.ndarray, w: np.ndarray, b: np.ndarray, x1: np.ndarray | None = None, relu: bool = False,
+               tile=(0, 0)):
+    """ivx_dev_unet3d_conv_layer: kind 0 = Conv3d(k 5, pad 2) with w (cout, cin, 5, 5, 5), kind 1 = ConvTranspose3d(k 4,
+    s 2, p 1) with w (cin, cout, 4, 4, 4), on channels-last x0 (nb, S, S, S, c0) [and x1, torch.cat((x0, x1), channel)]
+    -> (channels-last float32 output, (mt, nt) the kernel ran with).  `tile` forces that shape; (0, 0) is the forward's
+    own choice."""
+    x0 = np.ascontiguousarray(x0, dtype=np.float32)
+    x1 = None if x1 is None else np.ascontiguousarray(x1, dtype=np.float32)
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    b = np.ascontiguousarray(b, dtype=np.float32)
+    if x0.ndim != 5 or not (x0.shape[1] == x0.shape[2] == x0.shape[3]) or (x1 is not None and x1.shape[:4] != x0.shape[:4]):
+        raise ValueError("activations must be channels-last (nb, S, S, S, C), both sources of one shape but for C")
+    nb, S, c0 = x0.shape[0], x0.shape[1], x0.shape[4]
+    c1 = 0 if x1 is None else x1.shape[4]
+    cout = w.shape[0] if kind == 0 else w.shape[1]
+    if w.shape != ((cout, c0 + c1, 5, 5, 5) if kind == 0 else (c0 + c1, cout, 4, 4, 4)) or b.shape != (cout,):
+        raise ValueError("weights %s / bias %s do not fit kind %d with %d input channels" % (w.shape, b.shape, kind, c0 + c1))
+    T = S if kind == 0 else 2 * S
+    used = (ctypes.c_int(0), ctypes.c_int(0))
+
+    def call(d0, d1, dst):
+        L.check(L.lib().ivx_dev_unet3d_conv_layer(int(kind), d0, int(c0), d1, int(c1), L.ptr(w), L.ptr(b), int(cout), int(S),
+                                                  int(nb), int(bool(relu)), int(tile[0]), int(tile[1]), dst,
+                                                  ctypes.byref(used[0]), ctypes.byref(used[1]), None), "unet3d_conv_layer")
+
+    out = _run_layer([x0, x1], (nb, T, T, T, cout), call)
+    return out, (used[0].value, used[1].value)
+
+
+def pool_layer(x: np.ndarray) -> np.ndarray:
+    """ivx_dev_unet3d_pool_layer: MaxPool3d(2) on channels-last (nb, S, S, S, C) -> (nb, S/2, S/2, S/2, C)"""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 5 or not (x.shape[1] == x.shape[2] == x.shape[3]):
+        raise ValueError("activations must be channels-last (nb, S, S, S, C)")
+    nb, S, C = x.shape[0], x.shape[1], x.shape[4]
+
+    def call(din, dst):
+        L.check(L.lib().ivx_dev_unet3d_pool_layer(din, dst, int(S), int(C), int(nb), None), "unet3d_pool_layer")
+
+    return _run_layer([x], (nb, S // 2, S // 2, S // 2, C), call)
+
+
+def head_layer(x: np.ndarray, w: np.ndarray, b: float) -> np.ndarray:
+    """ivx_dev_unet3d_head_layer: sigmoid(x @ w + b) on (nvox, 8) activations -> (nvox,) float32 probabilities"""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 2 or x.shape[1] != 8 or np.size(w) != 8:
+        raise ValueError("the head takes (nvox, 8) activations and 8 weights")
+    w9 = np.ascontiguousarray(np.concatenate([np.ravel(w), [b]]), dtype=np.float32)
+
+    def call(din, dst):
+        L.check(L.lib().ivx_dev_unet3d_head_layer(din, L.ptr(w9), ctypes.c_int64(x.shape[0]), dst, None), "unet3d_head_layer")
+
+    return _run_layer([x], (x.shape[0],), call)
+
+
 def segment_unet3d(image: np.ndarray, weights, overlap: int = 50, patch_size: int = SIZE, apply_wwwl: bool = False,
                    window_width=255, window_level=127, probability_array: np.ndarray | None = None, comm_array=None,
                    batch: int = DEFAULT_BATCH) -> np.ndarray:

@@ -150,3 +150,61 @@ def host_pipeline(net, image, patch_size, overlap, apply_wwwl=False, ww=255, wl=
     patches = np.stack([p.copy() for _, p, _ in gen_patches(nrm, patch_size, overlap)])
     outs = net.forward(patches)
     return accumulate(nrm, patch_size, overlap, outs), nrm
+
+
+# -- one layer at a time (tests/test_gpu_unet_layers.py, test_gpu_segment.py) ----------------------------------------
+TILES = [(1, 1), (2, 1), (4, 1), (8, 1), (2, 2), (4, 2), (4, 4)]  # the instantiated k_conv<MT, NT, *>
+
+
+def allowed_tiles(cout):
+    """the shapes run_conv can choose for `cout`: NT column tiles need that many, 8 x 1 is for a single column tile"""
+    return [(mt, nt) for mt, nt in TILES if (nt == 1 or cout > 16 * (nt - 1)) and (mt != 8 or cout <= 16)]
+
+
+def pick_tile(kind, nvox, cout):
+    """run_conv's rule: the largest shape that still leaves 2048 waves"""
+    ntiles = -(-cout // 16)
+    m = nvox * (8 if kind == 1 else 1)
+    waves = lambda mt, nt: -(-m // (16 * mt)) * -(-ntiles // nt)  # noqa: E731
+    if ntiles >= 4 and waves(4, 4) >= 2048:
+        return 4, 4
+    if ntiles >= 2 and waves(4, 2) >= 2048:
+        return 4, 2
+    if ntiles == 1 and waves(8, 1) >= 2048:
+        return 8, 1
+    if ntiles >= 2 and waves(2, 2) >= 2048:
+        return 2, 2
+    if waves(4, 1) >= 2048:
+        return 4, 1
+    if waves(2, 1) >= 2048:
+        return 2, 1
+    return 1, 1
+
+
+def to_cl(x):
+    """(C, S, S, S) -> channels-last (S, S, S, C)"""
+    return np.ascontiguousarray(np.moveaxis(x, 0, -1))
+
+
+def from_cl(x):
+    return np.ascontiguousarray(np.moveaxis(x, -1, 0))
+
+
+def ref_layer(kind, x_cl, w, b):
+    """the layer per patch in float64 on channels-last (nb, S, S, S, cin) -> (nb, T, T, T, cout)"""
+    f = _conv5 if kind == 0 else _upconv
+    w, b = np.asarray(w, np.float64), np.asarray(b, np.float64)
+    return np.stack([to_cl(f(from_cl(p.astype(np.float64)), w, b)) for p in x_cl])
+
+
+def int_case(kind, c0, c1, cout, S, nb, seed):
+    """integer-valued float32 data, like post-ReLU activations: x in {0..7} with about a quarter zeros, w in
+    {-3..3} without 0, b in [-50, 50]"""
+    rng = np.random.default_rng(seed)
+    cin = c0 + c1
+    x = rng.integers(1, 8, (nb, S, S, S, cin)).astype(np.float32)
+    x[rng.random(x.shape) < 0.25] = 0
+    wshape = (cout, cin, 5, 5, 5) if kind == 0 else (cin, cout, 4, 4, 4)
+    w = (rng.integers(1, 4, wshape) * rng.choice([-1, 1], wshape)).astype(np.float32)
+    b = rng.integers(-50, 51, cout).astype(np.float32)
+    return x, w, b

@@ -52,6 +52,54 @@ def test_forward_patch_count_off_the_batch_tile(net, sd):
     assert np.array_equal(got, net.forward(x, batch=37))
 
 
+@pytest.fixture(scope="module")
+def sixteen(net, sd):
+    """16 distinct 16^3 patches, their forward in one batch of 16, and its distance from float64"""
+    x = _patches(16, 16, 900)
+    small = net.forward(x, batch=16)
+    err = max(float(np.abs(small[i].astype(np.float64) - R.forward64(sd, x[i])).max()) for i in range(16))
+    for a in (x, small):
+        a.setflags(write=False)
+    return x, small, err
+
+
+@pytest.mark.parametrize("n", [1024, 2048])
+def test_forward_in_one_large_batch_equals_small_batches(net, sixteen, n):
+    """One batch of 1024 (2048) patches makes run_conv take the 2 x 2 (4 x 2) tiles for the 32-channel layers, which no
+    smaller batch of 16^3 patches does; a patch's output is its own whatever the batch and the tile shape."""
+    x, small, err = sixteen
+    print("16 patches: max |dp| = %.3g" % err)
+    assert err <= BOUND
+    try:
+        got = net.forward(np.tile(x, (n // 16, 1, 1, 1)), batch=n)
+    except MemoryError:
+        if n == 2048:  # a workspace of 0.9 GB
+            pytest.skip("no room for the workspace of 2048 patches")
+        raise
+    assert np.array_equal(got.view(np.uint32), np.tile(small, (n // 16, 1, 1, 1)).view(np.uint32))
+
+
+@pytest.mark.parametrize("n,tile", [(1024, (2, 2)), (2048, (4, 2))])
+def test_run_conv_takes_the_big_tiles_for_the_32_channel_layers(ivxlib, n, tile):
+    """The 32-channel layers of a 16^3 patch (edge 4) in one batch of n, each through the layer entry point with the
+    forward's own choice of tile: if the rule is retuned this says that the test above lost its coverage.  Integer data:
+    the first two and the last patch are compared exactly with float64."""
+    from invesalius3_amd import segment as sg
+    #        kind, c0, c1, edge of the input
+    layers = [(0, 16, 0, 4), (0, 32, 0, 4), (1, 64, 0, 2), (0, 32, 32, 4)]  # enc3 conv1, 32 -> 32 convs, upconv3, dec3 conv1
+    for kind, c0, c1, S in layers:
+        assert R.pick_tile(kind, n * S ** 3, 32) == tile
+        x, w, b = R.int_case(kind, c0, c1, 32, S, 16, [kind, c0, c1])
+        x = np.tile(x, (n // 16, 1, 1, 1, 1))
+        x[-1] = x[-1, ::-1]  # the last patch is like no other
+        got, used = sg.conv_layer(kind, x[..., :c0], w, b, x[..., c0:] if c1 else None, relu=kind == 0)
+        assert used == tile, (kind, c0, c1, used)
+        sel = [0, 1, n - 1]
+        want = R.ref_layer(kind, x[sel], w, b)
+        assert np.array_equal(got[sel], (np.maximum(want, 0) if kind == 0 else want).astype(np.float32)), (kind, c0, c1)
+        assert np.array_equal(got[16:32], got[:16])
+
+
 @pytest.mark.parametrize("shape,P,overlap,batch", [((24, 40, 45), 32, 50, 32), ((24, 40, 45), 32, 50, 1),
                                                    ((20, 37, 30), 16, 25, 3), ((33, 18, 40), 16, 0, 5),
                                                    ((10, 12, 9), 16, 50, 2)])
