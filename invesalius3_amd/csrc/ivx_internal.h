@@ -91,6 +91,15 @@ int ccl_small_components(const ivx_flood_plan *p, const uint64_t *cand, uint64_t
                          const void *scratch_key, hipStream_t st);
 bool ccl_supported(uint32_t strct_bits);
 int ccl_run(const ivx_flood_plan *p, const uint64_t *cand, uint64_t *reached, const void *scratch_key, hipStream_t st);
+// tile-frontier flood (k_flood.hip) of the bits already in `reached` (their tiles marked dirty in `scratch`) to the
+// fix-point; what `planes` holds and which neighbourhood the flood follows:
+enum FloodMode {
+    FLOOD_SYMMETRIC, // the candidate plane; the plan's structuring element (what ivx_dev_flood_run does)
+    FLOOD_DIRECTED,  // the six edge planes of ivx_dev_flood_edges_auto: 6-neighbour steps allowed per SOURCE voxel
+    FLOOD_LINEAR,    // the three arc planes of a cost level and scipy's linear-index neighbourhood (k_costlevels.hip)
+};
+int flood_run(const ivx_flood_plan *p, const uint64_t *planes, FloodMode mode, uint64_t *reached, void *scratch, int *rounds,
+              void *stream);
 
 // GPU -> host mailbox in pinned, host-coherent memory: a 1-thread kernel copies up to 32 dwords and then stores a
 // sequence number; the host spins on the sequence word instead of paying a stream synchronisation round trip

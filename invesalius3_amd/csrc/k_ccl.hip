@@ -9,7 +9,7 @@
 // latency each); union-find has no such chain -- every phase is one flat pass over the 16 MiB bit plane:
 //   nodes      maximal runs of 1-bits inside each 64-bit word (a run that continues into the next word is two
 //              nodes, joined by an ordinary union) -> no cross-word scanning anywhere
-//   k_ccl_count / scan   runs per word -> node ids (wordbase + rank of the run's first bit)
+//   k_ccl_count / scan   (scan_u32.h) runs per word -> node ids (wordbase + rank of the run's first bit)
 //   k_ccl_union          one lane per word; each run is united with the runs it touches in the rows that PRECEDE it
 //                        in raster order ((z-1, y-1..y+1), (z, y-1)) and with the run ending at bit 63 of the previous
 //                        word; lock-free union by atomicMin on the larger root (stale parent reads only cost retries)
@@ -23,7 +23,7 @@
 #include <map>
 #include <mutex>
 
-#include "ivx_internal.h"
+#include "scan_u32.h"
 
 namespace {
 
@@ -54,70 +54,6 @@ __global__ __launch_bounds__(256) void k_ccl_count(const unsigned long long *__r
         cnt[i] = (uint32_t)__popcll(run_starts(cand[i]));
 }
 
-// ---- exclusive scan of u32 (in place), three passes, 4096 elements per workgroup -------------------------------------
-constexpr int SCAN_ITEMS = 16;
-__global__ __launch_bounds__(256) void k_scan_block(uint32_t *__restrict__ data, int64_t n, uint32_t *__restrict__ bsum) {
-    __shared__ uint32_t s_wave[4];
-    const int64_t base = ((int64_t)blockIdx.x * 256 + threadIdx.x) * SCAN_ITEMS;
-    uint32_t v[SCAN_ITEMS], sum = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; k++) {
-        v[k] = base + k < n ? data[base + k] : 0u;
-        sum += v[k];
-    }
-    uint32_t inc = sum;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) s_wave[wv] = inc;
-    __syncthreads();
-    uint32_t off = inc - sum;
-    for (int q = 0; q < wv; q++) off += s_wave[q];
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; k++) {
-        if (base + k < n) data[base + k] = off;
-        off += v[k];
-    }
-    if (threadIdx.x == 255) bsum[blockIdx.x] = off;
-}
-__global__ __launch_bounds__(1024) void k_scan_sums(uint32_t *__restrict__ bsum, int64_t nb, uint32_t *__restrict__ total) {
-    __shared__ uint32_t s_wave[16];
-    __shared__ uint32_t s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int64_t b0 = 0; b0 < nb; b0 += 1024) {
-        const int64_t i = b0 + threadIdx.x;
-        const uint32_t v = i < nb ? bsum[i] : 0u;
-        uint32_t inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t t = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += t;
-        }
-        if (lane == 63) s_wave[wv] = inc;
-        __syncthreads();
-        uint32_t wb = 0;
-        for (int q = 0; q < wv; q++) wb += s_wave[q];
-        const uint32_t carry = s_carry;
-        if (i < nb) bsum[i] = carry + wb + inc - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = carry + wb + inc;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = s_carry;
-}
-__global__ __launch_bounds__(256) void k_scan_add(uint32_t *__restrict__ data, int64_t n, const uint32_t *__restrict__ bsum) {
-    const uint32_t add = bsum[blockIdx.x];
-    const int64_t base = ((int64_t)blockIdx.x * 256 + threadIdx.x) * SCAN_ITEMS;
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; k++)
-        if (base + k < n) data[base + k] += add;
-}
-
 __global__ __launch_bounds__(256) void k_ccl_init(uint32_t *__restrict__ parent, uint8_t *__restrict__ flag, uint32_t nruns) {
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nruns; i += stride) {
@@ -127,23 +63,12 @@ __global__ __launch_bounds__(256) void k_ccl_init(uint32_t *__restrict__ parent,
 }
 
 // ---- union-find ------------------------------------------------------------------------------------------------------
-// parent[x] <= x always and only ever decreases, and every value ever stored in parent[x] is a member of x's set.
-// So plain (cacheable, possibly stale) loads are safe: a stale parent is a former ancestor, the walk still descends
-// and terminates, and the only place that needs the truth -- "is a still a root?" -- is decided by the atomicMin.
-// Path halving with plain stores is safe for the same reason (it only ever writes an ancestor).
 // parent[x] <= x always, parent values only ever decrease, and every value ever stored in parent[x] is a member of
 // x's set.  So plain (cacheable, possibly stale) loads are safe in find: a stale parent is a former ancestor, the
 // walk still descends and terminates, and the only step that needs the truth -- "is a still a root?" -- is decided
 // by the atomicMin in uf_union.  (Plain STORES into parent[] during the union are NOT safe -- measured: lost links.)
 __device__ __forceinline__ uint32_t uf_find(const uint32_t *parent, uint32_t x) {
     for (;;) { // no compression here: halving through atomicMin was measured slower (0.96 vs 0.86 ms at 512^3)
-        const uint32_t p = parent[x];
-        if (p == x) return x;
-        x = p;
-    }
-}
-__device__ __forceinline__ uint32_t uf_find_ro(const uint32_t *parent, uint32_t x) {
-    for (;;) {
         const uint32_t p = parent[x];
         if (p == x) return x;
         x = p;
@@ -160,7 +85,6 @@ __device__ __forceinline__ void uf_union(uint32_t *parent, uint32_t a, uint32_t 
         a = old;              // somebody re-parented a meanwhile: unite its new parent with b
     }
 }
-
 
 // ---- tile-local components in LDS ------------------------------------------------------------------------------------
 // One workgroup per 64(x) x 16(y) x 16(z) tile (one word wide, lane = word), exactly the flood tile.  The runs of the
@@ -345,7 +269,7 @@ __global__ __launch_bounds__(256) void k_ccl_union(const unsigned long long *__r
 
 __global__ __launch_bounds__(256) void k_ccl_flatten(uint32_t *parent, uint32_t nruns) {
     const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nruns; i += stride) parent[i] = uf_find_ro(parent, i);
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nruns; i += stride) parent[i] = uf_find(parent, i);
 }
 
 __global__ __launch_bounds__(256) void k_ccl_activate(const unsigned long long *__restrict__ cand,
@@ -490,7 +414,7 @@ static int ccl_prepare(const ivx_flood_plan *p, const uint64_t *cand, const void
         if (g_tab_owner[st] != scratch_key) state = CclState(); // another flood on this stream rebuilt the tables meanwhile
         g_tab_owner[st] = scratch_key;
     }
-    const int64_t nsb = cdiv(g.nwords, 256 * SCAN_ITEMS);
+    const int64_t nsb = scan_u32_blocks(g.nwords);
     void *d_wbase, *d_tab;
     int rc;
     if ((rc = ws_get_s(WS_CCL0, st, (size_t)g.nwords * 4 + (size_t)nsb * 4 + 64, &d_wbase))) return rc;
@@ -501,12 +425,7 @@ static int ccl_prepare(const ivx_flood_plan *p, const uint64_t *cand, const void
     if (!state.built) {
         hipLaunchKernelGGL(k_ccl_count, dim3(grid_for(g.nwords)), dim3(256), 0, st, c, g.nwords, wbase);
         IVX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_scan_block, dim3((unsigned)nsb), dim3(256), 0, st, wbase, g.nwords, bsum);
-        IVX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, st, bsum, nsb, d_total);
-        IVX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_scan_add, dim3((unsigned)nsb), dim3(256), 0, st, wbase, g.nwords, bsum);
-        IVX_LAUNCH_CHECK();
+        if ((rc = scan_u32_exclusive(wbase, g.nwords, bsum, d_total, st))) return rc;
         uint32_t seq, tot = 0;
         if ((rc = mailbox_publish(d_total, 1, st, &seq))) return rc;
         if ((rc = mailbox_wait(seq, st, &tot, 1))) return rc;

@@ -30,20 +30,18 @@
 //                       union-find engine (k_ccl.hip) takes over.
 //   k_flood_coarse      before the rounds: tiles that are ALL candidate are flooded as units on the tile graph (one
 //                       workgroup, rows of tile bits), so the solid interior of a region costs no rounds at all.
-//   k_flood_persistent  the same tile update in ONE launch with a device-side ticket queue (opt-in, measured slower).
 //   k_flood_apply(2)    reached bits -> out[v] = fill (only words with reached bits touch memory).
 #include <math.h>
 #include <map>
 #include <mutex>
 #include <stdlib.h>
 
-#include "ivx_internal.h"
+#include "flood_tiles.h"
 
 typedef short short8_t __attribute__((ext_vector_type(8)));
 
 namespace {
 
-constexpr int TY_LOG = 4, TY = 1 << TY_LOG, TZ = 16; // tile rows / slices (tile is one 64-voxel word wide)
 constexpr int NT = TY * TZ;           // lanes per tile workgroup (one per word)
 constexpr int HY = TY + 2, HZ = TZ + 2;
 constexpr int BATCH = 8;              // most rounds the host may keep queued ahead (the counter ring has 2 * BATCH entries)
@@ -57,84 +55,6 @@ constexpr unsigned int CLOSED = 0x40u;
 // together serialise on one counter at 5 - 10 ns each -- tools/micro/atomic_tail.hip: 1 024 workgroups x 1 append cost 5.5 us
 // more than none, x 4 appends 40 us more, spread over 8 counters 0.3 / 1.3 us -- but the rounds' appends do not arrive
 // together: region growing 0.192 -> 0.195 ms, the IFT cost levels 13.8 -> 14.3 ms.  Dropped.)
-
-struct Tiles {
-    int64_t dz, dy, dx, wx;
-    int64_t nty, ntz, ntiles;
-    uint32_t strct;
-    int itcap; // local iterations per tile visit before the tile re-enlists itself
-    int conn; // 6 / 18 / 26 when strct is exactly scipy's generate_binary_structure(3, 1|2|3), else 0 (generic path)
-};
-
-static int make_tiles(const ivx_flood_plan *p, Tiles *t) {
-    IVX_REQUIRE(p && p->dz >= 0 && p->dy >= 0 && p->dx >= 0, IVX_EINVAL, "flood: bad shape");
-    IVX_REQUIRE(p->wx == ivx::cdiv(p->dx, 64), IVX_EINVAL, "flood: plan.wx must be ceil(dx/64)");
-    t->dz = p->dz; t->dy = p->dy; t->dx = p->dx; t->wx = p->wx;
-    t->nty = ivx::cdiv(p->dy, TY); t->ntz = ivx::cdiv(p->dz, TZ);
-    t->ntiles = t->wx * t->nty * t->ntz;
-    t->strct = p->strct_bits & ~(1u << 13); // the centre never matters
-    {
-        uint32_t m6 = 0, m18 = 0, m26 = 0;
-        for (int k = 0; k < 27; k++) {
-            const int nzc = (k / 9 != 1) + ((k / 3) % 3 != 1) + (k % 3 != 1);
-            if (nzc <= 1) m6 |= 1u << k;
-            if (nzc <= 2) m18 |= 1u << k;
-            m26 |= 1u << k;
-        }
-        const uint32_t sb = p->strct_bits | (1u << 13);
-        t->conn = sb == m26 ? 26 : sb == m18 ? 18 : sb == m6 ? 6 : 0;
-    }
-    if (getenv("IVX_FLOOD_DBG")) t->strct |= 1u << 30;
-    // One tile crossing (TY = TZ = 16 rows) per visit: a tile that is still changing after that re-enlists itself and
-    // carries on in the next round, when its neighbours have already started on what it has published so far -- the
-    // rounds pipeline instead of waiting for the slowest tile's local fix-point (measured 0.240 -> 0.232 ms on the bench
-    // volume; below 16 a straight crossing needs two visits and the round count doubles).
-    static const int itcap = [] {
-        const char *e = getenv("IVX_FLOOD_ITCAP");
-        const int v = e ? atoi(e) : TY + TY / 2; // (round 6: 24 instead of 16 -- 9 rounds instead of 10 on the bench volume, 0.1916 -> 0.1871 ms; 20 .. 64 measure alike)
-        return v < 1 ? 1 : v;
-    }();
-    t->itcap = itcap;
-    IVX_REQUIRE(t->ntiles < 0x7fffffffll, IVX_EINVAL, "flood: too many tiles");
-    return IVX_OK;
-}
-
-// scratch: dirty[2][ntiles] u8 | counter ring | persistent-frontier queue | seed staging | round lists | coarse-pass row words
-constexpr size_t SEED_CHUNK = 4096;
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-struct FScratch {
-    size_t off_dirty0, off_dirty1, off_cnt, off_queue, off_queued, off_seeds, off_status, off_ring, off_list0, off_list1;
-    size_t off_full, off_whole, total;
-    uint32_t qcap;
-};
-// persistent-frontier queue header (device)
-struct Queue { // one 128-B line per hot word: tickets, pushes, in-flight count and the read-mostly done flag
-    unsigned int head, pad0[31];
-    unsigned int tail, pad1[31];
-    unsigned int pending, pad2[31];
-    unsigned int done, abort, visits, pad3[29];
-};
-constexpr unsigned int Q_EMPTY = 0xffffffffu;
-static FScratch make_fscratch(const Tiles &t) {
-    FScratch s;
-    s.off_dirty0 = 0;
-    s.off_dirty1 = al256((size_t)t.ntiles);
-    s.off_cnt = al256(s.off_dirty1 + (size_t)t.ntiles);
-    s.off_queue = al256(s.off_cnt + 64 * 4);
-    s.off_queued = al256(s.off_queue + sizeof(Queue));
-    s.off_seeds = al256(s.off_queued + (size_t)t.ntiles * 4); // everything before off_seeds is zeroed by flood_clear
-    s.off_status = al256(s.off_seeds + SEED_CHUNK * 3 * 8);
-    s.off_ring = al256(s.off_status + 64);
-    uint32_t q = 64;
-    while ((int64_t)q < 2 * t.ntiles + 2048) q <<= 1; // <= ntiles queued + <= 1024 waiting tickets, 2x slack
-    s.qcap = q;
-    s.off_list0 = al256(s.off_ring + (size_t)q * 4);
-    s.off_list1 = al256(s.off_list0 + (size_t)t.ntiles * 4);
-    s.off_full = al256(s.off_list1 + (size_t)t.ntiles * 4); // coarse pass: one word per row of tiles, all-candidate / wholly reached
-    s.off_whole = al256(s.off_full + (size_t)(t.nty * t.ntz) * 8);
-    s.total = al256(s.off_whole + (size_t)(t.nty * t.ntz) * 8);
-    return s;
-}
 
 template <typename T> __device__ __forceinline__ double as_double(T v) { return (double)v; }
 
@@ -212,18 +132,7 @@ __global__ __launch_bounds__(256) void k_flood_candidates(const T *__restrict__ 
     }
 }
 
-// ---- seeds ----------------------------------------------------------------------------------------
-// Bits that enter `reached` from OUTSIDE a tile visit (seeds, a neighbour slab's plane OR-ed into a halo slice) are news
-// nobody has reported: a visit only tells its neighbours about the faces IT changed.  Wake the word's own tile and every
-// tile that can see the word.
-__device__ __forceinline__ void mark_tile_nbhd(const Tiles &t, uint8_t *__restrict__ dirty, int64_t tz, int64_t ty, int64_t tx) {
-    for (int64_t az = tz - 1; az <= tz + 1; az++)
-        for (int64_t ay = ty - 1; ay <= ty + 1; ay++)
-            for (int64_t ax = tx - 1; ax <= tx + 1; ax++)
-                if (az >= 0 && az < t.ntz && ay >= 0 && ay < t.nty && ax >= 0 && ax < t.wx)
-                    dirty[(az * t.nty + ay) * t.wx + ax] = 1;
-}
-
+// ---- seeds (they wake tiles with mark_tile_nbhd, flood_tiles.h) ---------------------------------------------------
 template <typename T>
 __global__ void k_flood_seed(const T *__restrict__ data, Tiles t, double t0, double t1, const int64_t *__restrict__ seeds,
                              int64_t nseeds, unsigned long long *__restrict__ cand,
@@ -269,14 +178,14 @@ __device__ __forceinline__ unsigned long long fill_runs(unsigned long long seed,
     return __brevll(fill_up(__brevll(f), __brevll(m)));
 }
 
-// Tile update shared by the per-round kernel and the persistent frontier.
+// Tile update shared by the per-round kernel and the resident launch.
 // LDS holds, for the 18x18 rows of the tile + halo: sN = the row's word, sD = the row's word dilated by one voxel
 // along x including the carry bits of the x-neighbour words (so a full 3-wide strct row costs ONE LDS read), and the
 // two carry bits themselves (generic structuring elements).  The local fix-point is a chaotic relaxation: reached
 // bits only ever get OR'ed in, so a lane may read a neighbour's word while it is being rewritten -- any mix of old
 // and new bits is a valid intermediate state -- and ONE barrier per iteration (the termination vote) is enough.
 // ATOMIC: stage / publish with agent-scope atomics (needed when other workgroups update neighbours concurrently
-// AND no kernel boundary follows, i.e. in the persistent frontier).
+// AND no kernel boundary orders them, i.e. between the rounds of the resident launch, k_flood_resident).
 __device__ unsigned long long g_dbg[16];
 #define DBG_T(i) if (DBG && threadIdx.x == 0) g_dbg[i] = __builtin_readcyclecounter();
 // workgroup barrier that only waits for this wave's LDS traffic (lgkmcnt), NOT for its global stores/atomics in flight:
@@ -293,6 +202,13 @@ struct TileLds {
     unsigned int open; // some candidate of the tile is still unreached after this visit
     unsigned int vote[2]; // workgroup "anything changed" vote, double-buffered: ONE s_barrier per iteration
 };
+// a visit's direction bits -> L.dirs: OR across the wave in registers, then ONE LDS atomic per wave (256 same-address LDS
+// atomics serialise)
+__device__ __forceinline__ void post_dirs(TileLds &L, unsigned dirs) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) dirs |= __shfl_xor(dirs, o, 64);
+    if ((threadIdx.x & 63) == 0 && dirs) atomicOr(&L.dirs, dirs);
+}
 
 template <bool ATOMIC, int CONN, bool DBG = false>
 __device__ __forceinline__ void tile_update(const Tiles &t, const unsigned long long *__restrict__ cand,
@@ -434,11 +350,86 @@ __device__ __forceinline__ void tile_update(const Tiles &t, const unsigned long 
                 }
         if (exhausted) dirs |= 1u << 13; // iteration cap hit before the local fix-point: revisit this tile
     }
-    // OR across the wave in registers, then ONE LDS atomic per wave (256 same-address LDS atomics serialise)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) dirs |= __shfl_xor(dirs, o, 64);
-    if ((threadIdx.x & 63) == 0 && dirs) atomicOr(&L.dirs, dirs);
+    post_dirs(L, dirs);
     if (__any((c & ~r) != 0ull) && (threadIdx.x & 63) == 0) L.open = 1u;
+}
+
+// the structuring element's gather is a compile-time pattern for the three standard structures (see tile_update)
+template <bool ATOMIC>
+__device__ __forceinline__ void tile_update_conn(const Tiles &t, const unsigned long long *__restrict__ cand,
+                                                 unsigned long long *reached, int64_t tile, TileLds &L) {
+    if (t.conn == 26) tile_update<ATOMIC, 26>(t, cand, reached, tile, L);
+    else if (t.conn == 18) tile_update<ATOMIC, 18>(t, cand, reached, tile, L);
+    else if (t.conn == 6) tile_update<ATOMIC, 6>(t, cand, reached, tile, L);
+    else tile_update<ATOMIC, 0>(t, cand, reached, tile, L);
+}
+
+// ---- tile hand-off: what a visit leaves for the next round ------------------------------------------------------------
+#define AT_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define AT_STORE(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+// Mark tile nt in the next round's byte flags (four tiles per word: the atomicOr goes to the byte's word); whoever marks
+// a byte first appends the tile to the next round's list.  MARK / SEEN: the bit set and the bits that mean "somebody was
+// here before" (the coarse pass enlists with a bit of its own, see ENLISTED).  ATOMIC: the list entry is an agent-scope
+// store (the resident launch reads it without a kernel boundary in between).
+template <bool ATOMIC, unsigned int MARK = 1u, unsigned int SEEN = 0xffu>
+__device__ __forceinline__ void enlist_tile(uint8_t *dirty_next, unsigned int *list_next, unsigned int *n_next, int64_t nt) {
+    unsigned int *wp = (unsigned int *)(dirty_next + (nt & ~(int64_t)3));
+    const unsigned int sh = 8 * (unsigned int)(nt & 3);
+    const unsigned int old = atomicOr(wp, MARK << sh);
+    if (!((old >> sh) & SEEN)) {
+        unsigned int *slot = &list_next[atomicAdd(n_next, 1u)];
+        if (ATOMIC) AT_STORE(slot, (unsigned int)nt);
+        else *slot = (unsigned int)nt;
+    }
+}
+// After the tile update (L.dirs and L.open complete): a tile with no candidate left is closed for good, so nobody needs to
+// enlist it again (see CLOSED), and lane d < 27 wakes the neighbour tile in direction d when the visit changed a face that
+// tile can see (bit 13 = the tile itself: the iteration cap ended the visit).
+template <bool ATOMIC>
+__device__ __forceinline__ void publish_tile(const Tiles &t, int64_t tile, const TileLds &L, uint8_t *dirty_cur,
+                                             uint8_t *dirty_next, unsigned int *list_next, unsigned int *n_next) {
+    const int64_t txi = tile % t.wx, r1 = tile / t.wx;
+    const int64_t tyi = r1 % t.nty, tzi = r1 / t.nty;
+    if (threadIdx.x == 32 && !L.open) {
+        const unsigned int bit = CLOSED << (8 * (unsigned int)(tile & 3));
+        atomicOr((unsigned int *)(dirty_cur + (tile & ~(int64_t)3)), bit);
+        atomicOr((unsigned int *)(dirty_next + (tile & ~(int64_t)3)), bit);
+    }
+    if (threadIdx.x < 27 && (L.dirs >> threadIdx.x & 1u)) {
+        const int d = threadIdx.x;
+        const int64_t nz = tzi + d / 9 - 1, ny = tyi + (d / 3) % 3 - 1, nx = txi + d % 3 - 1;
+        if (nz >= 0 && nz < t.ntz && ny >= 0 && ny < t.nty && nx >= 0 && nx < t.wx)
+            enlist_tile<ATOMIC>(dirty_next, list_next, n_next, (nz * t.nty + ny) * t.wx + nx);
+    }
+}
+
+// ---- arc-plane relaxation, shared by the directed and the linear-index tile update ------------------------------------
+// Lane = word `me` of the staged rows.  e_ym / e_yp / e_zm / e_zp: the arcs arriving from the four row neighbours; exp /
+// bexm: the arcs along +x inside the word and, bit-reversed, along -x; carry: what the x-neighbour words hand in (constant
+// during a visit).  Same votes as tile_update.  Returns true when the iteration cap ended the loop before the local fix-point.
+__device__ __forceinline__ bool relax_arcs(int itcap, TileLds &L, int me, bool inside, unsigned long long exp,
+                                           unsigned long long bexm, unsigned long long e_ym, unsigned long long e_yp,
+                                           unsigned long long e_zm, unsigned long long e_zp, unsigned long long carry,
+                                           unsigned long long &r) {
+    for (int it = 0; it < itcap; it++) {
+        unsigned long long nr = r | carry | (L.sN[me - 1] & e_ym) | (L.sN[me + 1] & e_yp) | (L.sN[me - HY] & e_zm) |
+                                (L.sN[me + HY] & e_zp);
+        nr |= (exp + (nr & exp)) ^ exp;
+        unsigned long long rn = __brevll(nr);
+        rn |= (bexm + (rn & bexm)) ^ bexm;
+        nr = __brevll(rn);
+        if (!inside) nr = 0ull;
+        const bool ch = nr != r;
+        if (ch) {
+            r = nr;
+            L.sN[me] = r;
+        }
+        if (__any(ch) && (threadIdx.x & 63) == 0) L.vote[it & 1] = 1u;
+        if (threadIdx.x == 0) L.vote[(it + 1) & 1] = 0u;
+        __syncthreads();
+        if (!L.vote[it & 1]) return false;
+    }
+    return true;
 }
 
 // ---- directed tile update (floodfill_auto_threshold) -------------------------------------------------------------
@@ -484,28 +475,7 @@ __device__ __forceinline__ void tile_update_dir(const Tiles &t, const unsigned l
     const int me = (tz + 1) * HY + (ty + 1);
     const unsigned long long r_in = L.sN[me];
     unsigned long long r = r_in;
-    bool exhausted = true;
-    for (int it = 0; it < t.itcap; it++) {
-        unsigned long long nr = r | carry | (L.sN[me - 1] & e_ym) | (L.sN[me + 1] & e_yp) | (L.sN[me - HY] & e_zm) |
-                                (L.sN[me + HY] & e_zp);
-        nr |= (exp + (nr & exp)) ^ exp;
-        unsigned long long rn = __brevll(nr);
-        rn |= (bexm + (rn & bexm)) ^ bexm;
-        nr = __brevll(rn);
-        if (!inside) nr = 0ull;
-        const bool ch = nr != r;
-        if (ch) {
-            r = nr;
-            L.sN[me] = r;
-        }
-        if (__any(ch) && (threadIdx.x & 63) == 0) L.vote[it & 1] = 1u;
-        if (threadIdx.x == 0) L.vote[(it + 1) & 1] = 0u;
-        __syncthreads();
-        if (!L.vote[it & 1]) {
-            exhausted = false;
-            break;
-        }
-    }
+    const bool exhausted = relax_arcs(t.itcap, L, me, inside, exp, bexm, e_ym, e_yp, e_zm, e_zp, carry, r);
     const unsigned long long chg = r ^ r_in;
     unsigned dirs = 0;
     if (chg) {
@@ -521,9 +491,7 @@ __device__ __forceinline__ void tile_update_dir(const Tiles &t, const unsigned l
         if (xhi) dirs |= 1u << 14;
         if (exhausted) dirs |= 1u << 13;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) dirs |= __shfl_xor(dirs, o, 64);
-    if ((threadIdx.x & 63) == 0 && dirs) atomicOr(&L.dirs, dirs);
+    post_dirs(L, dirs);
     if (threadIdx.x == 0) L.open = 1u; // (edge planes: no candidate plane to be exhausted)
 }
 
@@ -542,10 +510,7 @@ __device__ __forceinline__ bool lin_enlist(const Tiles &t, int64_t word, int64_t
     const int64_t row = word / t.wx, txi = word - row * t.wx, z = row / t.dy, y = row - z * t.dy;
     const int64_t nt = ((z / TZ) * t.nty + (y >> TY_LOG)) * t.wx + txi;
     if (nt == self) return true;
-    unsigned int *wp = (unsigned int *)(dirty_next + (nt & ~(int64_t)3));
-    const unsigned int sh = 8 * (unsigned int)(nt & 3);
-    const unsigned int old = atomicOr(wp, 1u << sh);
-    if (!((old >> sh) & 0xffu)) list_next[atomicAdd(n_next, 1u)] = (unsigned int)nt;
+    enlist_tile<false>(dirty_next, list_next, n_next, nt);
     return false;
 }
 
@@ -595,28 +560,7 @@ __device__ __forceinline__ void tile_update_lin(const Tiles &t, const unsigned l
     const int me = (tz + 1) * HY + (ty + 1);
     const unsigned long long r_in = L.sN[me];
     unsigned long long r = r_in;
-    bool exhausted = true;
-    for (int it = 0; it < t.itcap; it++) {
-        unsigned long long nr = r | carry | (L.sN[me - 1] & e_ym) | (L.sN[me + 1] & e_yp) | (L.sN[me - HY] & e_zm) |
-                                (L.sN[me + HY] & e_zp);
-        nr |= (exp + (nr & exp)) ^ exp;
-        unsigned long long rn = __brevll(nr);
-        rn |= (bexm + (rn & bexm)) ^ bexm;
-        nr = __brevll(rn);
-        if (!inside) nr = 0ull;
-        const bool ch = nr != r;
-        if (ch) {
-            r = nr;
-            L.sN[me] = r;
-        }
-        if (__any(ch) && (threadIdx.x & 63) == 0) L.vote[it & 1] = 1u;
-        if (threadIdx.x == 0) L.vote[(it + 1) & 1] = 0u;
-        __syncthreads();
-        if (!L.vote[it & 1]) {
-            exhausted = false;
-            break;
-        }
-    }
+    const bool exhausted = relax_arcs(t.itcap, L, me, inside, exp, bexm, e_ym, e_yp, e_zm, e_zp, carry, r);
     const unsigned long long chg = r ^ r_in;
     unsigned dirs = 0;
     if (chg) {
@@ -649,9 +593,7 @@ __device__ __forceinline__ void tile_update_lin(const Tiles &t, const unsigned l
         }
         if (exhausted) dirs |= 1u << 13;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) dirs |= __shfl_xor(dirs, o, 64);
-    if ((threadIdx.x & 63) == 0 && dirs) atomicOr(&L.dirs, dirs);
+    post_dirs(L, dirs);
     if (threadIdx.x == 0) L.open = 1u; // (arc planes change from level to level: a tile is never closed for good)
 }
 
@@ -677,7 +619,7 @@ __global__ void k_flood_build_list(Tiles t, const uint8_t *__restrict__ dirty, u
 // last round that had any work.  The host polls word 0, keeps a few rounds queued ahead of the newest one it has seen
 // start, and stops when a round starts with an empty list.
 // MODE 0: candidate plane; 1 (directed): `cand` holds the six edge planes of k_flood_edges_auto instead; 2 (linear): the
-// three arc planes of k_wsa_edges and scipy's linear-index neighbourhood (tile_update_lin)
+// three arc planes of k_wsa_planes (k_costlevels.hip) and scipy's linear-index neighbourhood (tile_update_lin)
 template <int MODE>
 __global__ __launch_bounds__(NT, 6) void k_flood_round_list(Tiles t, const unsigned long long *__restrict__ cand,
                                                              unsigned long long *reached, const unsigned int *__restrict__ list_cur,
@@ -710,37 +652,14 @@ __global__ __launch_bounds__(NT, 6) void k_flood_round_list(Tiles t, const unsig
         if (MODE == 2) tile_update_lin(t, cand, reached, tile, L, dirty_next, list_next, n_next);
         else if (MODE == 1) tile_update_dir(t, cand, reached, tile, L);
         else if (dbg) tile_update<false, 26, true>(t, cand, reached, tile, L);
-        else if (t.conn == 26) tile_update<false, 26>(t, cand, reached, tile, L);
-        else if (t.conn == 18) tile_update<false, 18>(t, cand, reached, tile, L);
-        else if (t.conn == 6) tile_update<false, 6>(t, cand, reached, tile, L);
-        else tile_update<false, 0>(t, cand, reached, tile, L);
+        else tile_update_conn<false>(t, cand, reached, tile, L);
         lds_barrier(); // L.dirs complete; the publish stores keep flying (the kernel boundary orders them for the next round)
         if (dbg && threadIdx.x == 0) g_dbg[3] = __builtin_readcyclecounter();
-        const int64_t txi = tile % t.wx, r1 = tile / t.wx;
-        const int64_t tyi = r1 % t.nty, tzi = r1 / t.nty;
-        if (threadIdx.x == 32 && !L.open) { // closed for good: nobody needs to enlist this tile again (see CLOSED)
-            const unsigned int bit = CLOSED << (8 * (unsigned int)(tile & 3));
-            atomicOr((unsigned int *)(dirty_cur + (tile & ~(int64_t)3)), bit);
-            atomicOr((unsigned int *)(dirty_next + (tile & ~(int64_t)3)), bit);
-        }
-        if (threadIdx.x < 27 && (L.dirs >> threadIdx.x & 1u)) {
-            const int d = threadIdx.x;
-            const int64_t nz = tzi + d / 9 - 1, ny = tyi + (d / 3) % 3 - 1, nx = txi + d % 3 - 1;
-            if (nz >= 0 && nz < t.ntz && ny >= 0 && ny < t.nty && nx >= 0 && nx < t.wx) {
-                const int64_t nt = (nz * t.nty + ny) * t.wx + nx;
-                unsigned int *wp = (unsigned int *)(dirty_next + (nt & ~(int64_t)3));
-                const unsigned int sh = 8 * (unsigned int)(nt & 3);
-                const unsigned int old = atomicOr(wp, 1u << sh);
-                if (!((old >> sh) & 0xffu)) list_next[atomicAdd(n_next, 1u)] = (unsigned int)nt; // first mark: enlist
-            }
-        }
+        publish_tile<false>(t, tile, L, dirty_cur, dirty_next, list_next, n_next);
         if (dbg && threadIdx.x == 0) g_dbg[4] = __builtin_readcyclecounter();
         __syncthreads(); // L is reused by the next list entry of this workgroup
     }
 }
-
-#define AT_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define AT_STORE(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 
 // ---- resident rounds: the same rounds, ONE launch ------------------------------------------------------------------
 // A launch per round costs ~5 us of dispatch whether the round has 1 500 tiles or none, the host has to see a round start
@@ -764,7 +683,7 @@ struct ResCtl {
     unsigned int rounds; // rounds that had work
     unsigned int visits; // (statistics) tile visits
 };
-constexpr int RES_CTL_AT = 32; // dword index of ResCtl inside the counter block (cleared together with the ring)
+constexpr int RES_CTL_AT = 32; // dword index of ResCtl inside the counter block (cleared together with the counter ring)
 __global__ __launch_bounds__(NT, 6) void k_flood_resident(Tiles t, const unsigned long long *__restrict__ cand,
                                                            unsigned long long *reached, unsigned int *list0,
                                                            unsigned int *list1, unsigned int *cnt, uint8_t *dirty0,
@@ -803,29 +722,9 @@ __global__ __launch_bounds__(NT, 6) void k_flood_resident(Tiles t, const unsigne
                 L.open = 0;
             }
             __syncthreads();
-            if (t.conn == 26) tile_update<true, 26>(t, cand, reached, tile, L);
-            else if (t.conn == 18) tile_update<true, 18>(t, cand, reached, tile, L);
-            else if (t.conn == 6) tile_update<true, 6>(t, cand, reached, tile, L);
-            else tile_update<true, 0>(t, cand, reached, tile, L);
+            tile_update_conn<true>(t, cand, reached, tile, L);
             lds_barrier(); // L.dirs complete; the publishing atomics keep flying until the round's barrier
-            const int64_t txi = tile % t.wx, r1 = tile / t.wx;
-            const int64_t tyi = r1 % t.nty, tzi = r1 / t.nty;
-            if (threadIdx.x == 32 && !L.open) { // closed for good (see CLOSED)
-                const unsigned int bit = CLOSED << (8 * (unsigned int)(tile & 3));
-                atomicOr((unsigned int *)(dirty_cur + (tile & ~(int64_t)3)), bit);
-                atomicOr((unsigned int *)(dirty_next + (tile & ~(int64_t)3)), bit);
-            }
-            if (threadIdx.x < 27 && (L.dirs >> threadIdx.x & 1u)) {
-                const int d = threadIdx.x;
-                const int64_t nz = tzi + d / 9 - 1, ny = tyi + (d / 3) % 3 - 1, nx = txi + d % 3 - 1;
-                if (nz >= 0 && nz < t.ntz && ny >= 0 && ny < t.nty && nx >= 0 && nx < t.wx) {
-                    const int64_t nt = (nz * t.nty + ny) * t.wx + nx;
-                    unsigned int *wp = (unsigned int *)(dirty_next + (nt & ~(int64_t)3));
-                    const unsigned int sh = 8 * (unsigned int)(nt & 3);
-                    const unsigned int old = atomicOr(wp, 1u << sh);
-                    if (!((old >> sh) & 0xffu)) AT_STORE(&list_next[atomicAdd(n_next, 1u)], (unsigned int)nt);
-                }
-            }
+            publish_tile<true>(t, tile, L, dirty_cur, dirty_next, list_next, n_next);
             __syncthreads(); // L is reused by the next list entry of this workgroup
         }
         // the round's barrier: min(n, grid) workgroups had work and sign; everybody waits for all of them
@@ -856,92 +755,6 @@ __global__ __launch_bounds__(NT, 6) void k_flood_resident(Tiles t, const unsigne
         if (gate) AT_STORE(gate, gate_val); // whatever happened, the gate is open when the flood is over
         __hip_atomic_store(&line[0], ((unsigned long long)tag << 56) | ((unsigned long long)status << 48) | round, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
-
-// ---- persistent tile frontier: ONE launch, device-side work queue ---------------------------------------
-// Same tile update as k_flood_round_list, but workgroups pull dirty tiles from a ring buffer and push the neighbour
-// tiles whose halo they changed, until nothing is queued or in flight (`pending` == 0).  Cross-workgroup traffic
-// (reached words, queue words, flags) uses 4/8-byte agent-scope atomics on both sides (the placement-independent
-// form of the CDNA4 guide, G16): words are published with atomicOr (monotone, so two workgroups that happen to
-// own the same tile concurrently can never lose bits), drained with s_waitcnt vmcnt(0) before the push.
-// No co-residency is needed: a workgroup only ever waits for work while some OTHER running workgroup holds a tile.
-
-__global__ void k_flood_enqueue(Tiles t, uint8_t *dirty, Queue *q, unsigned int *queued, unsigned int *ring,
-                                unsigned int qmask) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= t.ntiles || !(dirty[i] & 1u)) return;
-    dirty[i] = 0;
-    if (atomicExch(&queued[i], 1u) == 0u) {
-        atomicAdd(&q->pending, 1u);
-        const unsigned int slot = atomicAdd(&q->tail, 1u);
-        AT_STORE(&ring[slot & qmask], (unsigned int)i);
-    }
-}
-
-__global__ __launch_bounds__(NT) void k_flood_persistent(Tiles t, const unsigned long long *__restrict__ cand,
-                                                          unsigned long long *reached, Queue *q, unsigned int *queued,
-                                                          unsigned int *ring, unsigned int qmask, unsigned int max_spins) {
-    __shared__ TileLds L;
-    __shared__ int s_tile;
-    unsigned int my_visits = 0;
-    // nothing was enqueued (the counter is final: the enqueue kernel has completed): nobody would ever set `done`
-    if (blockIdx.x == 0 && threadIdx.x == 0 && AT_LOAD(&q->pending) == 0u) AT_STORE(&q->done, 1u);
-    for (;;) {
-        if (threadIdx.x == 0) {
-            int tile = -1;
-            if (!AT_LOAD(&q->done) && !AT_LOAD(&q->abort)) {
-                // take a ticket: the h-th pop gets the h-th push; then poll ONLY our own ring slot (no hot word)
-                const unsigned int h = atomicAdd(&q->head, 1u);
-                unsigned int *slot = &ring[h & qmask];
-                for (unsigned int spins = 0;; spins++) {
-                    const unsigned int v = AT_LOAD(slot);
-                    if (v != Q_EMPTY) {
-                        AT_STORE(slot, Q_EMPTY);
-                        tile = (int)v;
-                        break;
-                    }
-                    if ((spins & 7u) == 7u && (AT_LOAD(&q->done) || AT_LOAD(&q->abort))) break;
-                    if (spins > max_spins) { AT_STORE(&q->abort, 1u); break; } // bounded: never hang the device
-                    if (spins < 64u) __builtin_amdgcn_s_sleep(2);
-                    else __builtin_amdgcn_s_sleep(32);
-                }
-            }
-            if (tile >= 0 && ++my_visits > max_spins) { AT_STORE(&q->abort, 2u); tile = -1; }
-            if (tile >= 0) atomicExch(&queued[tile], 0u); // cleared BEFORE staging: later changes re-queue the tile
-            s_tile = tile;
-            L.dirs = 0;
-            L.open = 0;
-        }
-        __syncthreads();
-        const int tile = s_tile;
-        if (tile < 0) return;
-        if (t.conn == 26) tile_update<true, 26>(t, cand, reached, tile, L);
-        else if (t.conn == 18) tile_update<true, 18>(t, cand, reached, tile, L);
-        else if (t.conn == 6) tile_update<true, 6>(t, cand, reached, tile, L);
-        else tile_update<true, 0>(t, cand, reached, tile, L);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // every publishing wave drains before the pushes
-        __syncthreads();
-        const int64_t txi = tile % t.wx, r1 = tile / t.wx;
-        const int64_t tyi = r1 % t.nty, tzi = r1 / t.nty;
-        if (threadIdx.x < 27 && (L.dirs >> threadIdx.x & 1u)) {
-            const int d = threadIdx.x;
-            const int64_t nz = tzi + d / 9 - 1, ny = tyi + (d / 3) % 3 - 1, nx = txi + d % 3 - 1;
-            if (nz >= 0 && nz < t.ntz && ny >= 0 && ny < t.nty && nx >= 0 && nx < t.wx) {
-                const int64_t nt = (nz * t.nty + ny) * t.wx + nx;
-                if (atomicExch(&queued[nt], 1u) == 0u) {
-                    atomicAdd(&q->pending, 1u); // counted before it becomes poppable
-                    const unsigned int slot = atomicAdd(&q->tail, 1u);
-                    AT_STORE(&ring[slot & qmask], (unsigned int)nt);
-                }
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads(); // all pushes (and their pending increments) have landed before this tile is retired
-        if (threadIdx.x == 0) {
-            atomicAdd(&q->visits, 1u);
-            if (atomicSub(&q->pending, 1u) == 1u) AT_STORE(&q->done, 1u); // nothing queued, nothing in flight
-        }
     }
 }
 
@@ -1162,14 +975,7 @@ __global__ __launch_bounds__(CT) void k_flood_coarse(Tiles t, Blocks bk, const u
 
 // reached = cand for the wholly reached blocks; the tiles around them that are not wholly reached themselves (and the
 // seeded tiles that are not whole) go straight onto the round-0 list: a dirty byte is enlisted by whoever sets its
-// ENLISTED bit first.
-__device__ __forceinline__ void coarse_enlist(uint8_t *dirty, int64_t tile, unsigned int *list, unsigned int *count) {
-    unsigned int *wp = (unsigned int *)(dirty + (tile & ~(int64_t)3));
-    const unsigned int sh = 8 * (unsigned int)(tile & 3);
-    const unsigned int old = atomicOr(wp, ENLISTED << sh);
-    if (!(old & ((ENLISTED | CLOSED) << sh))) list[atomicAdd(count, 1u)] = (unsigned int)tile;
-}
-
+// ENLISTED bit first (enlist_tile with that bit; a CLOSED byte counts as taken).
 // FRESH: every word of the plane is written (whole blocks: their candidates; the accepted seeds' bits; zero elsewhere), so
 // the plane needs no clearing pass before the flood
 template <bool FRESH>
@@ -1202,7 +1008,7 @@ __global__ __launch_bounds__(256) void k_flood_block_apply(Tiles t, Blocks bk, c
             // OR-ed into a halo slice): even when those bits already fill the tile, nobody has told its neighbours yet
             s_chg[threadIdx.x] = 1u;
         } else {
-            coarse_enlist(dirty, tile0 + threadIdx.x, list, count);
+            enlist_tile<false, ENLISTED, ENLISTED | CLOSED>(dirty, list, count, tile0 + threadIdx.x);
         }
     }
     if (!FRESH && !whole) return; // uniform
@@ -1251,7 +1057,7 @@ __global__ __launch_bounds__(256) void k_flood_block_apply(Tiles t, Blocks bk, c
         if (nz < 0 || nz >= t.ntz || ny < 0 || ny >= t.nty || nx < 0 || nx >= t.wx) continue;
         const unsigned int ex = block_exist(t, bk, nx);
         if (((unsigned int)(rowW[nz * t.nty + ny] >> (bk.q * nx)) & ex) == ex) continue; // wholly reached: nothing to gain
-        coarse_enlist(dirty, (nz * t.nty + ny) * t.wx + nx, list, count);
+        enlist_tile<false, ENLISTED, ENLISTED | CLOSED>(dirty, list, count, (nz * t.nty + ny) * t.wx + nx);
     }
 }
 
@@ -1559,15 +1365,14 @@ extern "C" int ivx_dev_flood_seed(const ivx_flood_plan *p, int dtype, const void
     return IVX_OK;
 }
 
-// one launch instead of three memsets: reached plane = 0, scratch head (dirty flags, counters, queue) = 0, ring = EMPTY
+// one launch instead of two memsets: reached plane = 0, scratch head (dirty flags, counters) = 0
 __global__ __launch_bounds__(256) void k_flood_clear(uint4 *__restrict__ reached, int64_t n16, uint4 *__restrict__ head,
-                                                     int64_t h16, uint4 *__restrict__ ring, int64_t r16) {
+                                                     int64_t h16) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const uint4 z = make_uint4(0u, 0u, 0u, 0u), e = make_uint4(~0u, ~0u, ~0u, ~0u);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16 + h16 + r16; i += stride) {
+    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16 + h16; i += stride) {
         if (i < n16) reached[i] = z;
-        else if (i < n16 + h16) head[i - n16] = z;
-        else ring[i - n16 - h16] = e;
+        else head[i - n16] = z;
     }
 }
 
@@ -1576,20 +1381,16 @@ extern "C" int ivx_dev_flood_clear(const ivx_flood_plan *p, uint64_t *reached, v
     int rc = make_tiles(p, &t);
     if (rc) return rc;
     const FScratch s = make_fscratch(t);
-    const size_t nb = (size_t)(t.dz * t.dy * t.wx) * 8, rb = (size_t)s.qcap * 4;
-    if ((nb | s.off_seeds | rb | (uintptr_t)reached | (uintptr_t)scratch | s.off_ring) & 15) { // odd sizes: plain memsets
+    const size_t nb = (size_t)(t.dz * t.dy * t.wx) * 8;
+    if ((nb | s.off_seeds | (uintptr_t)reached | (uintptr_t)scratch) & 15) { // odd sizes: plain memsets
         IVX_HIP(hipMemsetAsync(reached, 0, nb, ivx::S(stream)));
         IVX_HIP(hipMemsetAsync(scratch, 0, s.off_seeds, ivx::S(stream)));
-        IVX_HIP(hipMemsetAsync((char *)scratch + s.off_ring, 0xff, rb, ivx::S(stream)));
     } else {
-        const int64_t total = (int64_t)((nb + s.off_seeds + rb) / 16);
-        if (total) {
-            const int64_t blocks = ivx::cdiv(total, 256);
-            hipLaunchKernelGGL(k_flood_clear, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, ivx::S(stream),
-                               (uint4 *)reached, (int64_t)(nb / 16), (uint4 *)scratch, (int64_t)(s.off_seeds / 16),
-                               (uint4 *)((char *)scratch + s.off_ring), (int64_t)(rb / 16));
-            IVX_LAUNCH_CHECK();
-        }
+        const int64_t total = (int64_t)((nb + s.off_seeds) / 16);
+        const int64_t blocks = ivx::cdiv(total, 256);
+        hipLaunchKernelGGL(k_flood_clear, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, ivx::S(stream),
+                           (uint4 *)reached, (int64_t)(nb / 16), (uint4 *)scratch, (int64_t)(s.off_seeds / 16));
+        IVX_LAUNCH_CHECK();
     }
     ivx::ccl_invalidate(scratch);
     return IVX_OK;
@@ -1619,8 +1420,9 @@ __global__ void k_gate_set(unsigned int *word, unsigned int value) {
     if (threadIdx.x == 0) __hip_atomic_store(word, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// directed: `cand` = the six edge planes of ivx_dev_flood_edges_auto (rounds engine only: the coarse pass, the
-// union-find escape and the persistent frontier all rely on symmetric adjacency)
+// mode (ivx::FloodMode, ivx_internal.h): FLOOD_DIRECTED -- `cand` = the six edge planes of ivx_dev_flood_edges_auto;
+// FLOOD_LINEAR -- the three arc planes of a cost level (k_costlevels.hip).  Both run on the rounds engine only: the coarse
+// pass and the union-find escape rely on symmetric lattice adjacency.
 // `fresh` (may be NULL): the flood starts from these seeds on a plane whose old contents are dead (ivx_dev_flood_grow) --
 // the coarse pass then does the clearing and the seeding as well
 struct Fresh {
@@ -1629,23 +1431,77 @@ struct Fresh {
     double t0, t1;
     SeedPack sp;
 };
-static int flood_mode() {
-    static const int mode_env = [] {
+// IVX_FLOOD_MODE: "rounds" (default, and what any other value means) = tile frontier, one launch per round, with an escape
+// to the union-find path when a flood needs more than CCL_ESCAPE_ROUNDS rounds (serpentine / maze-like regions); "ccl" =
+// run-based union-find from the start (k_ccl.hip; no frontier, flat cost).  Measured at 512^3 on the bench blob (20
+// rounds): rounds 0.74 ms, ccl 0.86 ms (and 1.4 ms, with 2.7x more tile visits, for a single launch that pulled tiles from a
+// device-side ticket queue: removed).
+static bool flood_mode_ccl() {
+    static const bool ccl = [] {
         const char *e = getenv("IVX_FLOOD_MODE");
-        if (e && !strcmp(e, "ccl")) return 0;
-        if (e && !strcmp(e, "persistent")) return 2;
-        return 1;
+        return e && !strcmp(e, "ccl");
     }();
-    return mode_env;
+    return ccl;
 }
-static bool coarse_ok(const Tiles &t, bool directed) {
+static bool coarse_ok(const Tiles &t, ivx::FloodMode mode) {
     static const bool coarse_on = [] {
         const char *e = getenv("IVX_FLOOD_COARSE");
         return !(e && e[0] == '0');
     }();
     // standard structures only, tile grid small enough for one workgroup's LDS
-    return coarse_on && !directed && t.conn != 0 && t.wx <= 64 && (t.nty + 2) * (t.ntz + 2) <= CROWS_MAX &&
+    return coarse_on && mode == ivx::FLOOD_SYMMETRIC && t.conn != 0 && t.wx <= 64 && (t.nty + 2) * (t.ntz + 2) <= CROWS_MAX &&
            t.nty * t.ntz <= (int64_t)CT * CRP;
+}
+// The coarse pass's three launches (see k_flood_coarse): blocks of 16 / 32 / 64 x 16 x 16 voxels, the finest whose row fits
+// one word.  FRESH: the clearing and the seeding of `f` ride along; otherwise `f` carries no seeds.
+template <bool FRESH>
+static int coarse_pass(const Tiles &t, const FScratch &s, char *scr, const uint64_t *cand, uint64_t *reached, const Fresh &f,
+                       int ncnt, hipStream_t st) {
+    static const int bxs_env = [] {
+        const char *e = getenv("IVX_FLOOD_BLOCK"); // 16 / 32 / 64: force a coarser block (A/B measurements)
+        return e ? atoi(e) : 0;
+    }();
+    Blocks bk;
+    bk.bxs = 16;
+    while (bk.bxs < 64 && ((64 / bk.bxs) * t.wx > 64 || bk.bxs < bxs_env)) bk.bxs *= 2;
+    bk.q = 64 / bk.bxs;
+    uint8_t *dirty0 = (uint8_t *)(scr + s.off_dirty0), *dirty1 = (uint8_t *)(scr + s.off_dirty1);
+    unsigned int *cnt = (unsigned int *)(scr + s.off_cnt), *list0 = (unsigned int *)(scr + s.off_list0);
+    unsigned long long *rowF = (unsigned long long *)(scr + s.off_full), *rowW = (unsigned long long *)(scr + s.off_whole);
+    unsigned int *seed_ok = (unsigned int *)(scr + s.off_status) + 8;
+    const unsigned groups = (unsigned)(t.nty * t.ntz);
+    int ct = 64; // one row of tiles per lane up to 1024 lanes, then up to CRP rows per lane (128..1024 lanes measured equal)
+    while (ct < CT && ct < t.nty * t.ntz) ct *= 2;
+    hipLaunchKernelGGL(k_flood_block_flags<FRESH>, dim3(groups), dim3(256), 0, st, t, bk, (unsigned long long *)cand,
+                       (const unsigned long long *)reached, dirty0, dirty1, rowF, rowW, cnt, ncnt, f.sp, f.dtype, f.data, f.t0,
+                       f.t1, seed_ok);
+    IVX_LAUNCH_CHECK();
+    auto coarse = t.conn == 26 ? k_flood_coarse<26, FRESH> : t.conn == 18 ? k_flood_coarse<18, FRESH> : k_flood_coarse<6, FRESH>;
+    hipLaunchKernelGGL(coarse, dim3(1), dim3(ct), 0, st, t, bk, (const unsigned long long *)rowF, rowW, f.sp,
+                       (const unsigned int *)seed_ok);
+    IVX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_flood_block_apply<FRESH>, dim3(groups), dim3(256), 0, st, t, bk, (const unsigned long long *)cand,
+                       (unsigned long long *)reached, (const unsigned long long *)rowW, dirty0, list0, cnt, f.sp,
+                       (const unsigned int *)seed_ok);
+    IVX_LAUNCH_CHECK();
+    return IVX_OK;
+}
+// Spin on the first word of a pinned progress line until `done(word)`, at most `spins` polls; then take the safe path once:
+// synchronise the stream and look again.  `never`: the error when even that word does not satisfy `done`.
+template <typename Done>
+static int poll_line(volatile unsigned long long *line, long spins, hipStream_t st, Done done, const char *never,
+                     unsigned long long *word) {
+    for (long n = 0; n < spins; n++) {
+        *word = __atomic_load_n((const unsigned long long *)line, __ATOMIC_ACQUIRE);
+        if (done(*word)) return IVX_OK;
+#if defined(__x86_64__)
+        __builtin_ia32_pause();
+#endif
+    }
+    IVX_HIP(hipStreamSynchronize(st));
+    *word = __atomic_load_n((const unsigned long long *)line, __ATOMIC_ACQUIRE);
+    IVX_REQUIRE(done(*word), IVX_EHIP, "%s", never);
+    return IVX_OK;
 }
 // a resident launch (k_flood_resident) whose last word has not been read yet, keyed by the scratch it runs on
 struct ResPending {
@@ -1655,8 +1511,8 @@ struct ResPending {
 };
 static std::map<const void *, ResPending> g_res_pending;
 static std::mutex g_res_mu;
-static int flood_run_impl(const ivx_flood_plan *p, const uint64_t *cand, bool directed, uint64_t *reached, void *scratch_,
-                          int *rounds, void *stream, const Fresh *fresh = nullptr, bool linear = false, int resident = -1);
+static int flood_run_impl(const ivx_flood_plan *p, const uint64_t *cand, ivx::FloodMode mode, uint64_t *reached, void *scratch_,
+                          int *rounds, void *stream, const Fresh *fresh = nullptr, int resident = -1);
 // Wait for the resident launch on `scratch_` (if any) and finish what it left: *late = 1 when `reached` was completed after
 // the launch had ended (round cap -> union-find engine; timed-out barrier -> launches per round), i.e. when work the caller
 // queued behind the launch has seen an incomplete plane and must be queued again.
@@ -1673,46 +1529,32 @@ static int flood_wait_impl(const ivx_flood_plan *p, const uint64_t *cand, uint64
     }
     hipStream_t st = ivx::S(stream);
     unsigned long long v = 0;
-    bool got = false;
-    for (long spins = 0; spins < 40000000L; spins++) {
-        v = __atomic_load_n((const unsigned long long *)rp.line, __ATOMIC_ACQUIRE);
-        if ((uint32_t)(v >> 56) == rp.tag && ((v >> 48) & 0xffull) != 0) { got = true; break; }
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-    }
-    if (!got) {
-        IVX_HIP(hipStreamSynchronize(st));
-        v = __atomic_load_n((const unsigned long long *)rp.line, __ATOMIC_ACQUIRE);
-        IVX_REQUIRE((uint32_t)(v >> 56) == rp.tag && ((v >> 48) & 0xffull) != 0, IVX_EHIP, "flood: the resident launch never reported");
-    }
+    const uint32_t tag = rp.tag;
+    int rc = poll_line(rp.line, 40000000L, st,
+                       [tag](unsigned long long w) { return (uint32_t)(w >> 56) == tag && ((w >> 48) & 0xffull) != 0; },
+                       "flood: the resident launch never reported", &v);
+    if (rc) return rc;
     const unsigned int status = (unsigned int)((v >> 48) & 0xffull);
     int done_rounds = (int)(v & 0xffffffffull);
     static const bool trace = getenv("IVX_FLOOD_TRACE") != nullptr;
     if (trace) fprintf(stderr, "ivx flood: resident launch ended with status %u after %d rounds\n", status, done_rounds);
-    if (status == 2u && rp.ccl_at_cap) { // long, thin region: the union-find engine completes the components reached so far
+    if (status != 1u) {
+        // round cap on a long, thin region: the union-find engine completes the components reached so far; a barrier that
+        // timed out (or a cap without that escape): every tile is marked and launches per round finish the flood
+        const bool to_ccl = status == 2u && rp.ccl_at_cap;
+        if (!to_ccl)
+            fprintf(stderr, "ivx: resident flood launch ended with status %u after %d rounds; finishing with launches per round\n", status,
+                    done_rounds);
         Tiles t;
-        int rc = make_tiles(p, &t);
-        if (rc) return rc;
+        if ((rc = make_tiles(p, &t))) return rc;
         const FScratch s = make_fscratch(t);
         char *scr = (char *)scratch_;
-        IVX_HIP(hipMemsetAsync(scr + s.off_dirty0, 0, (size_t)t.ntiles, st));
+        IVX_HIP(hipMemsetAsync(scr + s.off_dirty0, to_ccl ? 0 : 1, (size_t)t.ntiles, st));
         IVX_HIP(hipMemsetAsync(scr + s.off_dirty1, 0, (size_t)t.ntiles, st));
-        if ((rc = ivx::ccl_run(p, cand, reached, scratch_, st))) return rc;
-        done_rounds += 1;
-        if (late) *late = 1;
-    } else if (status != 1u) { // a barrier timed out (or a cap without an escape): finish with one launch per round
-        fprintf(stderr, "ivx: resident flood launch ended with status %u after %d rounds; finishing with launches per round\n", status,
-                done_rounds);
-        Tiles t;
-        int rc = make_tiles(p, &t);
+        int more = 1;
+        if (to_ccl) rc = ivx::ccl_run(p, cand, reached, scratch_, st);
+        else rc = flood_run_impl(p, cand, ivx::FLOOD_SYMMETRIC, reached, scratch_, &more, stream, nullptr, 0);
         if (rc) return rc;
-        const FScratch s = make_fscratch(t);
-        char *scr = (char *)scratch_;
-        IVX_HIP(hipMemsetAsync(scr + s.off_dirty0, 1, (size_t)t.ntiles, st));
-        IVX_HIP(hipMemsetAsync(scr + s.off_dirty1, 0, (size_t)t.ntiles, st));
-        int more = 0;
-        if ((rc = flood_run_impl(p, cand, false, reached, scratch_, &more, stream, nullptr, false, 0))) return rc;
         done_rounds += more;
         if (late) *late = 1;
     }
@@ -1722,9 +1564,9 @@ static int flood_wait_impl(const ivx_flood_plan *p, const uint64_t *cand, uint64
 // resident: -1 = as IVX_FLOOD_RESIDENT says, returns when the flood is complete; 0 = launches per round; 1 = resident launch
 // allowed AND the call may return right behind it (ivx_dev_flood_grow_async: the caller picks the result up with
 // ivx_dev_flood_wait)
-static int flood_run_impl(const ivx_flood_plan *p, const uint64_t *cand, bool directed, uint64_t *reached, void *scratch_,
-                          int *rounds, void *stream, const Fresh *fresh, bool linear, int resident) {
-    if (linear) directed = true; // (arc planes: no coarse pass, no union-find escape, no persistent frontier)
+static int flood_run_impl(const ivx_flood_plan *p, const uint64_t *cand, ivx::FloodMode mode, uint64_t *reached, void *scratch_,
+                          int *rounds, void *stream, const Fresh *fresh, int resident) {
+    const bool sym = mode == ivx::FLOOD_SYMMETRIC;
     Tiles t;
     int rc = make_tiles(p, &t);
     if (rc) return rc;
@@ -1752,53 +1594,12 @@ static int flood_run_impl(const ivx_flood_plan *p, const uint64_t *cand, bool di
     char *scr = (char *)scratch_;
     uint8_t *dirty[2] = {(uint8_t *)(scr + s.off_dirty0), (uint8_t *)(scr + s.off_dirty1)};
     unsigned int *cnt = (unsigned int *)(scr + s.off_cnt);
-    // IVX_FLOOD_MODE: "rounds" (default) = tile frontier, one launch per round, with an escape to the union-find path
-    // when a flood needs more than CCL_ESCAPE_ROUNDS rounds (serpentine / maze-like regions); "ccl" = run-based
-    // union-find from the start (k_ccl.hip; no frontier, flat cost); "persistent" = tile frontier, single launch +
-    // device queue.  Measured at 512^3 on the bench blob (20 rounds): rounds 0.74 ms, ccl 0.86 ms, persistent 1.4 ms.
-    const int mode = directed ? 1 : flood_mode();
     constexpr int CCL_ESCAPE_ROUNDS = 48;
-    if (mode == 0 && ivx::ccl_supported(p->strct_bits)) {
+    if (sym && flood_mode_ccl() && ivx::ccl_supported(p->strct_bits)) {
         if (rounds) *rounds = 1;
         // the dirty-tile list is not used by this path; keep it empty so a later frontier run starts clean
         IVX_HIP(hipMemsetAsync(dirty[0], 0, (size_t)t.ntiles, st));
         return ivx::ccl_run(p, cand, reached, scratch_, st);
-    }
-    const bool use_rounds = mode != 2;
-    static const unsigned int max_spins = [] {
-        const char *e = getenv("IVX_FLOOD_MAX_SPINS");
-        return e ? (unsigned int)strtoul(e, nullptr, 10) : (1u << 20);
-    }();
-    if (!use_rounds) {
-        Queue *q = (Queue *)(scr + s.off_queue);
-        unsigned int *queued = (unsigned int *)(scr + s.off_queued);
-        unsigned int *ring = (unsigned int *)(scr + s.off_ring);
-        IVX_HIP(hipMemsetAsync(&q->done, 0, 128, st)); // done / abort / visits
-        // tickets of the previous run that were never served must not shift this run's slots
-        IVX_HIP(hipMemsetAsync(&q->head, 0, 256, st)); // head, tail (ring is all-EMPTY between runs)
-        hipLaunchKernelGGL(k_flood_enqueue, dim3((unsigned)ivx::cdiv(t.ntiles, 256)), dim3(256), 0, st, t, dirty[0], q,
-                           queued, ring, s.qcap - 1);
-        IVX_LAUNCH_CHECK();
-        const int64_t grid = t.ntiles < 1024 ? t.ntiles : 1024; // <= 4 workgroups per CU; no residency requirement
-        hipLaunchKernelGGL(k_flood_persistent, dim3((unsigned)grid), dim3(NT), 0, st, t,
-                           (const unsigned long long *)cand, (unsigned long long *)reached, q, queued, ring,
-                           s.qcap - 1, max_spins);
-        IVX_LAUNCH_CHECK();
-        Queue h;
-        IVX_HIP(hipMemcpyAsync(&h, q, sizeof(Queue), hipMemcpyDeviceToHost, st));
-        IVX_HIP(hipStreamSynchronize(st));
-        if (!h.abort && h.pending == 0) {
-            if (rounds) *rounds = (int)h.visits;
-            return IVX_OK;
-        }
-        // The frontier kernel bounds every spin and bails out instead of hanging.  `reached` is monotone, so the
-        // partial result is valid: reset the queue, mark every tile dirty and finish with one launch per round.
-        fprintf(stderr, "ivx: persistent flood frontier aborted (head=%u tail=%u pending=%u abort=%u visits=%u); "
-                        "finishing in rounds mode\n", h.head, h.tail, h.pending, h.abort, h.visits);
-        IVX_HIP(hipMemsetAsync(scr + s.off_queue, 0, s.off_seeds - s.off_queue, st));
-        IVX_HIP(hipMemsetAsync(scr + s.off_ring, 0xff, (size_t)s.qcap * 4, st));
-        IVX_HIP(hipMemsetAsync(dirty[0], 1, (size_t)t.ntiles, st));
-        IVX_HIP(hipMemsetAsync(dirty[1], 0, (size_t)t.ntiles, st));
     }
     int total_rounds = 0;
     unsigned int *list[2] = {(unsigned int *)(scr + s.off_list0), (unsigned int *)(scr + s.off_list1)};
@@ -1814,48 +1615,11 @@ static int flood_run_impl(const ivx_flood_plan *p, const uint64_t *cand, bool di
         const int v = e ? atoi(e) : 3;
         return v < 1 ? 1 : (v > BATCH ? BATCH : v);
     }();
-    // coarse pass (see k_flood_coarse): blocks of 16 / 32 / 64 x 16 x 16 voxels, the finest whose row fits one word
-    if (coarse_ok(t, directed)) {
-        static const int bxs_env = [] {
-            const char *e = getenv("IVX_FLOOD_BLOCK"); // 16 / 32 / 64: force a coarser block (A/B measurements)
-            return e ? atoi(e) : 0;
-        }();
-        Blocks bk;
-        bk.bxs = 16;
-        while (bk.bxs < 64 && ((64 / bk.bxs) * t.wx > 64 || bk.bxs < bxs_env)) bk.bxs *= 2;
-        bk.q = 64 / bk.bxs;
-        unsigned long long *rowF = (unsigned long long *)(scr + s.off_full), *rowW = (unsigned long long *)(scr + s.off_whole);
-        unsigned int *seed_ok = (unsigned int *)(scr + s.off_status) + 8;
-        const unsigned groups = (unsigned)(t.nty * t.ntz);
-        SeedPack none;
-        none.n = 0;
-        int ct = 64; // one row of tiles per lane up to 1024 lanes, then up to CRP rows per lane (128..1024 lanes measured equal)
-        while (ct < CT && ct < t.nty * t.ntz) ct *= 2;
-        if (fresh) {
-            hipLaunchKernelGGL(k_flood_block_flags<true>, dim3(groups), dim3(256), 0, st, t, bk, (unsigned long long *)cand,
-                               (const unsigned long long *)reached, dirty[0], dirty[1], rowF, rowW, cnt, RES_CTL_AT + 4, fresh->sp,
-                               fresh->dtype, fresh->data, fresh->t0, fresh->t1, seed_ok);
-            IVX_LAUNCH_CHECK();
-            if (t.conn == 26) hipLaunchKernelGGL((k_flood_coarse<26, true>), dim3(1), dim3(ct), 0, st, t, bk, rowF, rowW, fresh->sp, seed_ok);
-            else if (t.conn == 18) hipLaunchKernelGGL((k_flood_coarse<18, true>), dim3(1), dim3(ct), 0, st, t, bk, rowF, rowW, fresh->sp, seed_ok);
-            else hipLaunchKernelGGL((k_flood_coarse<6, true>), dim3(1), dim3(ct), 0, st, t, bk, rowF, rowW, fresh->sp, seed_ok);
-            IVX_LAUNCH_CHECK();
-            hipLaunchKernelGGL(k_flood_block_apply<true>, dim3(groups), dim3(256), 0, st, t, bk, (const unsigned long long *)cand,
-                               (unsigned long long *)reached, rowW, dirty[0], list[0], cnt, fresh->sp, seed_ok);
-            IVX_LAUNCH_CHECK();
-        } else {
-            hipLaunchKernelGGL(k_flood_block_flags<false>, dim3(groups), dim3(256), 0, st, t, bk, (unsigned long long *)cand,
-                               (const unsigned long long *)reached, dirty[0], dirty[1], rowF, rowW, cnt, RES_CTL_AT + 4, none, 0,
-                               (const void *)nullptr, 0.0, 0.0, seed_ok);
-            IVX_LAUNCH_CHECK();
-            if (t.conn == 26) hipLaunchKernelGGL((k_flood_coarse<26, false>), dim3(1), dim3(ct), 0, st, t, bk, rowF, rowW, none, seed_ok);
-            else if (t.conn == 18) hipLaunchKernelGGL((k_flood_coarse<18, false>), dim3(1), dim3(ct), 0, st, t, bk, rowF, rowW, none, seed_ok);
-            else hipLaunchKernelGGL((k_flood_coarse<6, false>), dim3(1), dim3(ct), 0, st, t, bk, rowF, rowW, none, seed_ok);
-            IVX_LAUNCH_CHECK();
-            hipLaunchKernelGGL(k_flood_block_apply<false>, dim3(groups), dim3(256), 0, st, t, bk, (const unsigned long long *)cand,
-                               (unsigned long long *)reached, rowW, dirty[0], list[0], cnt, none, seed_ok);
-            IVX_LAUNCH_CHECK();
-        }
+    if (coarse_ok(t, mode)) {
+        static const Fresh no_seeds = {0, nullptr, 0.0, 0.0, {{}, 0}};
+        rc = fresh ? coarse_pass<true>(t, s, scr, cand, reached, *fresh, RES_CTL_AT + 4, st)
+                   : coarse_pass<false>(t, s, scr, cand, reached, no_seeds, RES_CTL_AT + 4, st);
+        if (rc) return rc;
     } else {
         IVX_REQUIRE(!fresh, IVX_EINVAL, "flood: the fused start needs the coarse pass");
         IVX_HIP(hipMemsetAsync(cnt, 0, (RES_CTL_AT + 4) * 4, st));
@@ -1870,7 +1634,11 @@ static int flood_run_impl(const ivx_flood_plan *p, const uint64_t *cand, bool di
         const char *e = getenv("IVX_FLOOD_RESIDENT");
         return e && e[0] == '1';
     }();
-    if (!directed && resident != 0 && resident_env) {
+    if (sym && resident != 0 && resident_env) {
+        static const unsigned int max_spins = [] {
+            const char *e = getenv("IVX_FLOOD_MAX_SPINS");
+            return e ? (unsigned int)strtoul(e, nullptr, 10) : (1u << 20);
+        }();
         static int res_per_cu = 0, ncu = 0;
         if (!ncu) {
             int dev = 0, occ = 0, n = 0;
@@ -1908,22 +1676,15 @@ static int flood_run_impl(const ivx_flood_plan *p, const uint64_t *cand, bool di
     // longer than the grid is still served: workgroups stride over it).
     unsigned grid = grid_max;
     int64_t queued = 0; // rounds launched so far
+    auto round_kernel = mode == ivx::FLOOD_LINEAR ? k_flood_round_list<2> : mode == ivx::FLOOD_DIRECTED ? k_flood_round_list<1> : k_flood_round_list<0>;
     auto queue_round = [&]() -> int {
         const int r = (int)(queued % RING), cur = (int)(queued & 1);
         const unsigned int tr = (unsigned int)(tag << 24) | (unsigned int)((queued + 1) & 0xffffff);
-        unsigned int *gw = arm.word; // every round carries the gate: the first one with a short list opens it
-        if (linear)
-            hipLaunchKernelGGL(k_flood_round_list<2>, dim3(grid), dim3(NT), 0, st, t, (const unsigned long long *)cand,
-                               (unsigned long long *)reached, list[cur], cnt + r, dirty[cur], dirty[cur ^ 1], list[cur ^ 1],
-                               cnt + (r + 1) % RING, cnt + (r + 2) % RING, (unsigned long long *)line, tr, gw, arm.value, arm.below);
-        else if (directed)
-            hipLaunchKernelGGL(k_flood_round_list<1>, dim3(grid), dim3(NT), 0, st, t, (const unsigned long long *)cand,
-                               (unsigned long long *)reached, list[cur], cnt + r, dirty[cur], dirty[cur ^ 1], list[cur ^ 1],
-                               cnt + (r + 1) % RING, cnt + (r + 2) % RING, (unsigned long long *)line, tr, gw, arm.value, arm.below);
-        else
-            hipLaunchKernelGGL(k_flood_round_list<0>, dim3(grid), dim3(NT), 0, st, t, (const unsigned long long *)cand,
-                               (unsigned long long *)reached, list[cur], cnt + r, dirty[cur], dirty[cur ^ 1], list[cur ^ 1],
-                               cnt + (r + 1) % RING, cnt + (r + 2) % RING, (unsigned long long *)line, tr, gw, arm.value, arm.below);
+        // every round carries the gate (arm.word): the first one with a short list opens it
+        hipLaunchKernelGGL(round_kernel, dim3(grid), dim3(NT), 0, st, t, (const unsigned long long *)cand,
+                           (unsigned long long *)reached, (const unsigned int *)list[cur], (const unsigned int *)(cnt + r), dirty[cur],
+                           dirty[cur ^ 1], list[cur ^ 1], cnt + (r + 1) % RING, cnt + (r + 2) % RING, (unsigned long long *)line, tr,
+                           arm.word, arm.value, arm.below);
         IVX_LAUNCH_CHECK();
         queued++;
         return IVX_OK;
@@ -1933,22 +1694,12 @@ static int flood_run_impl(const ivx_flood_plan *p, const uint64_t *cand, bool di
     for (;;) {
         while (queued < seen + 1 + ahead)
             if ((rc = queue_round())) return rc;
-        // wait for a round beyond `seen` to report
+        // wait for a round beyond `seen` to report; a few hundred ms without news: the safe path once
         unsigned long long v = 0;
-        bool got = false;
-        for (long spins = 0; spins < 20000000L; spins++) {
-            v = __atomic_load_n((const unsigned long long *)line, __ATOMIC_ACQUIRE);
-            if ((uint32_t)(v >> 56) == tag && (int64_t)((v >> 32) & 0xffffffull) > seen) { got = true; break; }
-#if defined(__x86_64__)
-            __builtin_ia32_pause();
-#endif
-        }
-        if (!got) { // a few hundred ms without news: take the safe path once
-            IVX_HIP(hipStreamSynchronize(st));
-            v = __atomic_load_n((const unsigned long long *)line, __ATOMIC_ACQUIRE);
-            IVX_REQUIRE((uint32_t)(v >> 56) == tag && (int64_t)((v >> 32) & 0xffffffull) > seen, IVX_EHIP,
-                        "flood: the queued rounds never reported");
-        }
+        rc = poll_line(line, 20000000L, st,
+                       [tag, seen](unsigned long long w) { return (uint32_t)(w >> 56) == tag && (int64_t)((w >> 32) & 0xffffffull) > seen; },
+                       "flood: the queued rounds never reported", &v);
+        if (rc) return rc;
         seen = (int64_t)((v >> 32) & 0xffffffull);
         const unsigned int n_list = (unsigned int)(v & 0xffffffffull);
         if (trace) fprintf(stderr, "ivx flood: round %lld starts with %u of %lld tiles (%lld queued)\n", (long long)seen, n_list,
@@ -1961,7 +1712,7 @@ static int flood_run_impl(const ivx_flood_plan *p, const uint64_t *cand, bool di
             break;
         }
         total_rounds = (int)seen;
-        if (!directed && total_rounds >= CCL_ESCAPE_ROUNDS && ivx::ccl_supported(p->strct_bits)) {
+        if (sym && total_rounds >= CCL_ESCAPE_ROUNDS && ivx::ccl_supported(p->strct_bits)) {
             // long, thin region: stop paying one launch per tile hop -- every reached bit so far is correct, the
             // union-find path completes the components they belong to in one flat pass (the rounds already queued
             // keep flooding until then, which is harmless)
@@ -1977,437 +1728,14 @@ static int flood_run_impl(const ivx_flood_plan *p, const uint64_t *cand, bool di
     return IVX_OK;
 }
 
-// ---- the IFT watershed's cost map, level by level, on bit planes (ivx_dev_ws_cost_levels) ------------------------------
-// C(p) = min over paths from a marker of the largest arc |I(a) - I(b)| on the path.  {C <= c} is the set the markers reach
-// through arcs of weight <= c: a flood on bit planes with arc planes instead of a candidate plane, and {C == c} is what
-// level c adds to level c - 1.  The chaotic relaxation of the cost map (k_ws_relax) spends its time on the levels where the
-// bulk of a noise volume connects (percolation: long winding paths, every tile revisited ~15 times with 16-bit costs in
-// LDS); here those levels cost bit-parallel tile visits (64 voxels per lane and operation).  The caller stops after the
-// bulk is in and hands the rest -- isolated pockets whose cost is decided by their own few arcs -- to the relaxation,
-// which starts from exact costs and has nothing left to correct.
-namespace {
-template <typename MT>
-__global__ __launch_bounds__(256) void k_wsa_seed(const MT *__restrict__ mk, int64_t n, unsigned long long *__restrict__ R) {
-    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const unsigned long long b = __ballot(p < n && mk[p] != 0);
-    if ((threadIdx.x & 63) == 0 && p < n) R[p >> 6] = b;
-}
-
-// Arc weights once, as bytes: wx / wy / wz[p] = min(|I(p) - I(p + 1 / W / HW)|, 127), 127 also when the neighbour's linear
-// index is >= n (levels stop far below 127: the caller caps them at 120).  Lane = 8 voxels; the ALU-heavy part of the arc
-// planes (field extraction, absolute differences) then happens once instead of once per level.
-__global__ __launch_bounds__(256) void k_wsa_weights(const uint16_t *__restrict__ I, int64_t n, int64_t W, int64_t HW,
-                                                     unsigned long long *__restrict__ wts) {
-    const int64_t nch = n >> 3;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nch; i += stride) {
-        const int64_t p0 = i << 3;
-        const bool hy = p0 + W < n, hz = p0 + HW < n;
-        const uint4 v = *reinterpret_cast<const uint4 *>(I + p0);
-        const uint4 vy = *reinterpret_cast<const uint4 *>(I + (hy ? p0 + W : p0));
-        const uint4 vz = *reinterpret_cast<const uint4 *>(I + (hz ? p0 + HW : p0));
-        const int next = p0 + 8 < n ? (int)I[p0 + 8] : -1000000;
-        const unsigned int vw[4] = {v.x, v.y, v.z, v.w}, yw[4] = {vy.x, vy.y, vy.z, vy.w}, zw[4] = {vz.x, vz.y, vz.z, vz.w};
-        unsigned long long bx = 0, by = 0, bz = 0;
-#pragma unroll
-        for (int e = 0; e < 8; e++) {
-            const int iv = (int)((vw[e >> 1] >> (16 * (e & 1))) & 0xffffu);
-            const int nx = e < 7 ? (int)((vw[(e + 1) >> 1] >> (16 * ((e + 1) & 1))) & 0xffffu) : next;
-            const int ny = (int)((yw[e >> 1] >> (16 * (e & 1))) & 0xffffu), nz = (int)((zw[e >> 1] >> (16 * (e & 1))) & 0xffffu);
-            const int dx = min(abs(iv - nx), 127), dy = hy ? min(abs(iv - ny), 127) : 127, dz = hz ? min(abs(iv - nz), 127) : 127;
-            bx |= (unsigned long long)dx << (8 * e);
-            by |= (unsigned long long)dy << (8 * e);
-            bz |= (unsigned long long)dz << (8 * e);
-        }
-        wts[i] = bx;
-        wts[nch + i] = by;
-        wts[2 * nch + i] = bz;
-    }
-}
-
-// the arc planes of level c from the weight bytes: lane = word = 8 x 8 bytes per direction; "byte <= c" for eight bytes at
-// once: (x | 0x80) - (c + 1) keeps bit 7 exactly when x >= c + 1 (x, c < 128: no borrow between bytes), and the eight
-// sign bits are gathered with one multiply
-__device__ __forceinline__ unsigned long long le8(unsigned long long x, unsigned long long c1) {
-    const unsigned long long t = (x | 0x8080808080808080ull) - c1;
-    return ((~t & 0x8080808080808080ull) * 0x0002040810204081ull) >> 56;
-}
-// The arc planes of L consecutive levels c .. c + L - 1 in one pass over the weight bytes (level l's three planes at
-// E + l * 3 * nwords): the weights are 3 bytes per voxel, a level's planes 3 bits -- one pass per level read 400 MB to write 48
-// (84 us x 15 levels at 512^3, 0.67 ms x 12 at 1024^3).
-template <int L>
-__global__ __launch_bounds__(256) void k_wsa_planes(const unsigned long long *__restrict__ wts, int64_t nwords, int c,
-                                                    unsigned long long *__restrict__ E) {
-    const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (w >= nwords) return;
-    const int64_t nch = nwords * 8;
-    unsigned long long c1[L];
-#pragma unroll
-    for (int l = 0; l < L; l++) c1[l] = (unsigned long long)(c + l + 1) * 0x0101010101010101ull;
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-        const ulonglong2 *src = reinterpret_cast<const ulonglong2 *>(wts + d * nch + w * 8);
-        unsigned long long m[L];
-#pragma unroll
-        for (int l = 0; l < L; l++) m[l] = 0;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const ulonglong2 x = src[q];
-#pragma unroll
-            for (int l = 0; l < L; l++) {
-                m[l] |= le8(x.x, c1[l]) << (16 * q);
-                m[l] |= le8(x.y, c1[l]) << (16 * q + 8);
-            }
-        }
-#pragma unroll
-        for (int l = 0; l < L; l++) E[((int64_t)l * 3 + d) * nwords + w] = m[l];
-    }
-}
-
-// lane = word: would ONE relaxation step add a bit to this word?  Then its tile starts the level's flood.
-__global__ __launch_bounds__(256) void k_wsa_frontier(Tiles t, const unsigned long long *__restrict__ R,
-                                                      const unsigned long long *__restrict__ E, uint8_t *__restrict__ dirty) {
-    const int64_t nwords = t.dz * t.dy * t.wx, hwx = t.dy * t.wx;
-    const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (w >= nwords) return;
-    const unsigned long long *Ex = E, *Ey = E + nwords, *Ez = E + 2 * nwords;
-    const unsigned long long r = R[w];
-    if (r == ~0ull) return;
-    const unsigned long long exp = Ex[w];
-    unsigned long long nr = r;
-    if (w > 0) nr |= (R[w - 1] & Ex[w - 1]) >> 63;
-    if (w + 1 < nwords) nr |= ((R[w + 1] & 1ull) & (exp >> 63)) << 63;
-    if (w - t.wx >= 0) nr |= R[w - t.wx] & Ey[w - t.wx];
-    if (w + t.wx < nwords) nr |= R[w + t.wx] & Ey[w];
-    if (w - hwx >= 0) nr |= R[w - hwx] & Ez[w - hwx];
-    if (w + hwx < nwords) nr |= R[w + hwx] & Ez[w];
-    nr |= ((nr & exp) << 1) | ((nr & (exp << 1)) >> 1); // one step along x inside the word is enough to see a gain
-    if (nr != r) {
-        const int64_t row = w / t.wx, txi = w - row * t.wx, z = row / t.dy, y = row - z * t.dy;
-        dirty[((z / TZ) * t.nty + (y >> TY_LOG)) * t.wx + txi] = 1;
-    }
-}
-
-// reached voxels so far (grid-stride, one atomic per workgroup)
-__global__ __launch_bounds__(256) void k_wsa_count(const unsigned long long *__restrict__ R, int64_t nwords,
-                                                   unsigned long long *__restrict__ count) {
-    __shared__ unsigned long long s_part[4];
-    unsigned long long mine = 0;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nwords; i += stride) mine += (unsigned long long)__popcll(R[i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long t = s_part[0] + s_part[1] + s_part[2] + s_part[3];
-        if (t) atomicAdd(count, t);
-    }
-}
-
-// After the last level: snap[l] = the reached plane as level l left it (planes nested: a bit set at level l is set at every
-// later one).  C[p] = the first level that has p; voxels no level reached keep their cost.  Lane = 16 voxels.
-__global__ __launch_bounds__(256) void k_wsa_costs(const uint16_t *__restrict__ snap, int64_t nchunks, int64_t plane_chunks, int levels,
-                                                   uint16_t *__restrict__ C) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nchunks; i += stride) {
-        const unsigned int last = snap[(int64_t)(levels - 1) * plane_chunks + i];
-        if (!last) continue;
-        uint16_t *dst = C + i * 16;
-        unsigned int lev[16];
-#pragma unroll
-        for (int e = 0; e < 16; e++) lev[e] = 0xffffu;
-        unsigned int have = 0;
-        for (int l = 0; l < levels && have != last; l++) {
-            const unsigned int m = snap[(int64_t)l * plane_chunks + i];
-            unsigned int nw = m & ~have;
-            have |= m;
-#pragma unroll
-            for (int e = 0; e < 16; e++)
-                if (nw >> e & 1u) lev[e] = (unsigned int)l;
-        }
-        if (last == 0xffffu) {
-            reinterpret_cast<uint4 *>(dst)[0] = make_uint4(lev[0] | lev[1] << 16, lev[2] | lev[3] << 16, lev[4] | lev[5] << 16, lev[6] | lev[7] << 16);
-            reinterpret_cast<uint4 *>(dst)[1] = make_uint4(lev[8] | lev[9] << 16, lev[10] | lev[11] << 16, lev[12] | lev[13] << 16, lev[14] | lev[15] << 16);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 16; e++)
-                if (last >> e & 1u) dst[e] = (uint16_t)lev[e];
-        }
-    }
-}
-} // namespace
-
-// Levels 0, 1, 2, ... of the IFT cost map until `stop_frac` of the voxels are in (or `max_levels` are done): C[p] = level for
-// every voxel reached (the others keep what the caller put there: 0xFFFF), *levels_done = number of levels completed,
-// *reached_out = voxels with a final cost.  6-neighbour structure, scipy's linear-index neighbourhood; needs dx % 64 == 0
-// and dy % 16 == 0 (IVX_EINVAL otherwise: the caller then runs its relaxation from the markers alone).
-extern "C" int ivx_dev_ws_cost_levels(const uint16_t *I, int mdtype, const void *markers, int64_t dz, int64_t dy, int64_t dx,
-                                      uint16_t *C, int max_levels, double stop_frac, int *levels_done, int64_t *reached_out,
-                                      int64_t *rounds_out, void *stream) {
-    IVX_REQUIRE(I && markers && C && dz > 0 && dy > 0 && dx > 0, IVX_EINVAL, "ws_cost_levels: bad arguments");
-    IVX_REQUIRE(dx % 64 == 0 && dy % TY == 0, IVX_EINVAL, "ws_cost_levels: needs dx %% 64 == 0 and dy %% 16 == 0");
-    IVX_REQUIRE(mdtype == IVX_I16 || mdtype == IVX_I8, IVX_EINVAL, "ws_cost_levels: markers must be int16 or int8");
-    ivx_flood_plan plan;
-    plan.dz = dz; plan.dy = dy; plan.dx = dx; plan.wx = dx / 64;
-    plan.strct_bits = (1u << 4) | (1u << 10) | (1u << 12) | (1u << 13) | (1u << 14) | (1u << 16) | (1u << 22);
-    Tiles t;
-    int rc = make_tiles(&plan, &t);
-    if (rc) return rc;
-    hipStream_t st = ivx::S(stream);
-    const int64_t n = dz * dy * dx, nwords = n >> 6;
-    const FScratch fs = make_fscratch(t);
-    IVX_REQUIRE(max_levels >= 1, IVX_EINVAL, "ws_cost_levels: max_levels");
-    if (max_levels > 120) max_levels = 120; // (the weight bytes saturate at 127)
-    // workspace: R | arc planes Ex Ey Ez | weight bytes x y z | flood scratch | one snapshot of R per level
-    constexpr int PL = 4; // levels whose arc planes are made by one pass over the weights
-    const size_t pw = (size_t)nwords * 8, o_E = al256(pw), o_W = al256(o_E + (size_t)PL * 3 * pw), o_S = al256(o_W + 3 * (size_t)n);
-    const size_t o_P = al256(o_S + fs.total);
-    void *mem;
-    if ((rc = ivx::ws_get_s(ivx::WS_WSA, st, o_P + (size_t)max_levels * pw + 256, &mem))) return rc;
-    unsigned long long *R = (unsigned long long *)mem;
-    unsigned long long *E_all = (unsigned long long *)((char *)mem + o_E); // PL levels x (Ex | Ey | Ez), nwords each
-    unsigned long long *wts = (unsigned long long *)((char *)mem + o_W); // n bytes per direction
-    char *scr = (char *)mem + o_S;
-    char *snaps = (char *)mem + o_P;
-    unsigned long long *d_count = (unsigned long long *)(scr + fs.off_status) + 2;
-    IVX_HIP(hipMemsetAsync(scr, 0, fs.off_seeds, st)); // dirty flags, counters
-    const unsigned gv = (unsigned)ivx::cdiv(n, 256), gw = (unsigned)ivx::cdiv(nwords, 256);
-    if (mdtype == IVX_I16) hipLaunchKernelGGL(k_wsa_seed<int16_t>, dim3(gv), dim3(256), 0, st, (const int16_t *)markers, n, R);
-    else hipLaunchKernelGGL(k_wsa_seed<int8_t>, dim3(gv), dim3(256), 0, st, (const int8_t *)markers, n, R);
-    IVX_LAUNCH_CHECK();
-    {
-        const int64_t blocks = ivx::cdiv(n >> 3, 256);
-        hipLaunchKernelGGL(k_wsa_weights, dim3((unsigned)(blocks < 32768 ? blocks : 32768)), dim3(256), 0, st, I, n, dx, dy * dx, wts);
-        IVX_LAUNCH_CHECK();
-    }
-    int64_t rounds_total = 0, reached = 0;
-    int c = 0;
-    for (; c < max_levels; c++) {
-        if (c % PL == 0) { // (weights above 127 saturate: levels beyond max_levels <= 120 are never asked for, their planes cost nothing extra)
-            hipLaunchKernelGGL(k_wsa_planes<PL>, dim3(gw), dim3(256), 0, st, wts, nwords, c, E_all);
-            IVX_LAUNCH_CHECK();
-        }
-        unsigned long long *E = E_all + (size_t)(c % PL) * 3 * nwords;
-        hipLaunchKernelGGL(k_wsa_frontier, dim3(gw), dim3(256), 0, st, t, R, E, (uint8_t *)(scr + fs.off_dirty0));
-        IVX_LAUNCH_CHECK();
-        int rounds = 0;
-        if ((rc = flood_run_impl(&plan, (const uint64_t *)E, true, (uint64_t *)R, scr, &rounds, stream, nullptr, true))) return rc;
-        rounds_total += rounds;
-        IVX_HIP(hipMemcpyAsync(snaps + (size_t)c * pw, R, pw, hipMemcpyDeviceToDevice, st));
-        IVX_HIP(hipMemsetAsync(d_count, 0, 8, st));
-        hipLaunchKernelGGL(k_wsa_count, dim3(gw < 1024 ? gw : 1024), dim3(256), 0, st, R, nwords, d_count);
-        IVX_LAUNCH_CHECK();
-        uint32_t seq, got[2] = {0, 0};
-        if ((rc = ivx::mailbox_publish(d_count, 2, st, &seq))) return rc;
-        if ((rc = ivx::mailbox_wait(seq, st, got, 2))) return rc;
-        reached = (int64_t)(((uint64_t)got[1] << 32) | got[0]);
-        if ((double)reached >= stop_frac * (double)n) {
-            c++;
-            break;
-        }
-    }
-    {
-        const int64_t nchunks = n / 16, blocks = ivx::cdiv(nchunks, 256);
-        hipLaunchKernelGGL(k_wsa_costs, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, st, (const uint16_t *)snaps,
-                           nchunks, (int64_t)(pw / 2), c, C);
-        IVX_LAUNCH_CHECK();
-    }
-    if (levels_done) *levels_done = c;
-    if (reached_out) *reached_out = reached;
-    if (rounds_out) *rounds_out = rounds_total;
-    return IVX_OK;
-}
-
-// ---- the scikit-image branch's cost map, level by level (ivx_dev_sk_cost_levels) ---------------------------------------
-// There a path costs the largest image VALUE on it (markers cost their own value), so {C <= c} is what the markers of value
-// <= c reach inside the candidate plane {I <= c}: the ordinary region-growing engine, coarse pass included.  The gradient
-// of a windowed image is zero over everything the window saturates: level 0 alone is ~95 % of such a volume, one flood.
-namespace {
-// Eight lanes' bytes of bits -> one word in the first of them (lane & 7 == 0): three exchanges.
-__device__ __forceinline__ unsigned long long gather_word8(uint32_t bits8, int lane) {
-    unsigned long long w = (unsigned long long)bits8 << (8 * (lane & 7));
-#pragma unroll
-    for (int o = 1; o < 8; o <<= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)w, o, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(w >> 32), o, 64);
-        w |= ((unsigned long long)hi << 32) | lo;
-    }
-    return w;
-}
-// The markers as a bit plane, once per call (lane = 8 voxels: one 16-byte load of int16 markers): a level's seeds are then
-// marker & candidate & ~reached per WORD.  (Rounds 1 - 5 read the marker volume voxel by voxel at every level: 170 us x 3 at
-// 512^3, 1.35 ms x 3 at 1024^3.)
-template <typename MT>
-__global__ __launch_bounds__(256) void k_ska_marker_bits(const MT *__restrict__ mk, int64_t n8, unsigned long long *__restrict__ mb) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; // (n8 is a multiple of 8: whole words, whole groups of eight lanes)
-    uint32_t bits = 0;
-    if (i < n8) {
-        MT v[8];
-        if (sizeof(MT) == 2) *reinterpret_cast<uint4 *>(v) = reinterpret_cast<const uint4 *>(mk)[i];
-        else *reinterpret_cast<uint2 *>(v) = reinterpret_cast<const uint2 *>(mk)[i];
-#pragma unroll
-        for (int e = 0; e < 8; e++) bits |= (v[e] != 0 ? 1u : 0u) << e;
-    }
-    const unsigned long long w = gather_word8(bits, threadIdx.x & 63);
-    if ((threadIdx.x & 7) == 0 && i < n8) mb[i >> 3] = w;
-}
-// ... and the candidate planes {I <= l} of the first L levels in one pass over the image (L <= 4)
-template <int L>
-__global__ __launch_bounds__(256) void k_ska_cands(const uint16_t *__restrict__ I, int64_t n8, int64_t nwords, unsigned long long *__restrict__ cand) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    uint32_t bits[L];
-#pragma unroll
-    for (int l = 0; l < L; l++) bits[l] = 0;
-    if (i < n8) {
-        uint16_t v[8];
-        *reinterpret_cast<uint4 *>(v) = reinterpret_cast<const uint4 *>(I)[i];
-#pragma unroll
-        for (int e = 0; e < 8; e++)
-#pragma unroll
-            for (int l = 0; l < L; l++) bits[l] |= (v[e] <= (uint16_t)l ? 1u : 0u) << e;
-    }
-#pragma unroll
-    for (int l = 0; l < L; l++) {
-        const unsigned long long w = gather_word8(bits[l], threadIdx.x & 63);
-        if ((threadIdx.x & 7) == 0 && i < n8) cand[(int64_t)l * nwords + (i >> 3)] = w;
-    }
-}
-// seeds of level c, lane = word
-__global__ __launch_bounds__(256) void k_ska_seed_bits(Tiles t, const unsigned long long *__restrict__ mb, const unsigned long long *__restrict__ cand,
-                                                       unsigned long long *__restrict__ R, uint8_t *__restrict__ dirty) {
-    const int64_t nwords = t.dz * t.dy * t.wx;
-    const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (w >= nwords) return;
-    const unsigned long long add = mb[w] & cand[w] & ~R[w];
-    if (!add) return;
-    R[w] |= add;
-    const int64_t row = w / t.wx, txi = w - row * t.wx, z = row / t.dy, y = row - z * t.dy;
-    mark_tile_nbhd(t, dirty, z / TZ, y / TY, txi);
-}
-
-// lane = word: a candidate bit that is not reached and has a reached neighbour under the structure -> its tile (and the
-// tiles around it) start the level's flood
-__global__ __launch_bounds__(256) void k_ska_frontier(Tiles t, const unsigned long long *__restrict__ cand,
-                                                      const unsigned long long *__restrict__ R, uint8_t *__restrict__ dirty) {
-    const int64_t nwords = t.dz * t.dy * t.wx;
-    const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (w >= nwords) return;
-    const unsigned long long open = cand[w] & ~R[w];
-    if (!open) return;
-    const int64_t row = w / t.wx, txi = w - row * t.wx, z = row / t.dy, y = row - z * t.dy;
-    unsigned long long nb = 0;
-    for (int kk = 0; kk < 3; kk++)
-        for (int jj = 0; jj < 3; jj++) {
-            const uint32_t m3 = (t.strct >> (kk * 9 + jj * 3)) & 7u;
-            if (!m3) continue;
-            // voxel q reached => q + (kk-1, jj-1, ii-1) reached: the source row of this word is (z - (kk-1), y - (jj-1))
-            const int64_t zs = z - (kk - 1), ys = y - (jj - 1);
-            if (zs < 0 || zs >= t.dz || ys < 0 || ys >= t.dy) continue;
-            const unsigned long long *rr = R + (zs * t.dy + ys) * t.wx;
-            const unsigned long long c0 = rr[txi];
-            const unsigned long long cl = txi > 0 ? rr[txi - 1] >> 63 : 0ull, cr = txi + 1 < t.wx ? rr[txi + 1] & 1ull : 0ull;
-            if (m3 & 2u) nb |= c0;
-            if (m3 & 4u) nb |= (c0 << 1) | cl;        // ii = 2: source bit x - 1
-            if (m3 & 1u) nb |= (c0 >> 1) | (cr << 63); // ii = 0: source bit x + 1
-        }
-    if (nb & open) mark_tile_nbhd(t, dirty, z / TZ, y / TY, txi);
-}
-} // namespace
-
-// Levels 0, 1, 2, ... of scikit-image's cost map (value-on-path minimax, lattice neighbours, any symmetric 3x3x3 structure)
-// until `stop_frac` of the voxels are in or `max_levels` are done; C[p] = level for every voxel reached.  Needs dx % 64 == 0,
-// 16-byte aligned image and markers.
-extern "C" int ivx_dev_sk_cost_levels(const uint16_t *I, int mdtype, const void *markers, int64_t dz, int64_t dy, int64_t dx,
-                                      const uint8_t strct[27], uint16_t *C, int max_levels, double stop_frac, int *levels_done,
-                                      int64_t *reached_out, int64_t *rounds_out, void *stream) {
-    IVX_REQUIRE(I && markers && C && strct && dz > 0 && dy > 0 && dx > 0, IVX_EINVAL, "sk_cost_levels: bad arguments");
-    IVX_REQUIRE(dx % 64 == 0, IVX_EINVAL, "sk_cost_levels: needs dx %% 64 == 0");
-    IVX_REQUIRE(mdtype == IVX_I16 || mdtype == IVX_I8, IVX_EINVAL, "sk_cost_levels: markers must be int16 or int8");
-    IVX_REQUIRE(max_levels >= 1, IVX_EINVAL, "sk_cost_levels: max_levels");
-    IVX_REQUIRE((((uintptr_t)I | (uintptr_t)markers) & 15) == 0, IVX_EINVAL, "sk_cost_levels: image and markers must be 16-byte aligned");
-    ivx_flood_plan plan;
-    plan.dz = dz; plan.dy = dy; plan.dx = dx; plan.wx = dx / 64;
-    const int64_t s3[3] = {3, 3, 3};
-    int rc = ivx_flood_strct_bits(strct, s3, &plan.strct_bits);
-    if (rc) return rc;
-    Tiles t;
-    if ((rc = make_tiles(&plan, &t))) return rc;
-    hipStream_t st = ivx::S(stream);
-    const int64_t n = dz * dy * dx, nwords = n >> 6;
-    const FScratch fs = make_fscratch(t);
-    // workspace: R | candidate planes (the first `ahead` levels' made in one pass, then one at a time) | marker plane | flood scratch | snapshots
-    const int ahead = max_levels < 4 ? max_levels : 4;
-    const size_t pw = (size_t)nwords * 8, o_C = al256(pw), o_M = al256(o_C + (size_t)ahead * pw), o_S = al256(o_M + pw), o_P = al256(o_S + fs.total);
-    void *mem;
-    if ((rc = ivx::ws_get_s(ivx::WS_WSA, st, o_P + (size_t)max_levels * pw + 256, &mem))) return rc;
-    unsigned long long *R = (unsigned long long *)mem, *cand0 = (unsigned long long *)((char *)mem + o_C);
-    unsigned long long *mb = (unsigned long long *)((char *)mem + o_M);
-    char *scr = (char *)mem + o_S, *snaps = (char *)mem + o_P;
-    unsigned long long *d_count = (unsigned long long *)(scr + fs.off_status) + 2;
-    if ((rc = ivx_dev_flood_clear(&plan, (uint64_t *)R, scr, stream))) return rc;
-    const unsigned gw = (unsigned)ivx::cdiv(nwords, 256);
-    uint8_t *dirty = (uint8_t *)(scr + fs.off_dirty0);
-    int64_t rounds_total = 0, reached = 0;
-    {
-        const int64_t n8 = n >> 3;
-        const unsigned g8 = (unsigned)ivx::cdiv(n8, 256);
-        if (mdtype == IVX_I16) hipLaunchKernelGGL(k_ska_marker_bits<int16_t>, dim3(g8), dim3(256), 0, st, (const int16_t *)markers, n8, mb);
-        else hipLaunchKernelGGL(k_ska_marker_bits<int8_t>, dim3(g8), dim3(256), 0, st, (const int8_t *)markers, n8, mb);
-        IVX_LAUNCH_CHECK();
-        switch (ahead) {
-        case 1: hipLaunchKernelGGL(k_ska_cands<1>, dim3(g8), dim3(256), 0, st, I, n8, nwords, cand0); break;
-        case 2: hipLaunchKernelGGL(k_ska_cands<2>, dim3(g8), dim3(256), 0, st, I, n8, nwords, cand0); break;
-        case 3: hipLaunchKernelGGL(k_ska_cands<3>, dim3(g8), dim3(256), 0, st, I, n8, nwords, cand0); break;
-        default: hipLaunchKernelGGL(k_ska_cands<4>, dim3(g8), dim3(256), 0, st, I, n8, nwords, cand0); break;
-        }
-        IVX_LAUNCH_CHECK();
-    }
-    int c = 0;
-    for (; c < max_levels; c++) {
-        unsigned long long *cand = c < ahead ? cand0 + (size_t)c * nwords : cand0;
-        if (c >= ahead && (rc = ivx_dev_flood_candidates(&plan, IVX_U16, I, 0.0, (double)c, nullptr, 0, 0.0, (uint64_t *)cand, stream))) return rc;
-        if (c > 0) {
-            // "closed" tiles were closed for the previous level's candidate plane: this one has more candidates
-            IVX_HIP(hipMemsetAsync(scr + fs.off_dirty0, 0, fs.off_cnt - fs.off_dirty0, st));
-            hipLaunchKernelGGL(k_ska_frontier, dim3(gw), dim3(256), 0, st, t, cand, R, dirty);
-            IVX_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL(k_ska_seed_bits, dim3(gw), dim3(256), 0, st, t, mb, cand, R, dirty);
-        IVX_LAUNCH_CHECK();
-        ivx::ccl_invalidate(scr);
-        int rounds = 0;
-        if ((rc = flood_run_impl(&plan, (const uint64_t *)cand, false, (uint64_t *)R, scr, &rounds, stream))) return rc;
-        rounds_total += rounds;
-        IVX_HIP(hipMemcpyAsync(snaps + (size_t)c * pw, R, pw, hipMemcpyDeviceToDevice, st));
-        IVX_HIP(hipMemsetAsync(d_count, 0, 8, st));
-        hipLaunchKernelGGL(k_wsa_count, dim3(gw < 1024 ? gw : 1024), dim3(256), 0, st, R, nwords, d_count);
-        IVX_LAUNCH_CHECK();
-        uint32_t seq, got[2] = {0, 0};
-        if ((rc = ivx::mailbox_publish(d_count, 2, st, &seq))) return rc;
-        if ((rc = ivx::mailbox_wait(seq, st, got, 2))) return rc;
-        reached = (int64_t)(((uint64_t)got[1] << 32) | got[0]);
-        // enough is in -- or level 0 shows that this image has no plateau to speak of (a raw gradient: the bulk connects
-        // dozens of levels up, and walking there level by level costs more than the relaxation it would save)
-        if ((double)reached >= stop_frac * (double)n || (c == 0 && (double)reached < 0.05 * (double)n)) {
-            c++;
-            break;
-        }
-    }
-    {
-        const int64_t nchunks = n / 16, blocks = ivx::cdiv(nchunks, 256);
-        hipLaunchKernelGGL(k_wsa_costs, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, st, (const uint16_t *)snaps,
-                           nchunks, (int64_t)(pw / 2), c, C);
-        IVX_LAUNCH_CHECK();
-    }
-    if (levels_done) *levels_done = c;
-    if (reached_out) *reached_out = reached;
-    if (rounds_out) *rounds_out = rounds_total;
-    return IVX_OK;
+int ivx::flood_run(const ivx_flood_plan *p, const uint64_t *planes, ivx::FloodMode mode, uint64_t *reached, void *scratch,
+                   int *rounds, void *stream) {
+    return flood_run_impl(p, planes, mode, reached, scratch, rounds, stream);
 }
 
 extern "C" int ivx_dev_flood_run(const ivx_flood_plan *p, const uint64_t *cand, uint64_t *reached, void *scratch_,
                                  int *rounds, void *stream) {
-    return flood_run_impl(p, cand, false, reached, scratch_, rounds, stream);
+    return flood_run_impl(p, cand, ivx::FLOOD_SYMMETRIC, reached, scratch_, rounds, stream);
 }
 // clear + seed + run in one call: the flood of `seeds` over `cand` into a plane whose old contents are dead.  With at most
 // 16 seeds and a standard structuring element the clearing and the seeding ride on the coarse pass (three launches before
@@ -2429,10 +1757,10 @@ static int flood_grow_impl(const ivx_flood_plan *p, int dtype, const void *data,
         const char *e = getenv("IVX_FLOOD_FUSED");
         return !(e && e[0] == '0');
     }();
-    if (!(fused_on && nseeds >= 1 && nseeds <= 16 && t.ntiles > 0 && flood_mode() == 1 && coarse_ok(t, false))) {
+    if (!(fused_on && nseeds >= 1 && nseeds <= 16 && t.ntiles > 0 && !flood_mode_ccl() && coarse_ok(t, ivx::FLOOD_SYMMETRIC))) {
         if ((rc = ivx_dev_flood_clear(p, reached, scratch_, stream))) return rc;
         if ((rc = ivx_dev_flood_seed(p, dtype, data, t0, t1, seeds_xyz, nseeds, cand, reached, scratch_, stream))) return rc;
-        return flood_run_impl(p, cand, false, reached, scratch_, rounds, stream, nullptr, false, resident);
+        return flood_run_impl(p, cand, ivx::FLOOD_SYMMETRIC, reached, scratch_, rounds, stream, nullptr, resident);
     }
     ivx::ccl_invalidate(scratch_);
     Fresh f;
@@ -2443,7 +1771,7 @@ static int flood_grow_impl(const ivx_flood_plan *p, int dtype, const void *data,
     f.sp.n = (int)nseeds;
     for (int64_t n = 0; n < nseeds; n++)
         for (int q = 0; q < 3; q++) f.sp.xyz[n][q] = seeds_xyz[3 * n + q];
-    return flood_run_impl(p, cand, false, reached, scratch_, rounds, stream, &f, false, resident);
+    return flood_run_impl(p, cand, ivx::FLOOD_SYMMETRIC, reached, scratch_, rounds, stream, &f, resident);
 }
 extern "C" int ivx_dev_flood_grow(const ivx_flood_plan *p, int dtype, const void *data, double t0, double t1,
                                   const int64_t *seeds_xyz, int64_t nseeds, uint64_t *cand, uint64_t *reached, void *scratch_,
@@ -2472,7 +1800,7 @@ extern "C" int ivx_dev_flood_wait(const ivx_flood_plan *p, const uint64_t *cand,
 
 extern "C" int ivx_dev_flood_run_edges(const ivx_flood_plan *p, const uint64_t *edges, uint64_t *reached, void *scratch_,
                                        int *rounds, void *stream) {
-    return flood_run_impl(p, edges, true, reached, scratch_, rounds, stream);
+    return flood_run_impl(p, edges, ivx::FLOOD_DIRECTED, reached, scratch_, rounds, stream);
 }
 
 extern "C" int ivx_flood_edges_bytes(const ivx_flood_plan *p, size_t *nbytes) {

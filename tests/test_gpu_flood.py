@@ -185,10 +185,11 @@ def test_long_serpentine_escapes_to_union_find(ivxlib, oracle):
         assert (og == 9).sum() >= dx * dy // 2
 
 
-@pytest.mark.parametrize("mode", ["ccl", "persistent", "rounds", "resident"])
+@pytest.mark.parametrize("mode", ["ccl", "rounds", "resident"])
 def test_all_flood_engines_agree(ivxlib, oracle, mode):
-    """the engines (tile frontier per round, the same rounds in one resident launch, persistent frontier, union-find) in a
-    fresh process each"""
+    """the engines (tile frontier per round, the same rounds in one resident launch, union-find) in a fresh process each,
+    under the three standard structures and one that is none of them (6 faces + the four in-plane diagonals: the generic
+    gather of the tile update); every flood fills more than one tile and less than the volume"""
     import os
     import subprocess
     import sys
@@ -201,14 +202,17 @@ def test_all_flood_engines_agree(ivxlib, oracle, mode):
         "from oracle import oracle as orc\n"
         "img = synth_volume((40, 72, 136), seed=91)\n"
         "rng = np.random.default_rng(3)\n"
-        "for conn in (1, 2, 3):\n"
-        "    s = generate_binary_structure(3, conn)\n"
+        "s10 = generate_binary_structure(3, 1)\n"
+        "s10[1, ::2, ::2] = True\n"
+        "for conn in (1, 2, 3, 10):\n"
+        "    s = s10 if conn == 10 else generate_binary_structure(3, conn)\n"
         "    z, y, x = np.unravel_index(np.argmax(img), img.shape)\n"
         "    seeds = [(int(x), int(y), int(z)), (5, 5, 5)]\n"
-        "    og = (rng.random(img.shape) < 0.02).astype(np.uint8); orf = og.copy()\n"
+        "    og0 = (rng.random(img.shape) < 0.02).astype(np.uint8); og = og0.copy(); orf = og0.copy()\n"
         "    ff.floodfill_threshold(img, seeds, -820, 3071, 1, s, og)\n"
         "    orc.floodfill_threshold(img, seeds, -820, 3071, 1, s, orf)\n"
         "    assert np.array_equal(og, orf), conn\n"
+        "    assert 64 * 16 * 16 < int((orf == 1).sum()) - int((og0 == 1).sum()) < img.size, conn\n"
         "print('engines-ok')\n") % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                                    os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, IVX_FLOOD_MODE=mode)

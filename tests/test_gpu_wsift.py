@@ -180,7 +180,7 @@ def test_millions_of_marker_voxels(ivxlib, oracle):
 @pytest.mark.parametrize("shape", [(20, 16, 64), (33, 32, 128), (17, 48, 192), (40, 64, 64), (3, 16, 128)])
 @pytest.mark.parametrize("frac", ["0.9", "1.0", "0.3"])
 def test_cost_levels_on_bit_planes_equal_the_serial_flood(ivxlib, oracle, monkeypatch, shape, frac):
-    """The cost map's level floods (ivx_dev_ws_cost_levels, csrc/k_flood.hip: arc planes + scipy's linear-index
+    """The cost map's level floods (ivx_dev_ws_cost_levels, csrc/k_costlevels.hip: arc planes + scipy's linear-index
     neighbourhood on a flat bit array) followed by the relaxation of what is left: labels AND costs equal the serial,
     defect-free flood on volumes whose borders matter (one word / one tile wide, odd slice counts), whatever share of the
     voxels the levels take."""
