@@ -40,6 +40,7 @@ extern "C" {
 #define IVX_ENOMEM (-3) /* host or device allocation failed     -> MemoryError                     */
 #define IVX_EDOM (-4)   /* NumCast failure                      -> ValueError (Rust: unwrap panic) */
 #define IVX_EHIP (-5)   /* HIP runtime error / no device        -> RuntimeError                    */
+#define IVX_ESTALE (-6) /* a registered host array was written without ivx_host_touch (only with the stale check on) */
 
 /* dtype codes (image dtypes accepted by the reference's ImageTypes3 enum, invesalius_rs/src/types.rs:4-70) */
 #define IVX_U8 0
@@ -96,6 +97,52 @@ int ivx_stream_wait_event(void *stream, void *event); /* work queued on `stream`
 int ivx_event_elapsed_ms(void *start, void *stop, float *ms); /* synchronises on `stop` */
 /* free the cached device workspaces the host-level entry points keep between calls */
 int ivx_release_workspace(void);
+
+/* ------------------------------------------------------------------------------------------------
+ * resident host arrays: the project's image and mask matrices stay in HBM between host-level calls
+ *   no counterpart upstream: the reference keeps one array per project (`Slice.matrix`,
+ *   invesalius/data/slice_.py:175-188; `Mask.matrix`, invesalius/data/mask.py:422-431) and hands it to the
+ *   native layer again and again (styles.py:3200-3203, slice_.py:898,906); the host-level entry points of
+ *   this header keep that call surface, so without this block each of them stages its inputs per call.
+ * ivx_host_register mirrors the byte range [base, base + nbytes) on the current device, uploads it once and
+ * returns a handle.  From then on every host-level entry point of this header (and ivx_memcpy_h2d / _d2h,
+ * ivx_upload_strided / ivx_download_strided) that is handed memory whose whole byte extent -- computed from
+ * shape and signed byte strides -- lies inside the range
+ *   - takes its input from the mirror, device to device (dense, re-pitched, or gathered element by element for
+ *     short rows, stepped, reversed and transposed views) instead of from the host;
+ *   - writes its output to the host as before (the host copy is the authoritative one) AND into the mirror.
+ * A library write that only partly overlaps a range marks the overlap stale; it is uploaded again at the next
+ * use.  The calls stay synchronous: the destination is complete on return.
+ * The host side of the bargain: whoever writes registered memory with the CPU says so with ivx_host_touch /
+ * ivx_host_touch_range (offset and size in bytes from `base`); exactly those bytes are uploaded again at the
+ * next use.  ivx_host_set_check(1) (or IVX_RESIDENT_CHECK=1) makes every use compare the host bytes with the
+ * mirror first and fail with IVX_ESTALE -- ivx_last_error() names the first differing byte offset -- at the
+ * price of the upload the registration saves: a debugging aid, off by default.
+ * Rules: overlapping registrations are IVX_EINVAL; a view with a zero stride on an axis longer than 1 counts as
+ * not registered; a mirror belongs to the device that was current at registration, on any other device the
+ * range counts as not registered; a handle is a generation number that is never given out twice, so a released
+ * handle is IVX_EINVAL, never a lookup by address; ivx_host_release waits for a copy that is using the mirror.
+ * A mirror that does not fit is IVX_ENOMEM and the range stays unregistered (no eviction).  With nothing
+ * registered no byte moves differently.
+ * ivx_host_stats: out = { uploads served, bytes served, refresh uploads, bytes re-uploaded, write-throughs,
+ * bytes written through, invalidations, generation }.  ivx_transfer_stats (process-wide): out = { bytes the
+ * copy helpers moved host -> device, device -> host, host -> device for the stale check alone (not in [0]),
+ * bytes served from mirrors }.  Only the copy helpers named above are counted -- what carries images, masks and
+ * their views, the offset table of a packed refresh included; small arguments that an entry point sends with a
+ * plain hipMemcpy (seeds, the per-slice skip flags of ivx_threshold_all_slices, mesh arrays) are not.
+ * ---------------------------------------------------------------------------------------------- */
+int ivx_host_register(const void *base, size_t nbytes, uint64_t *handle);
+int ivx_host_touch(uint64_t handle);
+int ivx_host_touch_range(uint64_t handle, size_t offset, size_t nbytes);
+int ivx_host_release(uint64_t handle);
+int ivx_host_stats(uint64_t handle, uint64_t out[8]);
+int ivx_host_count(uint64_t *count); /* live registrations */
+int ivx_host_set_check(int on);
+int ivx_transfer_stats(uint64_t out[4]);
+/* a 3-D host view (signed byte strides, itemsize 1 / 2 / 4 / 8) <-> a dense device block: the staging every host-level
+ * entry point does with its arrays, for callers that keep device blocks of their own (DeviceBuffer.upload_view) */
+int ivx_upload_strided(void *dst, const void *src, const int64_t shape[3], const int64_t strides[3], size_t itemsize);
+int ivx_download_strided(void *dst, const int64_t shape[3], const int64_t strides[3], const void *src, size_t itemsize);
 
 /* ------------------------------------------------------------------------------------------------
  * threshold -> uint8 mask

@@ -14,7 +14,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("IVX_LIB_PATH") or os.path.join(_HERE, "libivx.so")  # IVX_LIB_PATH: A/B builds of the same ABI
 
-IVX_OK, IVX_EINVAL, IVX_ERANGE, IVX_ENOMEM, IVX_EDOM, IVX_EHIP = 0, -1, -2, -3, -4, -5
+IVX_OK, IVX_EINVAL, IVX_ERANGE, IVX_ENOMEM, IVX_EDOM, IVX_EHIP, IVX_ESTALE = 0, -1, -2, -3, -4, -5, -6
 U8, I16, F64, U16, F32, I32, I64, I8 = 0, 1, 2, 3, 4, 5, 6, 7
 DT = {np.dtype(np.uint8): U8, np.dtype(np.int16): I16, np.dtype(np.float64): F64, np.dtype(np.uint16): U16, np.dtype(np.float32): F32, np.dtype(np.int32): I32,
       np.dtype(np.int64): I64}
@@ -52,6 +52,22 @@ class VolrenParams(ctypes.Structure):
     ]
 
 
+class StaleError(RuntimeError):
+    """IVX_ESTALE: a registered host array (resident.bind) was written without a touch; raised only with the stale check on."""
+
+
+def _declare(lib):
+    """signatures of the resident-array calls (include/ivx.h): handles are 64-bit, sizes size_t"""
+    u64, sz, u64p = ctypes.c_uint64, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64)
+    i64p = ctypes.POINTER(c_i64)
+    for name, args in (("ivx_host_register", [c_vp, sz, u64p]), ("ivx_host_touch", [u64]), ("ivx_host_touch_range", [u64, sz, sz]),
+                       ("ivx_host_release", [u64]), ("ivx_host_stats", [u64, u64p]), ("ivx_host_count", [u64p]),
+                       ("ivx_host_set_check", [ctypes.c_int]), ("ivx_transfer_stats", [u64p]),
+                       ("ivx_upload_strided", [c_vp, c_vp, i64p, i64p, sz]), ("ivx_download_strided", [c_vp, i64p, i64p, c_vp, sz])):
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = args, ctypes.c_int
+
+
 _lib = None
 
 
@@ -65,6 +81,7 @@ def lib() -> ctypes.CDLL:
                 "(there is no CPU fallback in this package)" % LIB_PATH)
         _lib = ctypes.CDLL(LIB_PATH)
         _lib.ivx_last_error.restype = ctypes.c_char_p
+        _declare(_lib)
     return _lib
 
 
@@ -85,6 +102,8 @@ def check(rc: int, what: str = "ivx") -> int:
         raise MemoryError(msg)
     if rc == IVX_EDOM:
         raise ValueError(msg)
+    if rc == IVX_ESTALE:
+        raise StaleError(msg)
     raise RuntimeError(msg)
 
 

@@ -83,6 +83,11 @@ int download_strided(void *dst, const int64_t shape[3], const int64_t strides[3]
                      int hslot);
 int download_strided2(void *dst, const int64_t shape[2], const int64_t strides[2], const void *src_dev, size_t isz,
                       int hslot);
+// Resident host arrays (ivx_host_register; ivx_runtime.hip): the four helpers above serve uploads from a registered range's
+// device mirror and write downloads through to it.  An entry point that writes a caller's array with the CPU instead says
+// so here -- the view's values go into the mirror as well (through `d_scratch`, a device block with room for the view).
+// Does nothing when the view lies in no registered range.
+int mirror_host_view(const void *view, const int64_t shape[3], const int64_t strides[3], size_t isz, void *d_scratch, int hslot);
 
 // run-based union-find flood (k_ccl.hip)
 void ccl_forget_stream(void *stream);

@@ -7,6 +7,7 @@
 #include <sys/mman.h>
 #include <unistd.h>
 
+#include <atomic>
 #include <map>
 #include <vector>
 #include <mutex>
@@ -14,6 +15,7 @@
 #include <vector>
 
 #include "ivx_internal.h"
+#include "resident_ranges.h"
 
 namespace ivx {
 
@@ -281,15 +283,20 @@ static bool mostly_untouched(const void *p, size_t n) {
 //   device -> host into pages never touched (np.empty): hipMemcpy 24.9 GB/s (faults taken by one thread), lanes 46 GB/s -> lanes
 //   device -> host into touched pages: hipMemcpy 55 GB/s, lanes 47 GB/s                                                 -> hipMemcpy
 // IVX_STAGE_THREADS=0 never uses the lanes; IVX_STAGE_UP=1 sends uploads through them as well (A/B).
-int copy_h2d(void *dst_dev, const void *src, size_t n) {
+// (bytes the helpers of this file really moved across the link, ivx_transfer_stats: [0] host -> device, [1] device -> host,
+// [2] host -> device for the stale check alone (not in [0]), [3] served device -> device from a resident mirror)
+static std::atomic<uint64_t> g_xfer[4];
+static int raw_h2d(void *dst_dev, const void *src, size_t n) {
     if (!n) return IVX_OK;
+    g_xfer[0].fetch_add(n, std::memory_order_relaxed);
     static const bool up = []() { const char *e = getenv("IVX_STAGE_UP"); return e && e[0] == '1'; }();
     if (up && n >= STAGE_MIN && stage_lanes() > 0 && !host_is_pinned(src)) return staged_copy(dst_dev, const_cast<void *>(src), n, true);
     IVX_HIP(hipMemcpy(dst_dev, src, n, hipMemcpyHostToDevice));
     return IVX_OK;
 }
-int copy_d2h(void *dst, const void *src_dev, size_t n) {
+static int raw_d2h(void *dst, const void *src_dev, size_t n) {
     if (!n) return IVX_OK;
+    g_xfer[1].fetch_add(n, std::memory_order_relaxed);
     // IVX_D2H_LANES (read per call: A/B runs flip it inside one process): 1 = every pageable destination through the lanes,
     // 0 = never, unset = where the destination's pages are mostly not resident yet
     const char *force = getenv("IVX_D2H_LANES");
@@ -374,6 +381,340 @@ static int span_buffer(int hslot, size_t span, SpanSlot **out) {
     return IVX_OK;
 }
 
+// ---- resident host arrays -----------------------------------------------------------------------------
+// A caller declares once that a host byte range is the project's image or mask matrix (ivx_host_register): the range gets
+// a mirror in HBM, and every copy helper of this file that is handed memory inside it serves an upload from the mirror
+// (device -> device) and writes a download through to it, the host copy staying the authoritative one.  The range
+// arithmetic and the table are resident_ranges.h; here are the mirror, the kernels and the lock.  Every device operation
+// on a mirror runs on the null stream under g_res_mu and is synchronised before the lock is dropped, so a mirror is at
+// rest whenever the lock is free (a release therefore waits for a copy in flight) and every served copy is complete when
+// the helper returns, like the hipMemcpy it replaces.  g_res_count == 0 skips all of it.
+static std::mutex g_res_mu;
+static resident::Registry g_res;
+static std::atomic<size_t> g_res_count{0};
+static std::atomic<int> g_res_check{-1}; // ivx_host_set_check; -1: IVX_RESIDENT_CHECK decides
+static std::map<int, void *> g_res_chk;  // per device: staging block of the stale check and the packed refresh + the check's result word
+constexpr size_t RES_CHK_CHUNK = 16u << 20;
+
+static bool res_check_on() {
+    int v = g_res_check.load(std::memory_order_relaxed);
+    if (v < 0) {
+        const char *e = getenv("IVX_RESIDENT_CHECK");
+        v = e && e[0] == '1';
+        g_res_check.store(v, std::memory_order_relaxed);
+    }
+    return v != 0;
+}
+
+// Any 3-D view <-> dense, one element (or 16 bytes of the dense side) per lane.  Consecutive lanes walk the dense side's
+// innermost index, so the dense side is always coalesced; the view side is whatever the strides make it.  `view` points at
+// element [0][0][0], strides are signed bytes.  VEC: the dense rows are whole 16-byte chunks of an aligned block.
+template <typename T, bool SCATTER, bool VEC>
+static __device__ __forceinline__ void view_xfer_lane(uint8_t *__restrict__ view, int64_t s0, int64_t s1, int64_t s2, T *__restrict__ dense,
+                                                      int64_t n0, int64_t n1, int64_t n2) {
+    constexpr int E = VEC ? 16 / (int)sizeof(T) : 1;
+    const int64_t per_row = n2 / E;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n0 * n1 * per_row) return;
+    const int64_t c = i % per_row, r = i / per_row, y = r % n1, z = r / n1;
+    uint8_t *vp = view + z * s0 + y * s1 + c * E * s2;
+    T *dp = dense + r * n2 + c * E;
+    if (VEC) {
+        union {
+            uint4 q;
+            T e[E];
+        } u;
+        if (SCATTER) {
+            u.q = *reinterpret_cast<const uint4 *>(dp);
+#pragma unroll
+            for (int k = 0; k < E; k++) *reinterpret_cast<T *>(vp + k * s2) = u.e[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < E; k++) u.e[k] = *reinterpret_cast<const T *>(vp + k * s2);
+            *reinterpret_cast<uint4 *>(dp) = u.q;
+        }
+    } else {
+        if (SCATTER) *reinterpret_cast<T *>(vp) = *dp;
+        else
+            *dp = *reinterpret_cast<const T *>(vp);
+    }
+}
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void k_view_gather(uint8_t *__restrict__ view, int64_t s0, int64_t s1, int64_t s2, T *__restrict__ dense,
+                                                     int64_t n0, int64_t n1, int64_t n2) {
+    view_xfer_lane<T, false, VEC>(view, s0, s1, s2, dense, n0, n1, n2);
+}
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void k_view_scatter(uint8_t *__restrict__ view, int64_t s0, int64_t s1, int64_t s2, T *__restrict__ dense,
+                                                      int64_t n0, int64_t n1, int64_t n2) {
+    view_xfer_lane<T, true, VEC>(view, s0, s1, s2, dense, n0, n1, n2);
+}
+
+template <typename T, bool SCATTER, bool VEC>
+static int view_xfer_launch(uint8_t *view, const int64_t st[3], void *dense, const int64_t shape[3]) {
+    const int64_t E = VEC ? 16 / (int64_t)sizeof(T) : 1;
+    const int64_t blocks = cdiv(shape[0] * shape[1] * (shape[2] / E), 256);
+    IVX_REQUIRE(blocks > 0 && blocks < ((int64_t)1 << 31), IVX_EINVAL, "view copy: %lld workgroups", (long long)blocks);
+    if (SCATTER)
+        hipLaunchKernelGGL((k_view_scatter<T, VEC>), dim3((unsigned)blocks), dim3(256), 0, 0, view, st[0], st[1], st[2], (T *)dense, shape[0],
+                           shape[1], shape[2]);
+    else
+        hipLaunchKernelGGL((k_view_gather<T, VEC>), dim3((unsigned)blocks), dim3(256), 0, 0, view, st[0], st[1], st[2], (T *)dense, shape[0],
+                           shape[1], shape[2]);
+    IVX_LAUNCH_CHECK();
+    return IVX_OK;
+}
+template <bool SCATTER> static int view_xfer(uint8_t *view, const int64_t st[3], void *dense, const int64_t shape[3], size_t isz) {
+    const bool vec = (shape[2] * (int64_t)isz) % 16 == 0 && ((uintptr_t)dense & 15) == 0;
+    switch (isz) {
+    case 1: return vec ? view_xfer_launch<uint8_t, SCATTER, true>(view, st, dense, shape) : view_xfer_launch<uint8_t, SCATTER, false>(view, st, dense, shape);
+    case 2: return vec ? view_xfer_launch<uint16_t, SCATTER, true>(view, st, dense, shape) : view_xfer_launch<uint16_t, SCATTER, false>(view, st, dense, shape);
+    case 4: return vec ? view_xfer_launch<uint32_t, SCATTER, true>(view, st, dense, shape) : view_xfer_launch<uint32_t, SCATTER, false>(view, st, dense, shape);
+    case 8: return vec ? view_xfer_launch<uint64_t, SCATTER, true>(view, st, dense, shape) : view_xfer_launch<uint64_t, SCATTER, false>(view, st, dense, shape);
+    }
+    set_error("view copy: item size %zu (1, 2, 4 or 8)", isz);
+    return IVX_EINVAL;
+}
+
+// *first = min(*first, off0 + offset of the first byte where a and b differ); a, b 16-byte aligned, 16 bytes per lane
+__global__ __launch_bounds__(256) void k_bytes_differ(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, size_t n,
+                                                      unsigned long long off0, unsigned long long *first) {
+    __shared__ unsigned long long s[256];
+    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 16;
+    unsigned long long mine = ~0ull;
+    if (i < n) {
+        const int len = n - i < 16 ? (int)(n - i) : 16;
+        alignas(16) uint8_t x[16], y[16];
+        if (len == 16) {
+            *reinterpret_cast<uint4 *>(x) = *reinterpret_cast<const uint4 *>(a + i);
+            *reinterpret_cast<uint4 *>(y) = *reinterpret_cast<const uint4 *>(b + i);
+        } else
+            for (int q = 0; q < len; q++) x[q] = a[i + q], y[q] = b[i + q];
+        for (int q = len - 1; q >= 0; q--)
+            if (x[q] != y[q]) mine = off0 + i + (unsigned)q;
+    }
+    s[threadIdx.x] = mine;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w && s[threadIdx.x + w] < s[threadIdx.x]) s[threadIdx.x] = s[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && s[0] != ~0ull) atomicMin(first, s[0]);
+}
+
+// mirror[dst + i] = block[src + i] for the intervals of `tab` (dst, src, len triples at the head of the block): one
+// workgroup per interval -- the many small pending writes of a registration (flag cells) in one upload and one launch
+__global__ __launch_bounds__(256) void k_patch(uint8_t *__restrict__ mirror, const uint8_t *__restrict__ block) {
+    const unsigned long long *tab = reinterpret_cast<const unsigned long long *>(block) + 3 * (size_t)blockIdx.x;
+    const unsigned long long dst = tab[0], src = tab[1], len = tab[2];
+    for (unsigned long long i = threadIdx.x; i < len; i += 256) mirror[dst + i] = block[src + i];
+}
+
+static int res_scratch(int dev, void **blk) { // per device: RES_CHK_CHUNK bytes + the stale check's result word
+    void *&b = g_res_chk[dev];
+    if (!b) IVX_HIP(hipMalloc(&b, RES_CHK_CHUNK + 16));
+    *blk = b;
+    return IVX_OK;
+}
+
+// the host's pending writes into the mirror, exactly those bytes
+static int res_refresh(resident::Range *r) {
+    const size_t ni = r->pending.v.size(), nb = r->pending.bytes();
+    if (ni > 4 && ni * 24 + nb <= (1u << 20)) { // many small ones: packed behind a table, one copy, one launch
+        std::vector<uint8_t> pack(ni * 24 + nb);
+        unsigned long long *tab = reinterpret_cast<unsigned long long *>(pack.data());
+        size_t at = ni * 24;
+        for (size_t k = 0; k < ni; k++) {
+            const resident::Interval &iv = r->pending.v[k];
+            tab[3 * k] = iv.lo, tab[3 * k + 1] = at, tab[3 * k + 2] = iv.hi - iv.lo;
+            memcpy(pack.data() + at, (const char *)r->base + iv.lo, iv.hi - iv.lo);
+            at += iv.hi - iv.lo;
+        }
+        void *blk;
+        int rc = res_scratch(r->device, &blk);
+        if (rc || (rc = raw_h2d(blk, pack.data(), pack.size()))) return rc;
+        hipLaunchKernelGGL(k_patch, dim3((unsigned)ni), dim3(256), 0, 0, (uint8_t *)r->mirror, (const uint8_t *)blk);
+        IVX_LAUNCH_CHECK();
+        IVX_HIP(hipStreamSynchronize(nullptr));
+        r->stats[resident::ST_REFRESHES] += ni;
+        r->stats[resident::ST_REFRESH_BYTES] += nb;
+        r->pending.clear();
+        return IVX_OK;
+    }
+    for (const resident::Interval &iv : r->pending.v) {
+        int rc = raw_h2d((char *)r->mirror + iv.lo, (const char *)r->base + iv.lo, iv.hi - iv.lo);
+        if (rc) return rc;
+        r->stats[resident::ST_REFRESHES]++;
+        r->stats[resident::ST_REFRESH_BYTES] += iv.hi - iv.lo;
+    }
+    r->pending.clear();
+    return IVX_OK;
+}
+
+// IVX_RESIDENT_CHECK: host bytes [off, off + n) of the registration against the mirror (costs the upload the mirror saves)
+static int res_check(resident::Range *r, size_t off, size_t n) {
+    void *blk;
+    int rc = res_scratch(r->device, &blk);
+    if (rc) return rc;
+    unsigned long long *first = (unsigned long long *)((char *)blk + RES_CHK_CHUNK), none = ~0ull, got = ~0ull;
+    IVX_HIP(hipMemcpy(first, &none, 8, hipMemcpyHostToDevice));
+    const size_t lo = off & ~(size_t)15, hi = off + n; // (down to a 16-byte boundary of the mirror: still inside the range)
+    for (size_t at = lo; at < hi; at += RES_CHK_CHUNK) {
+        const size_t len = hi - at < RES_CHK_CHUNK ? hi - at : RES_CHK_CHUNK;
+        IVX_HIP(hipMemcpy(blk, (const char *)r->base + at, len, hipMemcpyHostToDevice));
+        g_xfer[2].fetch_add(len, std::memory_order_relaxed);
+        hipLaunchKernelGGL(k_bytes_differ, dim3((unsigned)cdiv((int64_t)cdiv((int64_t)len, 16), 256)), dim3(256), 0, 0,
+                           (const uint8_t *)blk, (const uint8_t *)r->mirror + at, len, (unsigned long long)at, first);
+        IVX_LAUNCH_CHECK();
+        IVX_HIP(hipStreamSynchronize(nullptr)); // the next chunk overwrites the block
+    }
+    IVX_HIP(hipMemcpy(&got, first, 8, hipMemcpyDeviceToHost));
+    if (got != ~0ull) {
+        set_error("IVX_ESTALE: the registered host array at %p (%zu bytes) differs from its device mirror, first at byte offset %llu: "
+                  "the host wrote it without ivx_host_touch", (void *)r->base, r->nbytes, got);
+        return IVX_ESTALE;
+    }
+    return IVX_OK;
+}
+
+// The registration of the current device that holds all of [lo, hi), with the registry lock held in `lk` for as long as the
+// caller works on the mirror; *out stays nullptr (and the lock is dropped) on a miss.  The host's pending writes are brought
+// in first; `reads`: the caller is going to read mirror bytes, so the stale check (when on) runs over them.
+static int res_acquire(uintptr_t lo, uintptr_t hi, bool reads, std::unique_lock<std::mutex> &lk, resident::Range **out) {
+    *out = nullptr;
+    lk = std::unique_lock<std::mutex>(g_res_mu);
+    int dev = 0;
+    IVX_HIP(hipGetDevice(&dev));
+    resident::Range *r = g_res.find_containing(lo, hi, dev);
+    if (!r) {
+        lk.unlock();
+        return IVX_OK;
+    }
+    int rc = res_refresh(r);
+    if (!rc && reads && res_check_on()) rc = res_check(r, lo - r->base, hi - lo);
+    if (rc) return rc;
+    *out = r;
+    return IVX_OK;
+}
+
+// the library wrote host bytes [lo, hi) that no mirror received: the registrations they overlap are stale there
+static void res_invalidate(uintptr_t lo, uintptr_t hi) {
+    std::lock_guard<std::mutex> lk(g_res_mu);
+    g_res.invalidate(lo, hi);
+}
+
+static bool res_aligned(const resident::Range *r, const void *p, const int64_t st[3], size_t isz) {
+    const int64_t m = (int64_t)isz;
+    return ((uintptr_t)p - r->base) % isz == 0 && st[0] % m == 0 && st[1] % m == 0 && st[2] % m == 0;
+}
+
+int copy_h2d(void *dst_dev, const void *src, size_t n) {
+    if (!n) return IVX_OK;
+    if (g_res_count.load(std::memory_order_acquire)) {
+        std::unique_lock<std::mutex> lk;
+        resident::Range *r;
+        int rc = res_acquire((uintptr_t)src, (uintptr_t)src + n, true, lk, &r);
+        if (rc) return rc;
+        if (r) {
+            IVX_HIP(hipMemcpyAsync(dst_dev, (const char *)r->mirror + ((uintptr_t)src - r->base), n, hipMemcpyDeviceToDevice, nullptr));
+            IVX_HIP(hipStreamSynchronize(nullptr));
+            r->stats[resident::ST_HITS]++;
+            r->stats[resident::ST_HIT_BYTES] += n;
+            g_xfer[3].fetch_add(n, std::memory_order_relaxed);
+            return IVX_OK;
+        }
+    }
+    return raw_h2d(dst_dev, src, n);
+}
+
+int copy_d2h(void *dst, const void *src_dev, size_t n) {
+    if (!n) return IVX_OK;
+    int rc = raw_d2h(dst, src_dev, n); // the host copy is the authoritative one, whatever happens to the mirror
+    if (rc || !g_res_count.load(std::memory_order_acquire)) return rc;
+    std::unique_lock<std::mutex> lk;
+    resident::Range *r;
+    if ((rc = res_acquire((uintptr_t)dst, (uintptr_t)dst + n, false, lk, &r))) return rc;
+    if (!r) {
+        res_invalidate((uintptr_t)dst, (uintptr_t)dst + n);
+        return IVX_OK;
+    }
+    IVX_HIP(hipMemcpyAsync((char *)r->mirror + ((uintptr_t)dst - r->base), src_dev, n, hipMemcpyDeviceToDevice, nullptr));
+    IVX_HIP(hipStreamSynchronize(nullptr));
+    r->stats[resident::ST_WRITES]++;
+    r->stats[resident::ST_WRITE_BYTES] += n;
+    return IVX_OK;
+}
+
+// upload_strided from a registered view: k_repitch for rows of 16 bytes and more, the general gather for everything else
+static int res_upload_view(void *dst_dev, const void *src, const int64_t shape[3], const int64_t st[3], size_t isz, bool *served) {
+    *served = false;
+    uintptr_t lo, hi;
+    if (!resident::view_extent((uintptr_t)src, shape, st, 3, isz, &lo, &hi)) return IVX_OK;
+    std::unique_lock<std::mutex> lk;
+    resident::Range *r;
+    int rc = res_acquire(lo, hi, true, lk, &r);
+    if (rc || !r) return rc;
+    if (!res_aligned(r, src, st, isz)) return IVX_OK;
+    uint8_t *m = (uint8_t *)r->mirror + ((uintptr_t)src - r->base);
+    const int64_t row = shape[2] * (int64_t)isz;
+    if (st[2] == (int64_t)isz && row >= 16) {
+        const int64_t chunks = (row + 15) / 16;
+        hipLaunchKernelGGL(k_repitch<false>, dim3((unsigned)cdiv(shape[0] * shape[1] * chunks, 256)), dim3(256), 0, 0, m, st[0], st[1],
+                           (uint8_t *)dst_dev, shape[0], shape[1], row);
+        IVX_LAUNCH_CHECK();
+    } else if ((rc = view_xfer<false>(m, st, dst_dev, shape, isz)))
+        return rc;
+    IVX_HIP(hipStreamSynchronize(nullptr));
+    const size_t n = (size_t)shape[0] * shape[1] * row;
+    r->stats[resident::ST_HITS]++;
+    r->stats[resident::ST_HIT_BYTES] += n;
+    g_xfer[3].fetch_add(n, std::memory_order_relaxed);
+    *served = true;
+    return IVX_OK;
+}
+
+// download_strided's span path into a registered parent: the result is scattered into the mirror itself (which holds the
+// bytes between the view's rows, so nothing is fetched from the host) and the span goes to the host from there
+static int res_download_span(void *dst, const int64_t shape[3], const int64_t st[3], const void *src_dev, size_t isz, size_t span, bool *served) {
+    *served = false;
+    std::unique_lock<std::mutex> lk;
+    resident::Range *r;
+    int rc = res_acquire((uintptr_t)dst, (uintptr_t)dst + span, true, lk, &r);
+    if (rc || !r) return rc;
+    uint8_t *m = (uint8_t *)r->mirror + ((uintptr_t)dst - r->base);
+    const int64_t row = shape[2] * (int64_t)isz, chunks = (row + 15) / 16;
+    hipLaunchKernelGGL(k_repitch<true>, dim3((unsigned)cdiv(shape[0] * shape[1] * chunks, 256)), dim3(256), 0, 0, m, st[0], st[1],
+                       (uint8_t *)const_cast<void *>(src_dev), shape[0], shape[1], row);
+    IVX_LAUNCH_CHECK();
+    IVX_HIP(hipStreamSynchronize(nullptr));
+    if ((rc = raw_d2h(dst, m, span))) return rc;
+    r->stats[resident::ST_WRITES]++;
+    r->stats[resident::ST_WRITE_BYTES] += (size_t)shape[0] * shape[1] * row;
+    *served = true;
+    return IVX_OK;
+}
+
+// after download_strided's host scatter: the same bytes into the mirror (general scatter), or the overlap marked stale
+static int res_after_view_write(void *dst, const int64_t shape[3], const int64_t st[3], const void *src_dev, size_t isz) {
+    uintptr_t lo, hi;
+    if (!resident::view_extent((uintptr_t)dst, shape, st, 3, isz, &lo, &hi)) return IVX_OK;
+    std::unique_lock<std::mutex> lk;
+    resident::Range *r;
+    int rc = res_acquire(lo, hi, false, lk, &r);
+    if (rc) return rc;
+    if (r && res_aligned(r, dst, st, isz)) {
+        if ((rc = view_xfer<true>((uint8_t *)r->mirror + ((uintptr_t)dst - r->base), st, const_cast<void *>(src_dev), shape, isz))) return rc;
+        IVX_HIP(hipStreamSynchronize(nullptr));
+        r->stats[resident::ST_WRITES]++;
+        r->stats[resident::ST_WRITE_BYTES] += (size_t)shape[0] * shape[1] * shape[2] * isz;
+        return IVX_OK;
+    }
+    if (r) g_res.invalidate(lo, hi); // (a misaligned view: the lock is still held)
+    else
+        res_invalidate(lo, hi);
+    return IVX_OK;
+}
+
 // rows gathered / scattered by a few host threads (views that are not sub-boxes of a contiguous parent)
 template <typename F> static void rows_parallel(int64_t nrows, F f) {
     const int nt = nrows > 4096 ? 4 : 1;
@@ -383,26 +724,10 @@ template <typename F> static void rows_parallel(int64_t nrows, F f) {
     for (auto &t : th) t.join();
 }
 
-int upload_strided(void *dst_dev, const void *src, const int64_t shape[3], const int64_t st[3], size_t isz,
-                   int hslot) {
+// a view gathered row by row on the host into page-locked staging, then one copy (views that are not sub-boxes of a
+// contiguous parent; short rows)
+static int upload_rows(void *dst_dev, const void *src, const int64_t shape[3], const int64_t st[3], size_t isz, int hslot) {
     const size_t n = (size_t)shape[0] * shape[1] * shape[2] * isz;
-    if (n == 0) return IVX_OK;
-    if (dense3(shape, st, isz)) return copy_h2d(dst_dev, src, n);
-    size_t span = 0;
-    if (hslot >= 0 && hslot < WS_COUNT && span_of(shape, st, isz, &span)) {
-        SpanSlot *sp;
-        int rc = span_buffer(hslot, span, &sp);
-        if (rc) return rc;
-        if ((rc = copy_h2d(sp->d, src, span))) return rc;
-        sp->host = src;
-        sp->nbytes = span;
-        sp->epoch = g_host_depth > 0 ? g_host_epoch : 0;
-        const int64_t row = shape[2] * (int64_t)isz, chunks = (row + 15) / 16;
-        hipLaunchKernelGGL(k_repitch<false>, dim3((unsigned)cdiv(shape[0] * shape[1] * chunks, 256)), dim3(256), 0, 0,
-                           (uint8_t *)sp->d, st[0], st[1], (uint8_t *)dst_dev, shape[0], shape[1], row);
-        IVX_LAUNCH_CHECK();
-        return IVX_OK;
-    }
     void *h;
     int rc = hs_get(hslot, n, &h);
     if (rc) return rc;
@@ -421,7 +746,56 @@ int upload_strided(void *dst_dev, const void *src, const int64_t shape[3], const
         }
     });
     IVX_HIP(hipMemcpy(dst_dev, h, n, hipMemcpyHostToDevice));
+    g_xfer[0].fetch_add(n, std::memory_order_relaxed);
     return IVX_OK;
+}
+
+int upload_strided(void *dst_dev, const void *src, const int64_t shape[3], const int64_t st[3], size_t isz,
+                   int hslot) {
+    const size_t n = (size_t)shape[0] * shape[1] * shape[2] * isz;
+    if (n == 0) return IVX_OK;
+    if (dense3(shape, st, isz)) return copy_h2d(dst_dev, src, n);
+    if (g_res_count.load(std::memory_order_acquire)) {
+        bool served = false;
+        int rc = res_upload_view(dst_dev, src, shape, st, isz, &served);
+        if (rc || served) return rc;
+    }
+    size_t span = 0;
+    if (hslot >= 0 && hslot < WS_COUNT && span_of(shape, st, isz, &span)) {
+        SpanSlot *sp;
+        int rc = span_buffer(hslot, span, &sp);
+        if (rc) return rc;
+        if ((rc = raw_h2d(sp->d, src, span))) return rc;
+        sp->host = src;
+        sp->nbytes = span;
+        sp->epoch = g_host_depth > 0 ? g_host_epoch : 0;
+        const int64_t row = shape[2] * (int64_t)isz, chunks = (row + 15) / 16;
+        hipLaunchKernelGGL(k_repitch<false>, dim3((unsigned)cdiv(shape[0] * shape[1] * chunks, 256)), dim3(256), 0, 0,
+                           (uint8_t *)sp->d, st[0], st[1], (uint8_t *)dst_dev, shape[0], shape[1], row);
+        IVX_LAUNCH_CHECK();
+        return IVX_OK;
+    }
+    return upload_rows(dst_dev, src, shape, st, isz, hslot);
+}
+
+// The library wrote the host view itself with the CPU (flag cells): the same values into the mirror, when there is one --
+// gathered from the host, uploaded (exactly the view's bytes) into the caller's `d_scratch` and scattered from there.
+int mirror_host_view(const void *view, const int64_t shape[3], const int64_t st[3], size_t isz, void *d_scratch, int hslot) {
+    if (!g_res_count.load(std::memory_order_acquire) || shape[0] * shape[1] * shape[2] == 0) return IVX_OK;
+    {
+        uintptr_t lo, hi;
+        if (!resident::view_extent((uintptr_t)view, shape, st, 3, isz, &lo, &hi)) return IVX_OK;
+        std::lock_guard<std::mutex> lk(g_res_mu);
+        int dev = 0;
+        IVX_HIP(hipGetDevice(&dev));
+        if (!g_res.find_containing(lo, hi, dev)) { // nothing to keep in step, or only an overlap: stale there
+            g_res.invalidate(lo, hi);
+            return IVX_OK;
+        }
+    }
+    int rc = upload_rows(d_scratch, view, shape, st, isz, hslot);
+    if (rc) return rc;
+    return res_after_view_write(const_cast<void *>(view), shape, st, d_scratch, isz);
 }
 
 int download_strided(void *dst, const int64_t shape[3], const int64_t st[3], const void *src_dev, size_t isz,
@@ -429,13 +803,19 @@ int download_strided(void *dst, const int64_t shape[3], const int64_t st[3], con
     const size_t n = (size_t)shape[0] * shape[1] * shape[2] * isz;
     if (n == 0) return IVX_OK;
     if (dense3(shape, st, isz)) return copy_d2h(dst, src_dev, n);
+    const bool res = g_res_count.load(std::memory_order_acquire) != 0;
     size_t span = 0;
     if (hslot >= 0 && hslot < WS_COUNT && span_of(shape, st, isz, &span)) {
+        if (res) {
+            bool served = false;
+            int rc = res_download_span(dst, shape, st, src_dev, isz, span, &served);
+            if (rc || served) return rc;
+        }
         SpanSlot *sp;
         int rc = span_buffer(hslot, span, &sp);
         if (rc) return rc;
         const bool fresh = sp->host == dst && sp->nbytes == span && sp->epoch != 0 && sp->epoch == g_host_epoch && g_host_depth > 0;
-        if (!fresh && (rc = copy_h2d(sp->d, dst, span))) return rc; // the bytes between the view's rows
+        if (!fresh && (rc = raw_h2d(sp->d, dst, span))) return rc; // the bytes between the view's rows
         const int64_t row = shape[2] * (int64_t)isz, chunks = (row + 15) / 16;
         hipLaunchKernelGGL(k_repitch<true>, dim3((unsigned)cdiv(shape[0] * shape[1] * chunks, 256)), dim3(256), 0, 0,
                            (uint8_t *)sp->d, st[0], st[1], (uint8_t *)const_cast<void *>(src_dev), shape[0], shape[1], row);
@@ -449,6 +829,7 @@ int download_strided(void *dst, const int64_t shape[3], const int64_t st[3], con
     int rc = hs_get(hslot, n, &h);
     if (rc) return rc;
     IVX_HIP(hipMemcpy(h, src_dev, n, hipMemcpyDeviceToHost));
+    g_xfer[1].fetch_add(n, std::memory_order_relaxed);
     const char *s = (const char *)h;
     char *d = (char *)dst;
     const size_t row = (size_t)shape[2] * isz;
@@ -463,6 +844,7 @@ int download_strided(void *dst, const int64_t shape[3], const int64_t st[3], con
                 for (int64_t x = 0; x < nx; x++) memcpy(dp + x * st[2], sp + x * isz, isz);
         }
     });
+    if (res) return res_after_view_write(dst, shape, st, src_dev, isz);
     return IVX_OK;
 }
 
@@ -684,6 +1066,101 @@ int ivx_memset(void *dptr, int value, size_t nbytes, void *stream) {
 // (pageable host memory of >= 4 MB travels through the page-locked lane buffers above; IVX_STAGE_THREADS=0: plain hipMemcpy)
 int ivx_memcpy_h2d(void *dst, const void *src, size_t nbytes) { return copy_h2d(dst, src, nbytes); }
 int ivx_memcpy_d2h(void *dst, const void *src, size_t nbytes) { return copy_d2h(dst, src, nbytes); }
+// a 3-D host view (signed byte strides) <-> a dense device block: what every host-level entry point does with its arrays
+int ivx_upload_strided(void *dst, const void *src, const int64_t shape[3], const int64_t strides[3], size_t itemsize) {
+    IVX_REQUIRE(dst && src && shape && strides, IVX_EINVAL, "ivx_upload_strided: null");
+    IVX_REQUIRE(itemsize == 1 || itemsize == 2 || itemsize == 4 || itemsize == 8, IVX_EINVAL, "ivx_upload_strided: item size %zu", itemsize);
+    IVX_REQUIRE(shape[0] >= 0 && shape[1] >= 0 && shape[2] >= 0, IVX_EINVAL, "ivx_upload_strided: negative shape");
+    HostCallGuard g; // (the staging blocks are the host-level entry points')
+    int rc = upload_strided(dst, src, shape, strides, itemsize, WS_IN);
+    if (rc) return rc;
+    // upload_strided leaves a sub-box's re-pitch kernel on the null stream, which is enough for the host-level entry points (they
+    // go on working there); this call's users launch on their own non-blocking streams next, so the block must be complete now
+    IVX_HIP(hipStreamSynchronize(nullptr));
+    return IVX_OK;
+}
+int ivx_download_strided(void *dst, const int64_t shape[3], const int64_t strides[3], const void *src, size_t itemsize) {
+    IVX_REQUIRE(dst && src && shape && strides, IVX_EINVAL, "ivx_download_strided: null");
+    IVX_REQUIRE(itemsize == 1 || itemsize == 2 || itemsize == 4 || itemsize == 8, IVX_EINVAL, "ivx_download_strided: item size %zu", itemsize);
+    IVX_REQUIRE(shape[0] >= 0 && shape[1] >= 0 && shape[2] >= 0, IVX_EINVAL, "ivx_download_strided: negative shape");
+    HostCallGuard g;
+    return download_strided(dst, shape, strides, src, itemsize, WS_OUT);
+}
+
+// ---- resident host arrays: the registry's public face (include/ivx.h) ----
+int ivx_host_register(const void *base, size_t nbytes, uint64_t *handle) {
+    IVX_REQUIRE(base && nbytes && handle, IVX_EINVAL, "ivx_host_register: null or empty range");
+    std::lock_guard<std::mutex> lk(g_res_mu);
+    int dev = 0;
+    IVX_HIP(hipGetDevice(&dev));
+    uint64_t h = 0;
+    IVX_REQUIRE(g_res.add((uintptr_t)base, nbytes, dev, &h) == resident::RES_OK, IVX_EINVAL,
+                "ivx_host_register: [%p, +%zu) overlaps a registered range", base, nbytes);
+    resident::Range *r = g_res.get(h);
+    hipError_t e = hipMalloc(&r->mirror, nbytes);
+    int rc = IVX_OK;
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("ivx_host_register: no device memory for a mirror of %zu bytes (%s)", nbytes, hipGetErrorString(e));
+        rc = e == hipErrorOutOfMemory ? IVX_ENOMEM : IVX_EHIP;
+    } else if ((rc = raw_h2d(r->mirror, base, nbytes)))
+        (void)hipFree(r->mirror);
+    if (rc) {
+        g_res.release(h);
+        return rc;
+    }
+    g_res_count.store(g_res.count(), std::memory_order_release);
+    *handle = h;
+    return IVX_OK;
+}
+int ivx_host_touch_range(uint64_t handle, size_t offset, size_t nbytes) {
+    std::lock_guard<std::mutex> lk(g_res_mu);
+    IVX_REQUIRE(g_res.get(handle), IVX_EINVAL, "ivx_host_touch: handle %llu is released or was never given out", (unsigned long long)handle);
+    IVX_REQUIRE(g_res.touch(handle, offset, nbytes) == resident::RES_OK, IVX_EINVAL,
+                "ivx_host_touch: [%zu, +%zu) leaves the registered range of %zu bytes", offset, nbytes, g_res.get(handle)->nbytes);
+    return IVX_OK;
+}
+int ivx_host_touch(uint64_t handle) {
+    size_t n = 0;
+    {
+        std::lock_guard<std::mutex> lk(g_res_mu);
+        resident::Range *r = g_res.get(handle);
+        IVX_REQUIRE(r, IVX_EINVAL, "ivx_host_touch: handle %llu is released or was never given out", (unsigned long long)handle);
+        n = r->nbytes;
+    }
+    return ivx_host_touch_range(handle, 0, n);
+}
+int ivx_host_release(uint64_t handle) {
+    std::lock_guard<std::mutex> lk(g_res_mu); // (held by every copy that uses a mirror: this waits for it)
+    resident::Range *r = g_res.get(handle);
+    IVX_REQUIRE(r, IVX_EINVAL, "ivx_host_release: handle %llu is released or was never given out", (unsigned long long)handle);
+    if (r->mirror) (void)hipFree(r->mirror);
+    g_res.release(handle);
+    g_res_count.store(g_res.count(), std::memory_order_release);
+    return IVX_OK;
+}
+int ivx_host_stats(uint64_t handle, uint64_t out[8]) {
+    std::lock_guard<std::mutex> lk(g_res_mu);
+    resident::Range *r = g_res.get(handle);
+    IVX_REQUIRE(r && out, IVX_EINVAL, "ivx_host_stats: handle %llu is released or was never given out", (unsigned long long)handle);
+    for (int i = 0; i < 8; i++) out[i] = r->stats[i];
+    return IVX_OK;
+}
+int ivx_host_count(uint64_t *count) {
+    IVX_REQUIRE(count, IVX_EINVAL, "ivx_host_count: null");
+    std::lock_guard<std::mutex> lk(g_res_mu);
+    *count = g_res.count();
+    return IVX_OK;
+}
+int ivx_host_set_check(int on) {
+    g_res_check.store(on ? 1 : 0, std::memory_order_relaxed);
+    return IVX_OK;
+}
+int ivx_transfer_stats(uint64_t out[4]) {
+    IVX_REQUIRE(out, IVX_EINVAL, "ivx_transfer_stats: null");
+    for (int i = 0; i < 4; i++) out[i] = g_xfer[i].load(std::memory_order_relaxed);
+    return IVX_OK;
+}
 // Page-locked host memory for callers that keep their arrays where the DMA engines can reach them directly: a pageable
 // numpy array crosses PCIe through the runtime's bounce buffers (~25-40 GB/s here), a pinned one at the link's rate.
 int ivx_host_alloc(void **hptr, size_t nbytes) {
@@ -788,6 +1265,12 @@ int ivx_event_elapsed_ms(void *start, void *stop, float *ms) {
     return IVX_OK;
 }
 int ivx_release_workspace(void) {
+    {
+        std::lock_guard<std::mutex> rk(g_res_mu); // the stale check's staging blocks (the mirrors stay: they are not workspace)
+        for (auto &kv : g_res_chk)
+            if (kv.second) (void)hipFree(kv.second);
+        g_res_chk.clear();
+    }
     std::lock_guard<std::mutex> lk(g_mu);
     for (int i = 0; i < WS_COUNT; i++) {
         if (g_ws[i].p) (void)hipFree(g_ws[i].p);

@@ -176,5 +176,6 @@ extern "C" int ivx_threshold_all_slices(const int16_t *img, const int64_t shape[
     IVX_HIP(hipDeviceSynchronize());
     if ((rc = download_strided(inner, shape, mst, d_mask, 1, WS_OUT))) return rc;
     for (int64_t z = 0; z < dz; z++) mask[(z + 1) * mst[0]] = honour_flags && hf[z] ? hf[z] : 1; // slice_.py:1767, 1247
-    return IVX_OK;
+    const int64_t fshape[3] = {1, 1, dz}, fst[3] = {0, 0, mst[0]}; // (a resident matrix gets the flag cells in its mirror too)
+    return mirror_host_view(mask + mst[0], fshape, fst, 1, d_flags, WS_SMALL);
 }

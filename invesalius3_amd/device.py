@@ -29,6 +29,32 @@ class DeviceBuffer:
         assert a.nbytes <= self.nbytes
         L.check(L.lib().ivx_memcpy_h2d(self.ptr, L.ptr(a), ctypes.c_size_t(a.nbytes)))
 
+    def upload_view(self, a: np.ndarray):
+        """upload() of a view as it stands -- `matrix[1:, 1:, 1:]`, a slab, a reversed or stepped axis -- without the host
+        copy np.ascontiguousarray would make: the library walks the strides (ivx_upload_strided), and a view of an array
+        bound with resident.bind comes out of its mirror in HBM.  More than three axes, or items that are not 1 / 2 / 4 / 8
+        bytes, take the copy."""
+        a = np.asarray(a)
+        if a.ndim > 3 or a.itemsize not in (1, 2, 4, 8) or a.ndim == 0:
+            return self.upload(a)
+        assert a.nbytes <= self.nbytes
+        pad = 3 - a.ndim  # (leading axes of length 1, with the stride a dense array would have there)
+        L.check(L.lib().ivx_upload_strided(self.ptr, L.ptr(a), L.i64((1,) * pad + a.shape),
+                                           L.i64((a.strides[0] * a.shape[0],) * pad + a.strides), a.itemsize), "upload_view")
+
+    def download_view(self, out: np.ndarray):
+        """the block's leading bytes into the view `out` (same rules as upload_view); the bytes of `out`'s parent between
+        the view's elements are left as they are"""
+        if out.ndim > 3 or out.itemsize not in (1, 2, 4, 8) or out.ndim == 0:
+            out[...] = self.download(out.shape, out.dtype)
+            return out
+        assert out.nbytes <= self.nbytes
+        pad = 3 - out.ndim
+        L.check(L.lib().ivx_download_strided(L.ptr(out), L.i64((1,) * pad + out.shape),
+                                             L.i64((out.strides[0] * out.shape[0],) * pad + out.strides), self.ptr, out.itemsize),
+                "download_view")
+        return out
+
     def download(self, shape, dtype, out: np.ndarray | None = None) -> np.ndarray:
         """`out`: a C-contiguous array with room for the result (e.g. `_lib.pinned_empty`); a view of it is returned"""
         if out is None:
@@ -197,7 +223,7 @@ class DeviceVolume:
         self.mask = TrackedBuffer(self.n, self._mask_touched)       # dense interior of mask.matrix[1:,1:,1:]
         self.out_mask = TrackedBuffer(self.n, self._out_touched)    # region-growing `out` (styles.py:3190)
         if image is not None:
-            self.image.upload(image)
+            self.image.upload_view(image)
         self.mask.zero(self.stream)
         self.zero_out_mask()
         # region growing bit planes + tile work-list

@@ -25,6 +25,7 @@ import numpy as np
 
 from . import _lib as L
 from . import project as prj
+from . import resident
 from . import surface_process as sp
 from .device import DeviceVolume, c64
 
@@ -39,7 +40,8 @@ def run(args) -> dict:
     out = {"project": proj.name, "shape": list(proj.matrix_shape), "spacing": list(proj.spacing), "dtype": proj.matrix_dtype}
     if proj.matrix.dtype != np.int16:
         raise TypeError("the GPU path takes int16 volumes (found %s)" % proj.matrix.dtype)
-    vol = DeviceVolume(np.ascontiguousarray(proj.matrix), spacing=proj.spacing)
+    bound = [resident.bind(proj.matrix)]  # the project's image, and below the mask the run works on, for its length
+    vol = DeviceVolume(proj.matrix, spacing=proj.spacing)
     lib = L.lib()
     try:
         filtered = None
@@ -96,7 +98,8 @@ def run(args) -> dict:
             if args.mask not in proj.masks:
                 raise KeyError("project holds no mask %d (masks: %s)" % (args.mask, sorted(proj.masks)))
             rec = proj.masks[args.mask]
-            vol.mask.upload(np.ascontiguousarray(rec.interior))
+            bound.append(resident.bind(rec.matrix))
+            vol.mask.upload_view(rec.interior)
             lo, hi = rec.threshold_range
             out["mask"] = {"index": args.mask, "name": rec.name, "threshold_range": [lo, hi]}
         if args.seed:
@@ -199,6 +202,8 @@ def run(args) -> dict:
             shell.close()
     finally:
         vol.close()
+        for b in bound:
+            b.release()
         proj.close()
         out["wall_s"] = round(time.perf_counter() - t_all, 3)
     return out

@@ -10,6 +10,7 @@ import ctypes
 import numpy as np
 
 from . import _lib as L
+from . import resident
 
 CON2D = {4: 1, 8: 2}
 CON3D = {6: 1, 18: 2, 26: 3}
@@ -19,6 +20,13 @@ def _structure(rank: int, connectivity: int) -> np.ndarray:
     """scipy.ndimage.generate_binary_structure(rank, connectivity): offsets with at most `connectivity` non-zero axes."""
     grid = np.indices((3,) * rank) - 1
     return (np.abs(grid).sum(axis=0) <= connectivity).astype(np.uint8)
+
+
+def bind_matrix(matrix: np.ndarray) -> "resident.Resident":
+    """Keep a mask's padded matrix in HBM: call it where the reference creates it (Mask.create_mask,
+    invesalius/data/mask.py:422-431).  What the library writes into the matrix goes to the host and to the mirror alike; a
+    numpy write (the brush, ``matrix[:] = 0``) is followed by ``touch`` on the returned `Resident`."""
+    return resident.bind(matrix)
 
 
 def fill_holes_auto(matrix: np.ndarray, target: str, conn: int, orientation: str, index: int, size: int) -> bool:

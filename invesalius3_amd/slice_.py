@@ -13,8 +13,16 @@ import math
 import numpy as np
 
 from . import _lib as L
+from . import resident
 
 PROJECTION_NORMAL, PROJECTION_MaxIP, PROJECTION_MinIP, PROJECTION_MeanIP = 0, 1, 2, 3  # invesalius/constants.py:803-806
+
+
+def bind_image(matrix: np.ndarray) -> "resident.Resident":
+    """Keep the project's image in HBM: call it where the reference sets ``Slice.matrix`` (invesalius/data/slice_.py:175-188).
+    Every entry point of this package that is then handed `matrix`, a slab or any other view of it uploads nothing; whoever
+    writes the array with numpy calls ``touch`` on the returned `Resident` (resident.py, INTEGRATION.md "Resident arrays")."""
+    return resident.bind(matrix)
 
 
 def _int_bounds(threshold_range):
@@ -199,6 +207,7 @@ def apply_reorientation(matrix: np.ndarray, spacing, q_orientation, center, inte
             del mask_copy
         else:
             mm[:] = 0
+            resident.touch(mm)
         if hasattr(mm, "flush"):
             mm.flush()
         if hasattr(mask, "clear_history"):

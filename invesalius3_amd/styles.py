@@ -10,6 +10,7 @@ import ctypes
 import numpy as np
 
 from . import _lib as L
+from . import resident
 from . import slice_ as sl
 from .device import DeviceVolume
 from .mask import CON3D, _structure
@@ -33,7 +34,7 @@ def do_3d_seg(image: np.ndarray, mask_matrix: np.ndarray, seed_xyz, method: str 
     if not (0 <= z < image.shape[0] and 0 <= y < image.shape[1] and 0 <= x < image.shape[2]):
         raise IndexError("seed outside the volume")
     strct = _structure(3, CON3D[con_3d])
-    with DeviceVolume(np.ascontiguousarray(image)) as vol:
+    with DeviceVolume(image) as vol:
         flood_image = None
         if use_ww_wl and method in ("dynamic", "confidence"):
             flood_image = vol.lut_image_255(ww, wl)  # get_LUT_value_255(image, ww, wl), int16
@@ -56,7 +57,7 @@ def do_3d_seg(image: np.ndarray, mask_matrix: np.ndarray, seed_xyz, method: str 
                 return False
         if threshold_range is not None:
             sl.do_threshold_to_all_slices(mask_matrix, image, threshold_range)
-        vol.mask.upload(np.ascontiguousarray(mask_matrix[1:, 1:, 1:]))
+        vol.mask.upload_view(mask_matrix[1:, 1:, 1:])
         vol.zero_out_mask()
         if method == "confidence":
             vol.region_grow_confidence((x, y, z), strct, confid_mult, confid_iters, select_value=int(fill_value),
@@ -64,6 +65,7 @@ def do_3d_seg(image: np.ndarray, mask_matrix: np.ndarray, seed_xyz, method: str 
         else:
             vol.region_grow([(x, y, z)], lo, hi, strct, fill=1, select_value=int(fill_value), image=flood_image)
         mask_matrix[1:, 1:, 1:] = vol.download_mask()
+        resident.touch(mask_matrix[1:, 1:, 1:])
         if flood_image is not None:
             flood_image.close()
     return True
@@ -141,6 +143,7 @@ def watershed_brush_release(image_matrix: np.ndarray, mask_matrix: np.ndarray, m
     if orientation == "AXIAL":
         image, mask, markers = image_matrix[n], mask_matrix[n + 1, 1:, 1:], markers_matrix[n]
         mask_matrix[n + 1, 0, 0] = 1
+        resident.touch(mask_matrix[n + 1, :1, :1])
     elif orientation == "CORONAL":
         image, mask, markers = image_matrix[:, n, :], mask_matrix[1:, n + 1, 1:], markers_matrix[:, n, :]
     elif orientation == "SAGITAL":
@@ -162,4 +165,5 @@ def watershed_brush_release(image_matrix: np.ndarray, mask_matrix: np.ndarray, m
     m2 = np.ascontiguousarray(mask)
     wp.merge(m2, tmp, bool(overwrite))
     mask[...] = m2
+    resident.touch(mask)
     return True

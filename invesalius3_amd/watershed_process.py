@@ -18,6 +18,7 @@ import numpy as np
 import warnings
 
 from . import _lib as L
+from . import resident
 
 
 class MarkerTieWarning(UserWarning):
@@ -245,6 +246,7 @@ def do_watershed(image, markers, tfile, shape, bstruct, algorithm, mg_size, use_
     _mark("ivx_do_watershed_into")
     if not direct:
         mask[:] = dst.reshape(image.shape)
+        resident.touch(mask)
     t_flush = time.perf_counter()
     mask.flush()  # (watershed_process.py:59: an msync of the label volume -- the reference's own cost, 20 - 35 ms at 512^3 on a disk-backed file)
     do_watershed.last_flush_ms = (time.perf_counter() - t_flush) * 1e3

@@ -21,6 +21,7 @@ cp $O/pmc_traffic.json profiles/ 2>/dev/null  # (so that the line below quotes i
 timeout -k 5 900 python bench.py --full < /dev/null > $O/bench.json 2> $O/bench.err
 timeout -k 5 300 python bench.py --full --scaling strong --no-others --no-cpu < /dev/null > $O/bench_strong_1gpu.json 2> $O/bench_strong_1gpu.err
 timeout -k 5 600 python tools/bench_host.py < /dev/null > $O/bench_host_512.json 2> $O/bench_host_512.err
+timeout -k 5 600 python tools/bench_resident.py < /dev/null > $O/bench_host_resident_512.json 2> $O/bench_host_resident_512.err  # the same calls with the arrays bound
 # the opt-in paths kept for A/B: marching cubes in one launch, the IFT level chain without link records
 IVX_MC_ONE_LAUNCH=1 timeout -k 5 300 python bench.py --full --no-others --no-cpu < /dev/null > $O/bench_mc_one_launch.json 2> /dev/null
 IVX_WS_LINKS=0 timeout -k 5 300 python bench.py --full --config watershed --size 512 --no-cpu < /dev/null > $O/bench_watershed_512_nolinks.json 2> /dev/null
