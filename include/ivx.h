@@ -253,6 +253,9 @@ typedef struct ivx_mc_params {
 } ivx_mc_params;
 /* scratch needed by count/emit for this piece (bytes); pass a device buffer of that size */
 int ivx_dev_mc_scratch_bytes(const ivx_mc_params *p, size_t *nbytes);
+/* host only, for tests: slice k, cell row j and word-in-row w of n cell-word ids (word id = (k * (NY-1) + j) * WC + w of the
+ * padded cell grid), by the division-free arithmetic and the per-piece constants the count and list kernels use */
+int ivx_mc_split_word_ids(const ivx_mc_params *p, const uint32_t *wid, size_t n, uint32_t *k, uint32_t *j, uint32_t *w);
 /* classify + per-row-group triangle counts + scan; *ntris (host) receives the total */
 int ivx_dev_mc_count(const ivx_mc_params *p, const void *a, void *scratch, int64_t *ntris, void *stream);
 /* Queue-only forms: nothing comes back to the host, so ivx_dev_mc_emit can be queued right behind them with the

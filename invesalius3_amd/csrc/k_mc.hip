@@ -14,14 +14,19 @@
 //                    when the words are read (funnel shift by one bit, constant pad rows), never stored.
 //   2. k_mc_count    one lane per 64-cell word: four row words (+ the carry bit of the next word) give the
 //                    active-cell mask with a handful of 64-bit ops; only active cells look up the case table.
-//                    Per-word triangle counts (u16) + per-workgroup sums.
-//   3. k_mc_scan     exclusive scan of the per-workgroup sums (u64 offsets), one workgroup per 16 384 sums.
-//   4. k_mc_emit     one workgroup per 256 words.  Corner words + a block scan of the counts go to LDS; then the
-//                    workgroup walks its TRIANGLES 256 at a time, one lane per triangle (binary search of the
-//                    owning word in LDS, short walk over that word's active cells), so lanes stay busy however
-//                    unevenly the surface is spread.  The 9 floats of each triangle are staged in LDS
-//                    (stride 9 dwords: conflict-free) and leave as fully coalesced dword stores: HBM sees each
-//                    output line once.
+//                    Per-word triangle counts (u16) + per-workgroup sums.  The word id is split into (slice, row,
+//                    word) with per-piece magic multipliers (McDiv), and a wave whose rows are all source rows
+//                    takes load_corners' interior form (no clamps, no row tests, one row base per lane): 344 ->
+//                    177 VALU in front of the first barrier, 34.0 -> 27.4 us at 512^3.
+//   3. k_mc_scan     exclusive scan of the per-workgroup sums (u64 offsets), one workgroup per 16 384 sums,
+//                    consecutive lanes on consecutive sums (16-byte loads and stores): 11.4 -> 4.9 us.
+//   3b. k_mc_list    one 64-bit descriptor per triangle in output order, written by the lane that owns the cell
+//                    word; a workgroup whose slice of the scan is empty leaves at once.
+//   4. k_mc_emit     one lane per triangle of the list, 256 consecutive triangles per workgroup, so lanes stay
+//                    busy however unevenly the surface is spread.  The 9 floats of each triangle are staged in
+//                    LDS (stride 9 dwords: conflict-free) and leave as aligned 16-byte non-temporal stores: HBM
+//                    sees each output line once.
+// (What was measured for the passes in front of the emit, part by part: profiles/mc_front_end_ab.md.)
 // Output order == the oracle's (iso-major, then k, j, i raster order of cells), so parity is an array compare.
 // Vertex arithmetic is done in double and rounded once to float32, exactly like the oracle.
 #include <cmath>
@@ -39,6 +44,32 @@ typedef unsigned char uchar16_t __attribute__((ext_vector_type(16)));
 
 namespace {
 
+// Division of a 32-bit number by a divisor that is fixed for a launch (words per cell row, cell rows per slice), without a
+// division: Granlund & Montgomery, "Division by invariant integers using multiplication" (PLDI 1994), figure 4.1 with N = 32.
+// With l = ceil(log2 d), mul = floor(2^32 (2^l - d) / d) + 1, s1 = min(l, 1), s2 = max(l - 1, 0):
+//   t = floor(mul * n / 2^32),  n / d = (t + ((n - t) >> s1)) >> s2      for EVERY n < 2^32 and every 1 <= d < 2^32
+// (2^32 + mul = floor(2^(32+l) / d) + 1 is a 33-bit multiplier whose error stays below one part in 2^32; t <= n, so n - t does not
+// wrap, and t + ((n - t) >> s1) <= n.)  Cell-word ids are below 2^32 (checked where the kernels are queued), so both
+// divisions of a word id are exact; tests/test_gpu_mc_front_end.py checks the constants against integer division on the host.
+struct McDiv {
+    uint32_t d, mul, s1, s2;
+};
+static inline McDiv mc_div_make(uint32_t d) {
+    if (d == 0) d = 1; // (an empty grid: nothing is divided)
+    uint32_t l = 0;
+    while (l < 32 && (1ull << l) < d) l++;
+    McDiv m;
+    m.d = d;
+    m.mul = (uint32_t)((((1ull << l) - d) << 32) / d + 1ull);
+    m.s1 = l < 1 ? l : 1;
+    m.s2 = l > 0 ? l - 1 : 0;
+    return m;
+}
+__host__ __device__ __forceinline__ uint32_t mc_div(uint32_t n, const McDiv &m) {
+    const uint32_t t = (uint32_t)(((uint64_t)m.mul * n) >> 32);
+    return (t + ((n - t) >> m.s1)) >> m.s2;
+}
+
 struct Geom {
     int64_t nz, ny, nx;  // piece
     int64_t NZ, NY, NX;  // padded grid points
@@ -50,7 +81,15 @@ struct Geom {
     double padv;
     double sx, sy, sz;
     int64_t yoff, zoff;
+    McDiv div_wc, div_rows; // by WC and by NY - 1: cell-word id -> (slice, row, word in the row)
 };
+// cell word `wid` (< nwords < 2^32) -> slice k, cell row j, word w of the row
+__host__ __device__ __forceinline__ void mc_split_wid(const Geom &g, uint32_t wid, uint32_t &k, uint32_t &j, uint32_t &w) {
+    const uint32_t row = mc_div(wid, g.div_wc);
+    w = wid - row * g.div_wc.d;
+    k = mc_div(row, g.div_rows);
+    j = row - k * g.div_rows.d;
+}
 
 static int make_geom(const ivx_mc_params *p, Geom *g) {
     IVX_REQUIRE(p && p->nz >= 0 && p->ny >= 0 && p->nx >= 0, IVX_EINVAL, "mc: bad shape");
@@ -70,6 +109,8 @@ static int make_geom(const ivx_mc_params *p, Geom *g) {
     g->sx = p->spacing[0]; g->sy = p->spacing[1]; g->sz = p->spacing[2];
     g->yoff = g->NY - 1 - g->pxy;
     g->zoff = p->roi_start - p->vtk_pz;
+    g->div_wc = mc_div_make((uint32_t)g->WC);
+    g->div_rows = mc_div_make((uint32_t)(g->NY > 1 ? g->NY - 1 : 1));
     return IVX_OK;
 }
 
@@ -230,52 +271,107 @@ struct Corner8 {
     uint64_t c[8];
     uint64_t active;
 };
+// 64-bit funnel shifts by one bit as two 32-bit ones each (v_alignbit_b32, full rate)
+__device__ __forceinline__ uint64_t mc_shl1(uint64_t x, uint32_t below_hi) { // (x << 1) | bit 31 of below_hi
+    const uint32_t xl = (uint32_t)x, xh = (uint32_t)(x >> 32);
+    return ((uint64_t)__builtin_amdgcn_alignbit(xh, xl, 31) << 32) | __builtin_amdgcn_alignbit(xl, below_hi, 31);
+}
+__device__ __forceinline__ uint64_t mc_shr1(uint64_t x, uint32_t above) { // (x >> 1) | (bit 0 of above) << 63
+    const uint32_t xl = (uint32_t)x, xh = (uint32_t)(x >> 32);
+    return ((uint64_t)__builtin_amdgcn_alignbit(above, xh, 1) << 32) | __builtin_amdgcn_alignbit(xh, xl, 1);
+}
+__device__ __forceinline__ uint64_t mc_lowbits(int32_t n) { // the n lowest bits (n <= 0: none, n >= 64: all)
+    return n >= 64 ? ~0ull : (n <= 0 ? 0ull : ((1ull << n) - 1ull));
+}
 // The eight corner words of cell word (k, j, w).  Same view as padded_pair, specialised: of the following word only
 // bit 0 is ever needed (corner x+1 of cell 63), so each of the four rows costs two loads instead of three and one mask
 // instead of two, and the masks that depend only on w are computed once for all four rows.
+// Two forms, chosen per WAVE (all lanes that call together take the same one).  INTERIOR: the four rows of every lane's word are
+// source rows (ja - 1 >= 0, ja < ny, ka >= 0, ka + 1 < nz) -- all but the waves that touch a pad row or slice, 98 % of them at 512^3.
+// No row is clamped or tested, the eight addresses are one 64-bit row base per lane plus launch-wide row strides, and the pad
+// bits enter through two per-lane constants (pad columns and the carry bit).  The word-level tests (has_c / has_m / has_p) are
+// not needed either: wherever one of them would zero a loaded word, srcm or src1 already masks every bit that word supplies
+// (w >= ws gives top <= pxy, so srcm keeps at most bit 0, which comes from word w - 1; w - 1 >= ws or w == 0 clear that bit too;
+// src1 implies w + 1 < ws without the pad column and w < ws with it).  GENERIC: any row may be padding; as before.
 __device__ __forceinline__ Corner8 load_corners(const uint64_t *__restrict__ bits, const Geom &g, int64_t k,
                                                 int64_t j, int64_t w, uint64_t pbits) {
     Corner8 r;
     const auto clampi = [](int64_t v, int64_t n) { return v >= n ? (n > 0 ? n - 1 : 0) : (v < 0 ? 0 : v); };
-    const int64_t rem = g.NX - w * 64; // padded points in this word
-    const uint64_t exist = rem >= 64 ? ~0ull : (rem <= 0 ? 0ull : ((1ull << rem) - 1ull));
+    // (32-bit: NX <= 2^21 + 2, w < 2^15)
+    const int32_t w32 = (int32_t)w, NX32 = (int32_t)g.NX, nx32 = (int32_t)g.nx, ws32 = (int32_t)g.ws;
+    const uint64_t exist = mc_lowbits(NX32 - w32 * 64); // padded points in this word
     uint64_t srcm = exist; // ... of which backed by source voxels (when the row is a source row)
-    if (g.pxy && w == 0) srcm &= ~1ull;
-    const int64_t top = g.pxy + g.nx - w * 64;
-    srcm &= top >= 64 ? ~0ull : (top <= 0 ? 0ull : ((1ull << top) - 1ull));
-    const int64_t x1 = (w + 1) * 64;              // padded x of the next word's first point
-    const bool exist1 = x1 < g.NX;
-    const bool src1 = x1 - g.pxy < g.nx;          // (x1 - pxy >= 0 always)
-    const bool has_m = w - 1 >= 0 && w - 1 < g.ws, has_c = w < g.ws, has_p = w + 1 < g.ws;
-    const int64_t wm = clampi(w - 1, g.ws), wc = clampi(w, g.ws), wp = clampi(w + 1, g.ws);
-    uint64_t a0[4], a1[4];
-    bool rin[4];
+    if (g.pxy && w32 == 0) srcm &= ~1ull;
+    srcm &= mc_lowbits(g.pxy + nx32 - w32 * 64);
+    const int32_t x1 = (w32 + 1) * 64;            // padded x of the next word's first point
+    const bool exist1 = x1 < NX32;
+    const bool src1 = x1 - g.pxy < nx32;          // (x1 - pxy >= 0 always)
+    const int32_t wc = w32 >= ws32 ? (ws32 > 0 ? ws32 - 1 : 0) : w32; // word indices clamped into the row (0 for an empty row)
+    const int32_t wm = w32 - 1 >= ws32 ? (ws32 > 0 ? ws32 - 1 : 0) : (w32 - 1 < 0 ? 0 : w32 - 1);
+    const int32_t wp = w32 + 1 >= ws32 ? (ws32 > 0 ? ws32 - 1 : 0) : w32 + 1;
+    const int32_t ja0 = ((int32_t)g.NY - 1 - (int32_t)j) - g.pxy, ka0 = (int32_t)k - g.pb; // source row of corner (dy = 0, dz = 0)
+    const bool inner = ja0 - 1 >= 0 && ja0 < (int32_t)g.ny && ka0 >= 0 && ka0 + 1 < (int32_t)g.nz;
+    if (__all(inner)) {
+        const uint64_t padlo = pbits & exist & ~srcm;
+        const bool use1 = exist1 && src1;
+        const uint32_t nbpad = exist1 ? (uint32_t)pbits & 1u : 0u;
+        // row (ka0, ja0); row ja0 - 1 lies ws words below it, slice ka0 + 1 ny * ws words above (ka0 * ny + ja0 < 2^32)
+        const uint64_t *row = bits + (uint64_t)((uint32_t)ka0 * (uint32_t)g.ny + (uint32_t)ja0) * (uint64_t)(uint32_t)ws32;
+        const uint64_t *pc = row + wc, *pa = row + (g.pxy ? wm : wp);
+        const int64_t dj = -g.ws, dk = g.ny * g.ws;
+        uint64_t a0[4], a1[4];
 #pragma unroll
-    for (int q = 0; q < 4; q++) { // issue the eight loads back to back
-        const int64_t ja = (g.NY - 1 - (j + (q & 1))) - g.pxy, ka = k + (q >> 1) - g.pb;
-        rin[q] = ja >= 0 && ja < g.ny && ka >= 0 && ka < g.nz;
-        const uint64_t *row = bits + (clampi(ka, g.nz) * g.ny + clampi(ja, g.ny)) * g.ws;
-        a0[q] = row[wc];
-        a1[q] = g.pxy ? row[wm] : row[wp];
-    }
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const uint64_t sc = (rin[q] && has_c) ? a0[q] : 0ull;
-        uint64_t v0, raw1;
-        if (g.pxy) {
-            const uint64_t sm = (rin[q] && has_m) ? a1[q] : 0ull;
-            v0 = (sc << 1) | (sm >> 63);
-            raw1 = sc >> 63;
-        } else {
-            const uint64_t sp = (rin[q] && has_p) ? a1[q] : 0ull;
-            v0 = sc;
-            raw1 = sp & 1ull;
+        for (int q = 0; q < 4; q++) { // the eight loads back to back
+            const int64_t d = ((q & 1) ? dj : 0) + ((q >> 1) ? dk : 0);
+            a0[q] = pc[d];
+            a1[q] = pa[d];
         }
-        const uint64_t src = rin[q] ? srcm : 0ull;
-        const uint64_t lo = (v0 & src) | (pbits & exist & ~src);
-        const uint64_t nb = exist1 ? ((rin[q] && src1) ? raw1 : (pbits & 1ull)) : 0ull;
-        r.c[2 * q] = lo;
-        r.c[2 * q + 1] = (lo >> 1) | (nb << 63);
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            uint64_t v0;
+            uint32_t raw1;
+            if (g.pxy) {
+                v0 = mc_shl1(a0[q], (uint32_t)(a1[q] >> 32));
+                raw1 = (uint32_t)(a0[q] >> 63);
+            } else {
+                v0 = a0[q];
+                raw1 = (uint32_t)a1[q] & 1u;
+            }
+            const uint64_t lo = (v0 & srcm) | padlo;
+            r.c[2 * q] = lo;
+            r.c[2 * q + 1] = mc_shr1(lo, use1 ? raw1 : nbpad);
+        }
+    } else {
+        const bool has_m = w32 - 1 >= 0 && w32 - 1 < ws32, has_c = w32 < ws32, has_p = w32 + 1 < ws32;
+        uint64_t a0[4], a1[4];
+        bool rin[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) { // issue the eight loads back to back
+            const int64_t ja = (g.NY - 1 - (j + (q & 1))) - g.pxy, ka = k + (q >> 1) - g.pb;
+            rin[q] = ja >= 0 && ja < g.ny && ka >= 0 && ka < g.nz;
+            const uint64_t *row = bits + (clampi(ka, g.nz) * g.ny + clampi(ja, g.ny)) * g.ws;
+            a0[q] = row[wc];
+            a1[q] = g.pxy ? row[wm] : row[wp];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const uint64_t sc = (rin[q] && has_c) ? a0[q] : 0ull;
+            uint64_t v0, raw1;
+            if (g.pxy) {
+                const uint64_t sm = (rin[q] && has_m) ? a1[q] : 0ull;
+                v0 = (sc << 1) | (sm >> 63);
+                raw1 = sc >> 63;
+            } else {
+                const uint64_t sp = (rin[q] && has_p) ? a1[q] : 0ull;
+                v0 = sc;
+                raw1 = sp & 1ull;
+            }
+            const uint64_t src = rin[q] ? srcm : 0ull;
+            const uint64_t lo = (v0 & src) | (pbits & exist & ~src);
+            const uint64_t nb = exist1 ? ((rin[q] && src1) ? raw1 : (pbits & 1ull)) : 0ull;
+            r.c[2 * q] = lo;
+            r.c[2 * q + 1] = (lo >> 1) | (nb << 63);
+        }
     }
     uint64_t any = 0, all = ~0ull;
 #pragma unroll
@@ -283,9 +379,7 @@ __device__ __forceinline__ Corner8 load_corners(const uint64_t *__restrict__ bit
         any |= r.c[c];
         all &= r.c[c];
     }
-    const int64_t ncell = (g.NX - 1) - w * 64; // cells of this word that exist
-    const uint64_t valid = ncell >= 64 ? ~0ull : ((1ull << ncell) - 1ull);
-    r.active = any & ~all & valid;
+    r.active = any & ~all & mc_lowbits(NX32 - 1 - w32 * 64); // ... among the cells of this word that exist
     return r;
 }
 __device__ __forceinline__ int case_of(const uint64_t *c, int b) {
@@ -305,8 +399,9 @@ __device__ __forceinline__ int case_of(const uint64_t *c, int b) {
 // Two phases per workgroup.  (a) every lane loads the eight corner words of its cell word and finds the active cells: most
 // words have none (13 % do on the bench surface).  (b) the words that have some are handed, packed, to the first lanes of
 // the workgroup, which walk their cells (one table look-up per active cell): the serial walks of a workgroup then sit in
-// ONE or two full waves instead of being scattered over four mostly idle ones (the kernel is bound by the walks, not by
-// the loads: 37 -> 2x us before / after on the bench volume).
+// ONE or two full waves instead of being scattered over four mostly idle ones (37 -> 34 us on the bench volume).  What
+// every lane of every wave runs in front of the first barrier costs as much as the walks: see load_corners' interior form and
+// mc_split_wid.  A workgroup without active cells (seven of eight) leaves after the first barrier.
 __global__ __launch_bounds__(256) void k_mc_count(const uint64_t *__restrict__ bits, Geom g, size_t nwords,
                                                   uint64_t pbits, uint16_t *__restrict__ counts,
                                                   uint32_t *__restrict__ bsum) {
@@ -316,24 +411,28 @@ __global__ __launch_bounds__(256) void k_mc_count(const uint64_t *__restrict__ b
     __shared__ uint8_t s_hi[256];    // bit 63 of the four odd corner words (cell 63's far corners)
     __shared__ uint16_t s_slot[256];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    s_ntri[tid] = MC_NTRI[tid];
+    const uint8_t ntri = MC_NTRI[tid]; // (in flight with the corner loads; stored below, when they are back)
     const size_t wid = (size_t)blockIdx.x * 256 + tid;
     uint64_t act = 0;
     Corner8 r;
     if (wid < nwords) {
-        // nwords < 2^32 (checked on the host): 32-bit divisions instead of two 64-bit ones per lane
-        const uint32_t row = (uint32_t)wid / (uint32_t)g.WC, w = (uint32_t)wid - row * (uint32_t)g.WC;
-        const uint32_t k = row / (uint32_t)(g.NY - 1), j = row - k * (uint32_t)(g.NY - 1);
+        uint32_t k, j, w; // nwords < 2^32 (checked on the host)
+        mc_split_wid(g, (uint32_t)wid, k, j, w);
         r = load_corners(bits, g, (int64_t)k, (int64_t)j, (int64_t)w, pbits);
         act = r.active;
         if (!act) counts[wid] = 0;
     }
     const unsigned long long am = __ballot(act != 0);
     if (lane == 0) s_wcnt[wv] = (uint32_t)__popcll(am);
+    s_ntri[tid] = ntri;
     __syncthreads();
     uint32_t before = 0;
     for (int q = 0; q < wv; q++) before += s_wcnt[q];
     const uint32_t nact = s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
+    if (!nact) { // (uniform) no active cell in the 256 words, as in seven workgroups of eight on the bench surface
+        if (tid == 0) bsum[blockIdx.x] = 0;
+        return;
+    }
     if (act) {
         const uint32_t slot = before + (uint32_t)__popcll(am & ((1ull << lane) - 1ull));
         s_slot[slot] = (uint16_t)tid;
@@ -381,11 +480,15 @@ __global__ __launch_bounds__(1024) void k_mc_scan(const uint32_t *__restrict__ b
     // One workgroup per 16 384 sums (one at 512^3, five at 1024^3 -- where the single workgroup of rounds 1 - 5 took 68 us, 5 % of
     // the stage).  No hand-over between workgroups: each first adds up everything in front of its chunk itself (a coalesced
     // read of at most a few hundred KB out of the L2) and then scans its own chunk.
+    // The chunk is read and written with consecutive lanes on consecutive elements: four rounds of one 16-byte load (four sums)
+    // and two 16-byte stores (four offsets) per lane, so a wave instruction covers 1 KB / 2 KB in a row.  (With sixteen consecutive
+    // sums per lane, as before, every wave instruction touched 64 different lines: 34 000 line requests through the one CU.)
     __shared__ uint64_t s_wave[16];
     __shared__ uint64_t s_carry;
-    constexpr int PER = 16; // consecutive elements per lane
+    __shared__ uint32_t s_tot[64], s_exc[64];
+    constexpr int RND = 4; // rounds of 4 096 sums: lane t of round r holds sums 4 096 r + 4 t .. + 3
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const size_t base = (size_t)blockIdx.x * (1024 * PER);
+    const size_t base = (size_t)blockIdx.x * (1024 * 4 * RND);
     uint64_t pre = 0;
     { // (base is a multiple of 16 384: whole 16-byte groups, four independent loads in flight per lane and trip)
         const uint4 *b4 = reinterpret_cast<const uint4 *>(bsum);
@@ -408,39 +511,65 @@ __global__ __launch_bounds__(1024) void k_mc_scan(const uint32_t *__restrict__ b
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) pre += __shfl_xor(pre, o, 64);
     if (lane == 0) s_wave[wv] = pre;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t c = 0;
-        for (int q = 0; q < 16; q++) c += s_wave[q];
-        s_carry = c;
-    }
-    __syncthreads();
-    {
-        const size_t i0 = base + (size_t)threadIdx.x * PER;
-        uint32_t v[PER];
-        uint64_t sum = 0;
+    // the chunk itself.  A sum is at most 256 words x 320 triangles, so the 16 384 sums of a chunk stay below 2^32: the scan inside
+    // the chunk runs in 32 bits and the 64-bit carry is added at the end.
+    const bool al16 = ((uintptr_t)bsum & 15) == 0 && ((uintptr_t)boff & 15) == 0; // (always, for the scratch layout)
+    uint32_t v[RND][4], inc[RND];
 #pragma unroll
-        for (int q = 0; q < PER; q++) {
-            v[q] = i0 + q < n ? bsum[i0 + q] : 0u;
-            sum += v[q];
+    for (int r = 0; r < RND; r++) { // the four loads back to back
+        const size_t i0 = base + (size_t)r * 4096 + (size_t)threadIdx.x * 4;
+        if (al16 && i0 + 3 < n) {
+            const uint4 a = *reinterpret_cast<const uint4 *>(bsum + i0);
+            v[r][0] = a.x; v[r][1] = a.y; v[r][2] = a.z; v[r][3] = a.w;
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; q++) v[r][q] = i0 + q < n ? bsum[i0 + q] : 0u;
         }
-        uint64_t inc = sum;
+    }
+#pragma unroll
+    for (int r = 0; r < RND; r++) {
+        inc[r] = v[r][0] + v[r][1] + v[r][2] + v[r][3];
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
-            const uint64_t t = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += t;
+            const uint32_t t = __shfl_up(inc[r], o, 64);
+            if (lane >= o) inc[r] += t;
         }
-        __syncthreads(); // (s_wave is reused)
-        if (lane == 63) s_wave[wv] = inc;
-        __syncthreads();
-        uint64_t off = s_carry + inc - sum;
-        for (int q = 0; q < wv; q++) off += s_wave[q];
+        if (lane == 63) s_tot[r * 16 + wv] = inc[r]; // (round, wave) totals, in element order
+    }
+    __syncthreads();
+    if (wv == 0) { // exclusive scan of the 64 totals, and the carry, by one wave
+        const uint32_t t = s_tot[lane];
+        uint32_t e = t;
 #pragma unroll
-        for (int q = 0; q < PER; q++) {
-            if (i0 + q < n) boff[i0 + q] = off;
-            off += v[q];
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t u = __shfl_up(e, o, 64);
+            if (lane >= o) e += u;
         }
-        if (threadIdx.x == 1023 && base + 1024 * PER >= n) boff[n] = off; // the last chunk's last lane holds the total
+        s_exc[lane] = e - t;
+        uint64_t c = 0;
+        for (int q = 0; q < 16; q++) c += s_wave[q];
+        if (lane == 0) s_carry = c;
+        if (lane == 63 && base + 1024 * 4 * RND >= n) boff[n] = c + e; // the last chunk leaves the total behind the offsets
+    }
+    __syncthreads();
+    const uint64_t carry = s_carry;
+#pragma unroll
+    for (int r = 0; r < RND; r++) {
+        const size_t i0 = base + (size_t)r * 4096 + (size_t)threadIdx.x * 4;
+        const uint32_t lanesum = v[r][0] + v[r][1] + v[r][2] + v[r][3];
+        const uint64_t o0 = carry + (uint64_t)(s_exc[r * 16 + wv] + inc[r] - lanesum);
+        const uint64_t o1 = o0 + v[r][0], o2 = o1 + v[r][1], o3 = o2 + v[r][2];
+        if (al16 && i0 + 3 < n) {
+            typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));
+            u64x2_t *d = reinterpret_cast<u64x2_t *>(boff + i0);
+            d[0] = u64x2_t{o0, o1};
+            d[1] = u64x2_t{o2, o3};
+        } else {
+            if (i0 < n) boff[i0] = o0;
+            if (i0 + 1 < n) boff[i0 + 1] = o1;
+            if (i0 + 2 < n) boff[i0 + 2] = o2;
+            if (i0 + 3 < n) boff[i0 + 3] = o3;
+        }
     }
 }
 
@@ -469,10 +598,17 @@ __global__ __launch_bounds__(256) void k_mc_list(const uint64_t *__restrict__ bi
     __shared__ uint8_t s_ntri[256];
     __shared__ uint16_t s_slot[256];
     __shared__ uint32_t s_pos[256];
+    __shared__ uint16_t s_n[256];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    s_ntri[tid] = MC_NTRI[tid];
+    // A workgroup without triangles (seven in eight on the bench surface) leaves as soon as two scalar loads show that its slice of
+    // the scan is empty: no LDS, no wave scan, no barrier.  The table and counts loads are issued in front of that test, so that a
+    // workgroup that stays has them in flight together (measured 0.4 us better on the kernel than issuing them behind it).
+    const uint8_t ntri = MC_NTRI[tid]; // (in flight with the count: one round trip, not two)
     const size_t wid0 = (size_t)blockIdx.x * 256;
     const uint32_t n = wid0 + tid < nwords ? (uint32_t)counts[wid0 + tid] : 0u;
+    const uint64_t pos0 = boff[blockIdx.x];
+    if (boff[blockIdx.x + 1] == pos0) return;
+    s_ntri[tid] = ntri;
     uint32_t inc = n;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
@@ -484,7 +620,6 @@ __global__ __launch_bounds__(256) void k_mc_list(const uint64_t *__restrict__ bi
     if (lane == 0) s_wcnt[wv] = (uint32_t)__popcll(am);
     __syncthreads();
     const uint32_t nact = s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
-    if (!nact) return; // (uniform)
     if (n) {
         uint32_t wbase = 0, before = 0;
         for (int q = 0; q < wv; q++) {
@@ -494,15 +629,16 @@ __global__ __launch_bounds__(256) void k_mc_list(const uint64_t *__restrict__ bi
         const uint32_t slot = before + (uint32_t)__popcll(am & ((1ull << lane) - 1ull));
         s_slot[slot] = (uint16_t)tid;
         s_pos[slot] = wbase + inc - n; // first triangle of the word, relative to the block
+        s_n[slot] = (uint16_t)n;       // (handed over with it: re-reading counts[] was a dependent global round trip)
     }
     __syncthreads();
     if ((uint32_t)tid >= nact) return;
     const size_t wid = wid0 + s_slot[tid];
-    uint64_t pos = boff[blockIdx.x] + s_pos[tid];
-    const uint32_t nmine = (uint32_t)counts[wid];
+    uint64_t pos = pos0 + s_pos[tid];
+    const uint32_t nmine = s_n[tid];
     if (pos + nmine > max_tris) return; // never write past the list the caller sized from the count
-    const uint32_t row = (uint32_t)wid / (uint32_t)g.WC, w = (uint32_t)wid - row * (uint32_t)g.WC;
-    const uint32_t k = row / (uint32_t)(g.NY - 1), j = row - k * (uint32_t)(g.NY - 1);
+    uint32_t k, j, w;
+    mc_split_wid(g, (uint32_t)wid, k, j, w);
     const Corner8 r = load_corners(bits, g, (int64_t)k, (int64_t)j, (int64_t)w, pbits);
     uint64_t act = r.active;
     while (act) {
@@ -738,10 +874,7 @@ __global__ __launch_bounds__(256) void k_mc_fused(const uint64_t *__restrict__ b
     Corner8 r;
     uint32_t k = 0, j = 0, w = 0;
     if (wid < nwords) {
-        const uint32_t row = (uint32_t)wid / (uint32_t)g.WC;
-        w = (uint32_t)wid - row * (uint32_t)g.WC;
-        k = row / (uint32_t)(g.NY - 1);
-        j = row - k * (uint32_t)(g.NY - 1);
+        mc_split_wid(g, (uint32_t)wid, k, j, w);
         r = load_corners(bits, g, (int64_t)k, (int64_t)j, (int64_t)w, pbits);
         act = r.active;
     }
@@ -1378,6 +1511,16 @@ static MciLayout mci_layout(const Geom &g, const Scratch &s, int niso) {
 static inline uint64_t pad_qbits(const ivx_mc_params *p, int q) { return p->pad_value > p->iso[q] ? ~0ull : 0ull; }
 
 } // namespace
+
+// The (slice, row, word) of `n` cell-word ids of the piece `p`, computed on the host with the constants and the arithmetic the
+// kernels use (no device needed): what the tests hold against integer division.
+extern "C" int ivx_mc_split_word_ids(const ivx_mc_params *p, const uint32_t *wid, size_t n, uint32_t *k, uint32_t *j, uint32_t *w) {
+    Geom g;
+    int rc = make_geom(p, &g);
+    if (rc) return rc;
+    for (size_t i = 0; i < n; i++) mc_split_wid(g, wid[i], k[i], j[i], w[i]);
+    return IVX_OK;
+}
 
 extern "C" int ivx_dev_mc_scratch_bytes(const ivx_mc_params *p, size_t *nbytes) {
     Geom g;
