@@ -569,6 +569,12 @@ int ivx_dev_flood_run(const ivx_flood_plan *p, const uint64_t *cand, uint64_t *r
 int ivx_dev_flood_grow(const ivx_flood_plan *p, int dtype, const void *data, double t0, double t1,
                        const int64_t *seeds_xyz, int64_t nseeds, uint64_t *cand, uint64_t *reached, void *scratch,
                        int *rounds, void *stream);
+/* host only, for tests: the path ivx_dev_flood_grow takes for this plan and `nseeds` seeds, from the functions that size its
+ * launches (no device call).  out[0] coarse pass on (0/1), out[1] block width in voxels along x (16 / 32 / 64), out[2] blocks
+ * per tile along x, out[3] lanes of the coarse workgroup, out[4] rows of tiles per lane = ceil(rows / lanes) (out[1..4] are 0
+ * with the coarse pass off), out[5] fused start taken for `nseeds` (0/1), out[6] the most workgroups a round is launched
+ * with, out[7] tiles.  The IVX_FLOOD_* switches of the process count as they do for a flood. */
+int ivx_flood_describe(const ivx_flood_plan *p, int64_t nseeds, int32_t out[8]);
 /* The rounds of a flood run in ONE resident launch (k_flood_resident: round boundaries are device-wide barriers; the launch
  * ends at the first empty round) -- IVX_FLOOD_RESIDENT=0 brings back one launch per round.  ivx_dev_flood_grow waits for the
  * launch's last word before it returns; ivx_dev_flood_grow_async returns right behind the launch (*pending = 1; *rounds is

@@ -1452,11 +1452,8 @@ static bool coarse_ok(const Tiles &t, ivx::FloodMode mode) {
     return coarse_on && mode == ivx::FLOOD_SYMMETRIC && t.conn != 0 && t.wx <= 64 && (t.nty + 2) * (t.ntz + 2) <= CROWS_MAX &&
            t.nty * t.ntz <= (int64_t)CT * CRP;
 }
-// The coarse pass's three launches (see k_flood_coarse): blocks of 16 / 32 / 64 x 16 x 16 voxels, the finest whose row fits
-// one word.  FRESH: the clearing and the seeding of `f` ride along; otherwise `f` carries no seeds.
-template <bool FRESH>
-static int coarse_pass(const Tiles &t, const FScratch &s, char *scr, const uint64_t *cand, uint64_t *reached, const Fresh &f,
-                       int ncnt, hipStream_t st) {
+// the block width of the coarse graph for this tile grid (see Blocks)
+static Blocks coarse_blocks(const Tiles &t) {
     static const int bxs_env = [] {
         const char *e = getenv("IVX_FLOOD_BLOCK"); // 16 / 32 / 64: force a coarser block (A/B measurements)
         return e ? atoi(e) : 0;
@@ -1465,13 +1462,27 @@ static int coarse_pass(const Tiles &t, const FScratch &s, char *scr, const uint6
     bk.bxs = 16;
     while (bk.bxs < 64 && ((64 / bk.bxs) * t.wx > 64 || bk.bxs < bxs_env)) bk.bxs *= 2;
     bk.q = 64 / bk.bxs;
+    return bk;
+}
+// lanes of k_flood_coarse's one workgroup: one row of tiles per lane up to 1024 lanes, then up to CRP rows per lane
+// (128..1024 lanes measured equal)
+static int coarse_lanes(const Tiles &t) {
+    int ct = 64;
+    while (ct < CT && ct < t.nty * t.ntz) ct *= 2;
+    return ct;
+}
+// The coarse pass's three launches (see k_flood_coarse): blocks of 16 / 32 / 64 x 16 x 16 voxels, the finest whose row fits
+// one word.  FRESH: the clearing and the seeding of `f` ride along; otherwise `f` carries no seeds.
+template <bool FRESH>
+static int coarse_pass(const Tiles &t, const FScratch &s, char *scr, const uint64_t *cand, uint64_t *reached, const Fresh &f,
+                       int ncnt, hipStream_t st) {
+    const Blocks bk = coarse_blocks(t);
     uint8_t *dirty0 = (uint8_t *)(scr + s.off_dirty0), *dirty1 = (uint8_t *)(scr + s.off_dirty1);
     unsigned int *cnt = (unsigned int *)(scr + s.off_cnt), *list0 = (unsigned int *)(scr + s.off_list0);
     unsigned long long *rowF = (unsigned long long *)(scr + s.off_full), *rowW = (unsigned long long *)(scr + s.off_whole);
     unsigned int *seed_ok = (unsigned int *)(scr + s.off_status) + 8;
     const unsigned groups = (unsigned)(t.nty * t.ntz);
-    int ct = 64; // one row of tiles per lane up to 1024 lanes, then up to CRP rows per lane (128..1024 lanes measured equal)
-    while (ct < CT && ct < t.nty * t.ntz) ct *= 2;
+    const int ct = coarse_lanes(t);
     hipLaunchKernelGGL(k_flood_block_flags<FRESH>, dim3(groups), dim3(256), 0, st, t, bk, (unsigned long long *)cand,
                        (const unsigned long long *)reached, dirty0, dirty1, rowF, rowW, cnt, ncnt, f.sp, f.dtype, f.data, f.t0,
                        f.t1, seed_ok);
@@ -1486,6 +1497,8 @@ static int coarse_pass(const Tiles &t, const FScratch &s, char *scr, const uint6
     IVX_LAUNCH_CHECK();
     return IVX_OK;
 }
+// the most workgroups a round is launched with: 6 workgroups per CU are resident (80 VGPRs)
+static unsigned round_grid_cap(const Tiles &t) { return (unsigned)(t.ntiles < 1536 ? t.ntiles : 1536); }
 // Spin on the first word of a pinned progress line until `done(word)`, at most `spins` polls; then take the safe path once:
 // synchronise the stream and look again.  `never`: the error when even that word does not satisfy `done`.
 template <typename Done>
@@ -1670,7 +1683,7 @@ static int flood_run_impl(const ivx_flood_plan *p, const uint64_t *cand, ivx::Fl
             return flood_wait_impl(p, cand, reached, scratch_, rounds, nullptr, stream);
         }
     }
-    const unsigned grid_max = (unsigned)(t.ntiles < 1536 ? t.ntiles : 1536); // 6 workgroups per CU are resident (80 VGPRs)
+    const unsigned grid_max = round_grid_cap(t);
     // The rounds queued ahead are sized by the newest list length the host has seen: the lists shrink towards the end, and
     // dispatching 1536 workgroups that find nothing costs ~3 us more per round than dispatching 128 (a list that turns out
     // longer than the grid is still served: workgroups stride over it).
@@ -1737,6 +1750,14 @@ extern "C" int ivx_dev_flood_run(const ivx_flood_plan *p, const uint64_t *cand, 
                                  int *rounds, void *stream) {
     return flood_run_impl(p, cand, ivx::FLOOD_SYMMETRIC, reached, scratch_, rounds, stream);
 }
+// does a flood of `nseeds` seeds take the fused start (clear and seed inside the coarse pass)?
+static bool fused_start(const Tiles &t, int64_t nseeds) {
+    static const bool fused_on = [] {
+        const char *e = getenv("IVX_FLOOD_FUSED");
+        return !(e && e[0] == '0');
+    }();
+    return fused_on && nseeds >= 1 && nseeds <= 16 && t.ntiles > 0 && !flood_mode_ccl() && coarse_ok(t, ivx::FLOOD_SYMMETRIC);
+}
 // clear + seed + run in one call: the flood of `seeds` over `cand` into a plane whose old contents are dead.  With at most
 // 16 seeds and a standard structuring element the clearing and the seeding ride on the coarse pass (three launches before
 // the rounds instead of five, no separate pass over the plane); otherwise the three calls run one after the other.
@@ -1753,11 +1774,7 @@ static int flood_grow_impl(const ivx_flood_plan *p, int dtype, const void *data,
                     "flood: seed (%lld,%lld,%lld) outside volume (%lld,%lld,%lld) [x,y,z]", (long long)x, (long long)y,
                     (long long)z, (long long)t.dx, (long long)t.dy, (long long)t.dz);
     }
-    static const bool fused_on = [] {
-        const char *e = getenv("IVX_FLOOD_FUSED");
-        return !(e && e[0] == '0');
-    }();
-    if (!(fused_on && nseeds >= 1 && nseeds <= 16 && t.ntiles > 0 && !flood_mode_ccl() && coarse_ok(t, ivx::FLOOD_SYMMETRIC))) {
+    if (!fused_start(t, nseeds)) {
         if ((rc = ivx_dev_flood_clear(p, reached, scratch_, stream))) return rc;
         if ((rc = ivx_dev_flood_seed(p, dtype, data, t0, t1, seeds_xyz, nseeds, cand, reached, scratch_, stream))) return rc;
         return flood_run_impl(p, cand, ivx::FLOOD_SYMMETRIC, reached, scratch_, rounds, stream, nullptr, resident);
@@ -1772,6 +1789,28 @@ static int flood_grow_impl(const ivx_flood_plan *p, int dtype, const void *data,
     for (int64_t n = 0; n < nseeds; n++)
         for (int q = 0; q < 3; q++) f.sp.xyz[n][q] = seeds_xyz[3 * n + q];
     return flood_run_impl(p, cand, ivx::FLOOD_SYMMETRIC, reached, scratch_, rounds, stream, &f, resident);
+}
+// host only, for tests: the path ivx_dev_flood_grow takes for this plan and seed count, by the very functions that size
+// its launches (no device call)
+extern "C" int ivx_flood_describe(const ivx_flood_plan *p, int64_t nseeds, int32_t out[8]) {
+    IVX_REQUIRE(out, IVX_EINVAL, "flood_describe: NULL argument");
+    Tiles t;
+    int rc = make_tiles(p, &t);
+    if (rc) return rc;
+    for (int i = 0; i < 8; i++) out[i] = 0;
+    if (coarse_ok(t, ivx::FLOOD_SYMMETRIC)) {
+        const Blocks bk = coarse_blocks(t);
+        const int ct = coarse_lanes(t);
+        out[0] = 1;
+        out[1] = bk.bxs;
+        out[2] = bk.q;
+        out[3] = ct;
+        out[4] = (int32_t)ivx::cdiv(t.nty * t.ntz, (int64_t)ct);
+    }
+    out[5] = fused_start(t, nseeds) ? 1 : 0;
+    out[6] = (int32_t)round_grid_cap(t);
+    out[7] = (int32_t)t.ntiles;
+    return IVX_OK;
 }
 extern "C" int ivx_dev_flood_grow(const ivx_flood_plan *p, int dtype, const void *data, double t0, double t1,
                                   const int64_t *seeds_xyz, int64_t nseeds, uint64_t *cand, uint64_t *reached, void *scratch_,
