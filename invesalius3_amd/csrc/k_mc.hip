@@ -20,13 +20,14 @@
 //                    177 VALU in front of the first barrier, 34.0 -> 27.4 us at 512^3.
 //   3. k_mc_scan     exclusive scan of the per-workgroup sums (u64 offsets), one workgroup per 16 384 sums,
 //                    consecutive lanes on consecutive sums (16-byte loads and stores): 11.4 -> 4.9 us.
-//   3b. k_mc_list    one 64-bit descriptor per triangle in output order, written by the lane that owns the cell
-//                    word; a workgroup whose slice of the scan is empty leaves at once.
+//   3b. k_mc_list    one 64-bit descriptor per triangle in output order: the active cells of a workgroup's 256 words,
+//                    one per lane, each storing its own descriptors at the place a block scan gives it; a workgroup whose
+//                    slice of the scan is empty leaves at once.
 //   4. k_mc_emit     one lane per triangle of the list, 256 consecutive triangles per workgroup, so lanes stay
 //                    busy however unevenly the surface is spread.  The 9 floats of each triangle are staged in
 //                    LDS (stride 9 dwords: conflict-free) and leave as aligned 16-byte non-temporal stores: HBM
 //                    sees each output line once.
-// (What was measured for the passes in front of the emit, part by part: profiles/mc_front_end_ab.md.)
+// (What was measured for the passes in front of the emit, part by part: profiles/mc_front_end_ab.md, profiles/mc_list_stores_ab.md.)
 // Output order == the oracle's (iso-major, then k, j, i raster order of cells), so parity is an array compare.
 // Vertex arithmetic is done in double and rounded once to float32, exactly like the oracle.
 #include <cmath>
@@ -401,7 +402,7 @@ __device__ __forceinline__ int case_of(const uint64_t *c, int b) {
 // the workgroup, which walk their cells (one table look-up per active cell): the serial walks of a workgroup then sit in
 // ONE or two full waves instead of being scattered over four mostly idle ones (37 -> 34 us on the bench volume).  What
 // every lane of every wave runs in front of the first barrier costs as much as the walks: see load_corners' interior form and
-// mc_split_wid.  A workgroup without active cells (seven of eight) leaves after the first barrier.
+// mc_split_wid.  A workgroup without active cells (54 % of them on the bench surface) leaves after the first barrier.
 __global__ __launch_bounds__(256) void k_mc_count(const uint64_t *__restrict__ bits, Geom g, size_t nwords,
                                                   uint64_t pbits, uint16_t *__restrict__ counts,
                                                   uint32_t *__restrict__ bsum) {
@@ -429,7 +430,7 @@ __global__ __launch_bounds__(256) void k_mc_count(const uint64_t *__restrict__ b
     uint32_t before = 0;
     for (int q = 0; q < wv; q++) before += s_wcnt[q];
     const uint32_t nact = s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
-    if (!nact) { // (uniform) no active cell in the 256 words, as in seven workgroups of eight on the bench surface
+    if (!nact) { // (uniform) no active cell in the 256 words, as in 5 006 workgroups of 9 253 on the bench surface
         if (tid == 0) bsum[blockIdx.x] = 0;
         return;
     }
@@ -584,73 +585,133 @@ __device__ __forceinline__ void edge_decode(int e, int &ax, int &bx, int &by, in
     bz = ax == 2 ? 0 : b;
 }
 
-// 4a. list: the OWNER of each cell word writes one 64-bit descriptor per triangle into a flat global list, in output
-//     order: (k << 48) | (j << 32) | (w << 17) | (cell bit << 11) | (case << 3) | triangle-in-case, (k, j, w) = the cell
-//     word's slice, row and word in the row (the readers -- one lane per triangle -- then need no divisions: two 32-bit
-//     divisions by run-time divisors were a quarter of k_mc_emit's instructions).  One case evaluation per
-//     active cell; only workgroups that own triangles do anything beyond a 256-entry scan.  Like the count, in two
-//     phases: the words that own triangles are handed, packed, to the first lanes of the workgroup, so that the corner
-//     loads and the serial walks fill one or two waves instead of idling in four.
+// 4a. list: one 64-bit descriptor per triangle in a flat global list, in output order: (k << 48) | (j << 32) | (w << 17) |
+//     (cell bit << 11) | (case << 3) | triangle-in-case, (k, j, w) = the cell word's slice, row and word in the row (the readers
+//     -- one lane per triangle -- then need no divisions: two 32-bit divisions by run-time divisors were a quarter of
+//     k_mc_emit's instructions).  One case evaluation per active cell; only workgroups that own triangles (46 % of them on the
+//     bench surface) do anything beyond two scalar loads.
+//     CELL-PARALLEL.  Before, the lane that owned a cell word walked its cells one after the other and stored each cell's
+//     descriptors itself: a wave ran 26 dependent iterations (the longest word of 64) so that its average lane could do 10, and
+//     every store instruction hit up to 64 different lines.  Measured on the bench surface with parts left out
+//     (profiles/mc_list_stores_ab.md): 50.6 us as it was, 11.6 us with every store but each word's first removed, i.e. the
+//     stores were four fifths of the pass.  Now:
+//       phase 1  the words that own triangles (counts[] != 0 <=> the word has an active cell) load their corner words where
+//                they are, leave them in LDS (s_c, s_hi, as k_mc_count does) with their (k, j, w) prefix, and -- after a scan of
+//                the words' popcounts -- scatter one 2-byte record (word, bit) per active cell into an LDS array in raster
+//                order.  That loop only stores; nothing in it waits on a table look-up.
+//       phase 2  one cell per LANE, MCL_CHUNK cells at a time: case index from s_c, triangle count from the table, a block scan
+//                of the counts (wave scan in DPP + four partial sums, one barrier per chunk, two sets of partial sums so that the
+//                next chunk's writers never meet this chunk's readers), and the lane stores its cell's descriptors at
+//                list[first of the block + offset ...].  Consecutive lanes own consecutive cells, so a store instruction covers
+//                one stretch of the list (64 cells x 2.25 triangles x 8 bytes, about ten lines) instead of 64 lines anywhere.
+//     The position of a cell's first triangle is the running sum over the block's cells: the per-word counts are only used to
+//     tell which words to load.  Clipped per ENTRY: nothing at or beyond max_tris is written, everything below it is.
+//     Also measured and not kept (same file): the descriptors of a chunk staged in an LDS window and copied out with consecutive
+//     lanes on consecutive entries (36.0 us against 32.0: the second barrier per chunk and 10 KB more LDS, i.e. six workgroups per
+//     CU instead of eight, cost more than the fewer store requests save -- the new pass is bound by the latency chain of a
+//     workgroup times the workgroups a CU holds: with LDS padded to four workgroups per CU it takes 47 us instead of 39), and
+//     16-byte pairs in that copy-out (41.7 us against 41.1 for 8-byte stores).
+constexpr int MCL_CHUNK = 256;   // cells per chunk: one per lane
+constexpr int MCL_CELLS = 2048;  // cell records in LDS at a time (eight chunks; the densest block of the bench surface has 2 708)
+// inclusive scan of one value per lane over the wave, in DPP: within rows of 16 lanes by shifts of 1, 2, 4 and 8, then lane 15 of
+// rows 0 and 2 into rows 1 and 3, then lane 31 into rows 2 and 3.  Every lane of the wave must be active.
+__device__ __forceinline__ uint32_t mcl_wave_scan(uint32_t v) {
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false); // row_shr:1
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false); // row_shr:2
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false); // row_shr:4
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false); // row_shr:8
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false); // row_bcast:15 into rows 1 and 3
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false); // row_bcast:31 into rows 2 and 3
+    return v;
+}
 __global__ __launch_bounds__(256) void k_mc_list(const uint64_t *__restrict__ bits, Geom g, size_t nwords, uint64_t pbits,
                                                  const uint16_t *__restrict__ counts, const uint64_t *__restrict__ boff,
                                                  uint64_t *__restrict__ list, uint64_t max_tris) {
-    __shared__ uint32_t s_wave[4], s_wcnt[4];
+    __shared__ uint32_t s_wave[4], s_part[2][4];
     __shared__ uint8_t s_ntri[256];
-    __shared__ uint16_t s_slot[256];
-    __shared__ uint32_t s_pos[256];
-    __shared__ uint16_t s_n[256];
+    __shared__ uint64_t s_c[4][256];        // per cell word: the four even corner words
+    __shared__ uint8_t s_hi[256];           // bit 63 of the four odd corner words (cell 63's far corners)
+    __shared__ uint64_t s_pre[256];         // (k << 48) | (j << 32) | (w << 17)
+    __shared__ uint16_t s_cell[MCL_CELLS];  // active cells in raster order: (word of the block << 6) | bit
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    // A workgroup without triangles (seven in eight on the bench surface) leaves as soon as two scalar loads show that its slice of
-    // the scan is empty: no LDS, no wave scan, no barrier.  The table and counts loads are issued in front of that test, so that a
-    // workgroup that stays has them in flight together (measured 0.4 us better on the kernel than issuing them behind it).
+    // A workgroup without triangles (54 % of them on the bench surface: 5 006 of 9 253) leaves as soon as two scalar loads show
+    // that its slice of the scan is empty: no wave scan, no barrier.  The table and counts loads are issued in front of that test,
+    // so that a workgroup that stays has them in flight together (measured 0.4 us better on the kernel than issuing them behind it).
     const uint8_t ntri = MC_NTRI[tid]; // (in flight with the count: one round trip, not two)
     const size_t wid0 = (size_t)blockIdx.x * 256;
     const uint32_t n = wid0 + tid < nwords ? (uint32_t)counts[wid0 + tid] : 0u;
     const uint64_t pos0 = boff[blockIdx.x];
-    if (boff[blockIdx.x + 1] == pos0) return;
-    s_ntri[tid] = ntri;
-    uint32_t inc = n;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    const unsigned long long am = __ballot(n != 0);
-    if (lane == 63) s_wave[wv] = inc;
-    if (lane == 0) s_wcnt[wv] = (uint32_t)__popcll(am);
-    __syncthreads();
-    const uint32_t nact = s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
+    if (boff[blockIdx.x + 1] == pos0 || pos0 >= max_tris) return; // (the second: nothing of this block fits the caller's list)
+    // phase 1
+    uint64_t a2 = 0;
     if (n) {
-        uint32_t wbase = 0, before = 0;
-        for (int q = 0; q < wv; q++) {
-            wbase += s_wave[q];
-            before += s_wcnt[q];
-        }
-        const uint32_t slot = before + (uint32_t)__popcll(am & ((1ull << lane) - 1ull));
-        s_slot[slot] = (uint16_t)tid;
-        s_pos[slot] = wbase + inc - n; // first triangle of the word, relative to the block
-        s_n[slot] = (uint16_t)n;       // (handed over with it: re-reading counts[] was a dependent global round trip)
-    }
-    __syncthreads();
-    if ((uint32_t)tid >= nact) return;
-    const size_t wid = wid0 + s_slot[tid];
-    uint64_t pos = pos0 + s_pos[tid];
-    const uint32_t nmine = s_n[tid];
-    if (pos + nmine > max_tris) return; // never write past the list the caller sized from the count
-    uint32_t k, j, w;
-    mc_split_wid(g, (uint32_t)wid, k, j, w);
-    const Corner8 r = load_corners(bits, g, (int64_t)k, (int64_t)j, (int64_t)w, pbits);
-    uint64_t act = r.active;
-    while (act) {
-        const int b = __builtin_ctzll(act);
-        act &= act - 1;
-        const int idx = case_of(r.c, b);
-        const uint32_t nt = s_ntri[idx];
-        const uint64_t d0 = ((uint64_t)k << 48) | ((uint64_t)j << 32) | ((uint64_t)w << 17) | ((uint64_t)b << 11) | ((uint64_t)idx << 3);
+        uint32_t k, j, w;
+        mc_split_wid(g, (uint32_t)(wid0 + tid), k, j, w);
+        const Corner8 r = load_corners(bits, g, (int64_t)k, (int64_t)j, (int64_t)w, pbits);
+        a2 = r.active;
+        uint32_t hi = 0;
 #pragma unroll
-        for (uint32_t t = 0; t < MC_MAX_TRI; t++)
-            if (t < nt) list[pos + t] = d0 | t;
-        pos += nt;
+        for (int q = 0; q < 4; q++) {
+            s_c[q][tid] = r.c[2 * q];
+            hi |= (uint32_t)(r.c[2 * q + 1] >> 63) << q;
+        }
+        s_hi[tid] = (uint8_t)hi;
+        s_pre[tid] = ((uint64_t)k << 48) | ((uint64_t)j << 32) | ((uint64_t)w << 17);
+    }
+    const uint32_t pc = (uint32_t)__popcll(a2);
+    const uint32_t inc = mcl_wave_scan(pc);
+    if (lane == 63) s_wave[wv] = inc;
+    s_ntri[tid] = ntri;
+    __syncthreads();
+    uint32_t ci = inc - pc; // this word's first cell among the block's active cells
+    for (int q = 0; q < wv; q++) ci += s_wave[q];
+    const uint32_t ncell = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    uint64_t P = pos0; // list position of the next chunk's first triangle
+    int par = 0;
+    for (uint32_t sb = 0; sb < ncell; sb += MCL_CELLS) { // (every bound of the loops below is the same in all lanes)
+        const uint32_t se = sb + MCL_CELLS < ncell ? sb + MCL_CELLS : ncell;
+        // (the records of the round before were last read in front of a barrier every lane has passed since)
+        while (a2 && ci < se) {
+            const int b = __builtin_ctzll(a2);
+            a2 &= a2 - 1;
+            s_cell[ci - sb] = (uint16_t)((tid << 6) | b);
+            ci++;
+        }
+        __syncthreads();
+        // phase 2
+        for (uint32_t cb = sb; cb < se; cb += MCL_CHUNK) {
+            const uint32_t c = cb + tid;
+            uint32_t nt = 0;
+            uint64_t d0 = 0;
+            if (c < se) {
+                const uint32_t rec = s_cell[c - sb], sl = rec >> 6;
+                const int b = (int)(rec & 63u);
+                const uint64_t c0 = s_c[0][sl], c1 = s_c[1][sl], c2 = s_c[2][sl], c3 = s_c[3][sl];
+                int idx;
+                if (b != 63) {
+                    idx = (int)((c0 >> b) & 3ull) | ((int)((c1 >> b) & 3ull) << 2) | ((int)((c2 >> b) & 3ull) << 4) | ((int)((c3 >> b) & 3ull) << 6);
+                } else {
+                    const uint32_t hi = s_hi[sl];
+                    idx = (int)(c0 >> 63) | ((int)(hi & 1u) << 1) | ((int)(c1 >> 63) << 2) | ((int)(hi >> 1 & 1u) << 3) | ((int)(c2 >> 63) << 4) |
+                          ((int)(hi >> 2 & 1u) << 5) | ((int)(c3 >> 63) << 6) | ((int)(hi >> 3 & 1u) << 7);
+                }
+                nt = s_ntri[idx];
+                d0 = s_pre[sl] | ((uint64_t)b << 11) | ((uint64_t)idx << 3);
+            }
+            const uint32_t ti = mcl_wave_scan(nt);
+            if (lane == 63) s_part[par][wv] = ti;
+            __syncthreads();
+            uint32_t off = ti - nt;
+            for (int q = 0; q < wv; q++) off += s_part[par][q];
+            const uint32_t tot = s_part[par][0] + s_part[par][1] + s_part[par][2] + s_part[par][3];
+            const uint64_t p0 = P + off;
+#pragma unroll
+            for (uint32_t t = 0; t < MC_MAX_TRI; t++)
+                if (t < nt && p0 + t < max_tris) list[p0 + t] = d0 | t;
+            P += tot;
+            if (P >= max_tris) return; // (uniform: no lane is missing from a later barrier)
+            par ^= 1;
+        }
     }
 }
 
