@@ -256,7 +256,11 @@ int ivx_dev_mc_scratch_bytes(const ivx_mc_params *p, size_t *nbytes);
 /* host only, for tests: slice k, cell row j and word-in-row w of n cell-word ids (word id = (k * (NY-1) + j) * WC + w of the
  * padded cell grid), by the division-free arithmetic and the per-piece constants the count and list kernels use */
 int ivx_mc_split_word_ids(const ivx_mc_params *p, const uint32_t *wid, size_t n, uint32_t *k, uint32_t *j, uint32_t *w);
-/* classify + per-row-group triangle counts + scan; *ntris (host) receives the total */
+/* classify + per-row-group triangle counts + scan; *ntris (host) receives the total.  Every count (this one, the _async and
+ * the _bits forms) voids what the library remembered about the piece counted into `scratch` before: its inside plane, its
+ * triangle list, its iso-0 / iso-1 split and its vertex split.  A later call that needs one of them and does not find it
+ * returns IVX_EINVAL ("... must follow ..."): after a queue-only count of a two-iso piece, ivx_dev_mc_total comes before
+ * ivx_dev_mc_indexed_emit. */
 int ivx_dev_mc_count(const ivx_mc_params *p, const void *a, void *scratch, int64_t *ntris, void *stream);
 /* Queue-only forms: nothing comes back to the host, so ivx_dev_mc_emit can be queued right behind them with the
  * CAPACITY of `tris` as max_tris (the emit kernel reads the real count, and the iso-0 / iso-1 split, on the device and
@@ -279,18 +283,6 @@ int ivx_dev_mc_emit(const ivx_mc_params *p, const void *a, const void *scratch, 
  * triangle costs three bit look-ups instead of six byte gathers; same arithmetic on the same numbers, same soup. */
 int ivx_dev_mc_emit_levels(const ivx_mc_params *p, const void *scratch, const uint64_t *sel_bits, double v_out, double v_in,
                            double v_sel, float *tris, int64_t max_tris, void *stream);
-/* The whole surface in ONE launch (k_mc_fused): cell words -> active cells -> triangle counts -> output offsets by a decoupled
- * look-back across the workgroups -> triangles, without per-word counts, a scan launch or a triangle list.  One iso-value
- * (from_binary surfaces: surface_process.py:172-186 with the mask at iso 127; two-iso "Default" pieces keep count + emit).
- * inside_bits: the plane "value >= iso[0]" in source coordinates if the caller holds it, else NULL (derived from `a`).  Writes at
- * most max_tris triangles -- same soup, same order, same bits as ivx_dev_mc_count + ivx_dev_mc_emit (measured SLOWER than those at
- * 512^3, equal at 1024^3: an opt-in, IVX_MC_ONE_LAUNCH=1, see csrc/k_mc.hip); ivx_dev_mc_total then
- * returns the count (if it exceeds max_tris, call again with a larger buffer).  The *_levels form reads no voxel: the mask's
- * bytes are v_out outside inside_bits, v_sel where sel_bits has a bit, v_in elsewhere inside (see ivx_dev_mc_emit_levels). */
-int ivx_dev_mc_surface(const ivx_mc_params *p, const void *a, const uint64_t *inside_bits /* may be NULL */, void *scratch,
-                       float *tris, int64_t max_tris, void *stream);
-int ivx_dev_mc_surface_levels(const ivx_mc_params *p, const uint64_t *inside_bits, const uint64_t *sel_bits, double v_out, double v_in,
-                              double v_sel, void *scratch, float *tris, int64_t max_tris, void *stream);
 /* the list pass of ivx_dev_mc_emit on its own (it needs the counts, not the voxels): queue it early, on the stream the
  * emit will use; the emit that follows with max_tris <= this max_tris skips its own list pass */
 int ivx_dev_mc_list(const ivx_mc_params *p, const void *scratch, int64_t max_tris, void *stream);

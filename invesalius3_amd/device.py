@@ -9,10 +9,23 @@ from __future__ import annotations
 
 import ctypes
 import os
+from typing import NamedTuple, Optional
 
 import numpy as np
 
 from . import _lib as L
+
+
+class _MaskLevels(NamedTuple):
+    """a uint8 mask whose bytes are known: `v_in` inside the inside plane, `v_sel` where the plane `sel` has a bit.  Without a
+    second level `sel` is None (NULL for the kernels that accept it) and `v_sel == v_in`."""
+    v_in: float
+    sel: Optional[ctypes.c_void_p]
+    v_sel: float
+
+    @property
+    def has_second(self):
+        return self.sel is not None
 
 
 class DeviceBuffer:
@@ -537,38 +550,31 @@ class DeviceVolume:
             plane = self._mbits.at(z0 * self.dy * ((self.dx + 63) // 64) * 8)
         return src, plane
 
+    def _levels(self, p, plane, z0):
+        """The known byte levels of the mask as `_MaskLevels`, when the pipeline can prove them -- 0 outside the inside plane
+        `plane`, `v_in` inside it and `v_sel` where the plane `sel` has a bit --; None when it cannot: the voxels are read then.
+        (A caller's own `params` may carry another padding value, or levels that do not straddle iso 127 the way the kernels'
+        constants assume.)"""
+        lv = self._mask_levels
+        if not (plane is not None and lv is not None and self._fuse and os.environ.get("IVX_MC_LEVELS", "1") != "0"
+                and float(p.pad_value) == 0.0 and lv[0] > 127 and (lv[1] is None or lv[1] > 127)):
+            return None
+        if lv[1] is None:
+            return _MaskLevels(float(lv[0]), None, float(lv[0]))
+        return _MaskLevels(float(lv[0]), self.reached.at(z0 * self.dy * ((self.dx + 63) // 64) * 8), float(lv[1]))
+
     def _emit(self, p, src, plane, z0, cap, stream):
         """the triangle emit of a counted piece: from the known byte levels of the mask when the pipeline can prove them
         (no voxel is read), else from the voxels"""
-        lib, lv = L.lib(), self._mask_levels
-        # (the same predicate as marching_cubes_indexed: a caller's own `params` may carry another padding value or levels
-        # that do not straddle the iso-value the way the constants assume)
-        if (plane is not None and lv is not None and self._fuse and os.environ.get("IVX_MC_LEVELS", "1") != "0"
-                and float(p.pad_value) == 0.0 and lv[0] > 127 and (lv[1] is None or lv[1] > 127)):
-            if lv[1] is None:
-                sel, v_sel = plane, float(lv[0])  # (no second level: any plane will do, both values are the same)
-            else:
-                sel, v_sel = self.reached.at(z0 * self.dy * ((self.dx + 63) // 64) * 8), float(lv[1])
+        lib, levels = L.lib(), self._levels(p, plane, z0)
+        if levels is not None:
+            # (the emit wants a plane in any case: without a second level any will do, both values are the same)
+            sel = levels.sel if levels.has_second else plane
             L.check(lib.ivx_dev_mc_emit_levels(ctypes.byref(p), self._mc_scratch.ptr, sel, ctypes.c_double(0.0),
-                                               ctypes.c_double(float(lv[0])), ctypes.c_double(v_sel), self._tris.ptr, c64(cap), stream),
-                    "mc_emit")
+                                               ctypes.c_double(levels.v_in), ctypes.c_double(levels.v_sel), self._tris.ptr, c64(cap),
+                                               stream), "mc_emit")
         else:
             L.check(lib.ivx_dev_mc_emit(ctypes.byref(p), src, self._mc_scratch.ptr, self._tris.ptr, c64(cap), stream), "mc_emit")
-
-    def _surface_one_launch(self, p, src, plane, z0, cap, stream):
-        """count + offsets + emit of a one-iso piece in ONE kernel (ivx_dev_mc_surface / _levels: no per-word counts, no scan
-        launch, no triangle list); `ivx_dev_mc_total` reads the count afterwards.  Same predicate as `_emit` for the levels form."""
-        lib, lv = L.lib(), self._mask_levels
-        if (plane is not None and lv is not None and self._fuse and os.environ.get("IVX_MC_LEVELS", "1") != "0"
-                and float(p.pad_value) == 0.0 and lv[0] > 127 and (lv[1] is None or lv[1] > 127)):
-            if lv[1] is None:
-                sel, v_sel = plane, float(lv[0])
-            else:
-                sel, v_sel = self.reached.at(z0 * self.dy * ((self.dx + 63) // 64) * 8), float(lv[1])
-            L.check(lib.ivx_dev_mc_surface_levels(ctypes.byref(p), plane, sel, ctypes.c_double(0.0), ctypes.c_double(float(lv[0])),
-                                                  ctypes.c_double(v_sel), self._mc_scratch.ptr, self._tris.ptr, c64(cap), stream), "mc_surface")
-        else:
-            L.check(lib.ivx_dev_mc_surface(ctypes.byref(p), src, plane, self._mc_scratch.ptr, self._tris.ptr, c64(cap), stream), "mc_surface")
 
     def _second_stream(self):
         if self._stream2 is None:
@@ -667,20 +673,7 @@ class DeviceVolume:
                 # the surface outgrew the buffer: take the ordinary path below (it re-counts and re-emits)
         src, plane = self._mc_setup(p, z0)
         n = ctypes.c_int64(0)
-        if self._tris is not None and p.niso == 1 and os.environ.get("IVX_MC_ONE_LAUNCH", "0") == "1":
-            # opt-in (measured slower at 512^3, equal at 1024^3: csrc/k_mc.hip, k_mc_fused): the whole surface in ONE launch
-            # (count, output offsets by a look-back across the workgroups, emit); the count is read afterwards and only a
-            # surface that outgrew the buffer is emitted again
-            cap = self._tris.nbytes // 36
-            with self.timer.span("mc_emit"):
-                self._surface_one_launch(p, src, plane, z0, cap, self.stream)
-            L.check(lib.ivx_dev_mc_total(ctypes.byref(p), self._mc_scratch.ptr, ctypes.byref(n), self.stream), "mc_total")
-            nt = n.value
-            if nt > cap:
-                self._tris.close()
-                self._tris = DeviceBuffer(int(nt * 36 * 1.25) + 4096)
-                self._surface_one_launch(p, src, plane, z0, nt, self.stream)
-        elif self._tris is not None:
+        if self._tris is not None:
             # steady state: the triangle buffer of the previous call gives a capacity, so count, list and emit are queued
             # back to back and the count is read afterwards (no host round trip between the two halves)
             cap = self._tris.nbytes // 36
@@ -731,13 +724,10 @@ class DeviceVolume:
                         "mc_count")
             else:
                 L.check(lib.ivx_dev_mc_count(ctypes.byref(p), src, self._mc_scratch.ptr, ctypes.byref(nt), self.stream), "mc_count")
-        # the mask's bytes known through the pipeline's planes (see _emit): neither the strictly-inside plane nor a vertex
-        # needs a voxel
-        lv = self._mask_levels
-        levels = (plane is not None and lv is not None and self._fuse and os.environ.get("IVX_MC_LEVELS", "1") != "0"
-                  and float(p.pad_value) == 0.0 and lv[0] > 127 and (lv[1] is None or lv[1] > 127))
+        # the mask's bytes known through the pipeline's planes: neither the strictly-inside plane nor a vertex needs a voxel
+        levels = self._levels(p, plane, z0)
         with self.timer.span("mci_count"):
-            if levels:
+            if levels is not None:
                 L.check(lib.ivx_dev_mc_indexed_count_levels(ctypes.byref(p), self._mc_scratch.ptr, ctypes.byref(nv), self.stream),
                         "mc_indexed_count")
             else:
@@ -750,13 +740,9 @@ class DeviceVolume:
                     buf.close()
                 setattr(self, name, DeviceBuffer(int(need * 1.25) + 4096))
         with self.timer.span("mci_emit"):
-            if levels:
-                if lv[1] is None:
-                    sel, v_sel = None, float(lv[0])
-                else:
-                    sel, v_sel = self.reached.at(z0 * self.dy * ((self.dx + 63) // 64) * 8), float(lv[1])
-                L.check(lib.ivx_dev_mc_indexed_emit_levels(ctypes.byref(p), self._mc_scratch.ptr, sel, ctypes.c_double(0.0),
-                                                           ctypes.c_double(float(lv[0])), ctypes.c_double(v_sel), self._verts.ptr,
+            if levels is not None:
+                L.check(lib.ivx_dev_mc_indexed_emit_levels(ctypes.byref(p), self._mc_scratch.ptr, levels.sel, ctypes.c_double(0.0),
+                                                           ctypes.c_double(levels.v_in), ctypes.c_double(levels.v_sel), self._verts.ptr,
                                                            c64(nv.value), self._faces.ptr, c64(nt.value), self.stream),
                         "mc_indexed_emit")
             else:

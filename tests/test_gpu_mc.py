@@ -154,11 +154,10 @@ def test_indexed_mesh_is_the_merged_soup(ivxlib, oracle, case):
 
 
 @pytest.mark.parametrize("dtype", [np.uint8, np.int16])
-def test_single_launch_surface_equals_count_list_emit_and_the_oracle(ivxlib, oracle, monkeypatch, dtype):
-    """ivx_dev_mc_surface (k_mc_fused: count, look-back offsets and emit in one launch) against the four-launch path and the
-    oracle, soup for soup: dense binary noise (thousands of triangles per workgroup -> several LDS windows, every output
-    phase of the 16-byte stores), padded and unpadded pieces, rows that are not whole words, many workgroups (look-back
-    across more than 64 predecessors)."""
+def test_dense_noise_partial_words_unpadded_pieces_many_workgroups(ivxlib, oracle, dtype):
+    """count + list + emit against the oracle, soup for soup: dense binary noise (thousands of triangles per workgroup: several
+    rounds of the list's cell records, emit chunks that begin anywhere in a cell word), padded and unpadded pieces, rows that are
+    not whole words, many workgroups."""
     from invesalius3_amd import surface_process as sp
     rng = np.random.default_rng(11)
     for shape, pads, dens in [((12, 40, 200), (True, True, True), 0.5), ((5, 33, 130), (False, False, False), 0.5),
@@ -171,29 +170,119 @@ def test_single_launch_surface_equals_count_list_emit_and_the_oracle(ivxlib, ora
             a = np.where(rng.random(shape) < dens, rng.integers(300, 2000, shape), rng.integers(-1000, 299, shape)).astype(np.int16)
             iso, padv = 299.5, float(np.iinfo(np.int16).min)
         args = ((0.5, 0.75, 2.0), [iso], 7, *pads, padv, int(pads[0] and pads[1]))
-        monkeypatch.setenv("IVX_MC_ONE_LAUNCH", "1")
-        new = sp.marching_cubes(a, *args)
-        monkeypatch.setenv("IVX_MC_ONE_LAUNCH", "0")
-        old = sp.marching_cubes(a, *args)
-        monkeypatch.delenv("IVX_MC_ONE_LAUNCH")
-        assert len(new) > 0
-        _cmp(new, old)
-        _cmp(new, oracle.marching_cubes(a, *args))
+        got = sp.marching_cubes(a, *args)
+        assert len(got) > 0
+        _cmp(got, oracle.marching_cubes(a, *args))
 
 
-def test_single_launch_surface_that_outgrows_its_buffer(ivxlib, oracle, monkeypatch):
-    """A resident volume's triangle buffer comes from the previous call: a surface that outgrew it is written up to the
-    capacity (nothing past it), the count says so, and the second launch into a larger buffer gives the whole soup."""
+def test_resident_surface_that_outgrows_its_buffer(ivxlib, oracle):
+    """A resident volume's triangle buffer comes from the previous call, and count, list and emit are queued into it before the
+    count is known: a surface that outgrew it is written up to the capacity (nothing past it), the total says so, and the second
+    emit into a larger buffer gives the whole soup."""
     from invesalius3_amd.device import DeviceVolume
-    monkeypatch.setenv("IVX_MC_ONE_LAUNCH", "1")  # (opt-in path: measured slower than count + list + emit at 512^3)
     rng = np.random.default_rng(12)
     img = rng.integers(-1000, 1000, (40, 64, 128)).astype(np.int16)
-    vol = DeviceVolume(img)
-    for lo in (990, 0, 600, -500):  # sparse -> dense (outgrows) -> sparser (fits) -> densest
-        vol.threshold(lo, 3071)
-        got = vol.marching_cubes(from_binary=True, download=True)
+    los = (990, 0, 600, -500)  # sparse -> dense (outgrows) -> sparser (fits) -> densest
+    want = {}
+    for lo in los:
         mask = np.zeros(tuple(s + 1 for s in img.shape), np.uint8)
         oracle.set_mask_threshold_volume(mask, img, (lo, 3071))
-        want = oracle.create_surface_piece(None, mask, slice(0, img.shape[0]), (1.0, 1.0, 1.0), 0, 0, True)
-        _cmp(got, want)
+        want[lo] = oracle.create_surface_piece(None, mask, slice(0, img.shape[0]), (1.0, 1.0, 1.0), 0, 0, True)
+    # the first buffer has room for 1.25 times the first surface (and 4 KiB): the second surface does not fit in it
+    assert len(want[0]) * 36 > int(len(want[990]) * 36 * 1.25) + 4096
+    vol = DeviceVolume(img)
+    for lo in los:
+        before = vol._tris.nbytes if vol._tris is not None else None
+        vol.threshold(lo, 3071)
+        got = vol.marching_cubes(from_binary=True, download=True)
+        _cmp(got, want[lo])
+        if lo == 0:  # emitted into the first call's buffer, which was too small, and again into a new one
+            assert before < len(want[0]) * 36 <= vol._tris.nbytes
+        elif lo == 600:  # steady state: the buffer is kept
+            assert vol._tris.nbytes == before >= len(want[600]) * 36
     vol.close()
+
+
+def _mc_piece(L, a, isos, pad_value):
+    """(params, scratch, voxels on the device) of the fully padded piece `a`"""
+    import ctypes
+    from invesalius3_amd.device import DeviceBuffer
+    p = L.McParams(dtype=L.DT[a.dtype], pad_xy=1, pad_bottom=1, pad_top=1, vtk_pz=1, niso=len(isos), nz=a.shape[0], ny=a.shape[1],
+                   nx=a.shape[2], roi_start=0, pad_value=pad_value, spacing=(ctypes.c_double * 3)(1, 1, 1),
+                   iso=(ctypes.c_double * 2)(*(list(isos) + [0.0])[:2]))
+    nb = ctypes.c_size_t(0)
+    L.check(L.lib().ivx_dev_mc_scratch_bytes(ctypes.byref(p), ctypes.byref(nb)))
+    d_a = DeviceBuffer(a.nbytes)
+    d_a.upload(a)
+    return p, DeviceBuffer(nb.value), d_a
+
+
+def test_a_triangle_list_overwritten_by_another_piece_is_built_again(ivxlib, oracle):
+    """Two pieces with a scratch each on one stream, so they share the stream's list buffer: count A, list A, count B, emit B
+    (B's list goes where A's was), emit A (must not take the buffer for its own list any more)."""
+    import ctypes
+    from invesalius3_amd import _lib as L
+    from invesalius3_amd.device import DeviceBuffer
+    lib, c64, rng = L.lib(), ctypes.c_int64, np.random.default_rng(51)
+    pieces = []
+    for shape in ((6, 20, 70), (5, 17, 130)):
+        a = rng.integers(0, 256, shape).astype(np.uint8)
+        ref = oracle.marching_cubes(a, (1.0, 1.0, 1.0), [127.0], 0, True, True, True, 0.0, 1)
+        assert len(ref) > 256
+        pieces.append((a, ref) + _mc_piece(L, a, [127.0], 0.0))
+    (_, ref_a, p_a, s_a, d_a), (_, ref_b, p_b, s_b, d_b) = pieces
+    cap = max(len(ref_a), len(ref_b))  # (A's list has room for either surface: B's does not need a larger buffer)
+    t_a, t_b = DeviceBuffer(len(ref_a) * 36), DeviceBuffer(len(ref_b) * 36)
+    n = c64(0)
+    L.check(lib.ivx_dev_mc_count(ctypes.byref(p_a), d_a.ptr, s_a.ptr, ctypes.byref(n), None))
+    assert n.value == len(ref_a)
+    L.check(lib.ivx_dev_mc_list(ctypes.byref(p_a), s_a.ptr, c64(cap), None))
+    L.check(lib.ivx_dev_mc_count(ctypes.byref(p_b), d_b.ptr, s_b.ptr, ctypes.byref(n), None))
+    assert n.value == len(ref_b)
+    L.check(lib.ivx_dev_mc_emit(ctypes.byref(p_b), d_b.ptr, s_b.ptr, t_b.ptr, c64(len(ref_b)), None))
+    L.check(lib.ivx_dev_mc_emit(ctypes.byref(p_a), d_a.ptr, s_a.ptr, t_a.ptr, c64(len(ref_a)), None))
+    L.check(lib.ivx_device_synchronize())
+    _cmp(t_b.download(ref_b.shape, np.float32), ref_b)
+    _cmp(t_a.download(ref_a.shape, np.float32), ref_a)
+    for d in (s_a, d_a, s_b, d_b, t_a, t_b):
+        d.close()
+
+
+def test_indexed_calls_behind_a_queue_only_count_need_the_total(ivxlib, oracle):
+    """A two-iso piece on a scratch that another piece was counted into before: after ivx_dev_mc_count_async the place where
+    iso 0's triangles end is not known on the host until ivx_dev_mc_total has read it, and ivx_dev_mc_indexed_emit says so
+    (a host-side refusal) instead of splitting the faces where the earlier piece's triangles ended."""
+    import ctypes
+    from invesalius3_amd import _lib as L
+    from invesalius3_amd.device import DeviceBuffer
+    lib, c64, rng = L.lib(), ctypes.c_int64, np.random.default_rng(52)
+    isos, padv = [0.5, 300.5], float(np.iinfo(np.int16).min)
+    earlier = rng.integers(-1000, 1000, (5, 12, 66)).astype(np.int16)
+    a = rng.integers(-1000, 1000, (5, 12, 66)).astype(np.int16)
+    soup = oracle.marching_cubes(a, (1.0, 1.0, 1.0), isos, 0, True, True, True, padv, 1)
+    split = len(oracle.marching_cubes(a, (1.0, 1.0, 1.0), isos[:1], 0, True, True, True, padv, 1))
+    split_earlier = len(oracle.marching_cubes(earlier, (1.0, 1.0, 1.0), isos[:1], 0, True, True, True, padv, 1))
+    assert 0 < split < len(soup) and split_earlier != split
+    p, d_s, d_a = _mc_piece(L, a, isos, padv)
+    n, nv = c64(0), c64(0)
+    d_a.upload(earlier)
+    L.check(lib.ivx_dev_mc_count(ctypes.byref(p), d_a.ptr, d_s.ptr, ctypes.byref(n), None))  # (reads the total: a split is known)
+    d_a.upload(a)
+    L.check(lib.ivx_dev_mc_count_async(ctypes.byref(p), d_a.ptr, d_s.ptr, None))
+    L.check(lib.ivx_dev_mc_indexed_count(ctypes.byref(p), d_a.ptr, d_s.ptr, ctypes.byref(nv), None))
+    d_v, d_f = DeviceBuffer(nv.value * 12), DeviceBuffer(len(soup) * 12)
+    emit = lambda: L.check(lib.ivx_dev_mc_indexed_emit(ctypes.byref(p), d_a.ptr, d_s.ptr, d_v.ptr, c64(nv.value), d_f.ptr,
+                                                       c64(len(soup)), None))
+    with pytest.raises(TypeError, match="ivx_dev_mc_indexed_emit must follow ivx_dev_mc_count"):
+        emit()
+    L.check(lib.ivx_dev_mc_total(ctypes.byref(p), d_s.ptr, ctypes.byref(n), None))
+    assert n.value == len(soup)
+    nv2 = c64(0)
+    L.check(lib.ivx_dev_mc_indexed_count(ctypes.byref(p), d_a.ptr, d_s.ptr, ctypes.byref(nv2), None))
+    assert nv2.value == nv.value
+    emit()
+    L.check(lib.ivx_device_synchronize())
+    verts, faces = d_v.download((nv.value, 3), np.float32), d_f.download((len(soup), 3), np.int32)
+    _cmp(verts[faces], soup)
+    for d in (d_s, d_a, d_v, d_f):
+        d.close()

@@ -17,7 +17,7 @@ def _cmp(got, ref):
 
 
 def _grid(shape, pxy, pb, pt):
-    """(NZ, NY, NX, WC) of the padded point grid, as make_geom in csrc/k_mc.hip"""
+    """(NZ, NY, NX, WC) of the padded point grid, as make_geom in csrc/mc_common.h"""
     nz, ny, nx = shape
     NZ, NY, NX = nz + int(pb) + int(pt), ny + 2 * int(pxy), nx + 2 * int(pxy)
     return NZ, NY, NX, (NX - 1 + 63) // 64
@@ -89,7 +89,7 @@ def test_padding_inside_the_surface(ivxlib, oracle, nx, isos, padv):
 
 # ---- the benchmark's own path ----------------------------------------------------------------------------------------------
 @gpu
-@pytest.mark.parametrize("env", [{}, {"IVX_MC_LEVELS": "0"}, {"IVX_MC_ONE_LAUNCH": "1"}])
+@pytest.mark.parametrize("env", [{}, {"IVX_MC_LEVELS": "0"}])
 @pytest.mark.parametrize("shape", [(20, 48, 128), (5, 33, 64)])
 def test_resident_threshold_grow_surface(ivxlib, oracle, monkeypatch, shape, env):
     """DeviceVolume: threshold (inside plane written by the same pass), 26-neighbour region growing that selects with 254,

@@ -22,8 +22,7 @@ timeout -k 5 900 python bench.py --full < /dev/null > $O/bench.json 2> $O/bench.
 timeout -k 5 300 python bench.py --full --scaling strong --no-others --no-cpu < /dev/null > $O/bench_strong_1gpu.json 2> $O/bench_strong_1gpu.err
 timeout -k 5 600 python tools/bench_host.py < /dev/null > $O/bench_host_512.json 2> $O/bench_host_512.err
 timeout -k 5 600 python tools/bench_resident.py < /dev/null > $O/bench_host_resident_512.json 2> $O/bench_host_resident_512.err  # the same calls with the arrays bound
-# the opt-in paths kept for A/B: marching cubes in one launch, the IFT level chain without link records
-IVX_MC_ONE_LAUNCH=1 timeout -k 5 300 python bench.py --full --no-others --no-cpu < /dev/null > $O/bench_mc_one_launch.json 2> /dev/null
+# the opt-in path kept for A/B: the IFT level chain without link records
 IVX_WS_LINKS=0 timeout -k 5 300 python bench.py --full --config watershed --size 512 --no-cpu < /dev/null > $O/bench_watershed_512_nolinks.json 2> /dev/null
 timeout -k 5 300 python bench.py --full --config mip < /dev/null > $O/bench_mip.json 2> $O/bench_mip.err
 timeout -k 5 120 python bench.py --dry-comm < /dev/null > $O/dry_comm.json 2> $O/dry_comm.err
@@ -59,7 +58,7 @@ timeout -k 5 600 python bench.py --full --config sharded2048 < /dev/null > $O/be
 find $O -name "*_kernel_trace.csv" -size +8M -delete
 find $O -name "*_counter_collection.csv" -size +8M -delete
 cat $O/gpu_tests.txt 2>/dev/null
-for f in bench bench_strong_1gpu bench_mc_one_launch bench_mip bench_surface_tail bench_watershed_512 bench_watershed_512_nolinks bench_watershed_sk_512 bench_watershed_1024 bench_watershed_sk_1024 bench_sharded2048_1gpu; do
+for f in bench bench_strong_1gpu bench_mip bench_surface_tail bench_watershed_512 bench_watershed_512_nolinks bench_watershed_sk_512 bench_watershed_1024 bench_watershed_sk_1024 bench_sharded2048_1gpu; do
 python - $O/$f.json $f <<'PY'
 import json,sys
 try:
