@@ -37,10 +37,9 @@
 //        k_sk_rank_pairs (pairwise ranks) | k_sk_merge_pass (lists of more than 128 chunks) -> k_sk_assign_ranked.  The EARLY
 //        part of a level is sorted on a SIDE STREAM while the level underneath floods; behind that flood only the late part
 //        is keyed and ONE launch stamps everything (k_sk_split_assign: late pairs ranked by brute force in LDS).
-//        k_sk_gen0 (the whole of it in one launch behind a device-wide barrier) is an opt-in that measured slower.
 //        Then the level's rounds in ONE resident launch (k_sk_level: a round boundary is a hand-over through a polled control
-//        word; IVX_SK_PERSIST=0: k_sk_round launches in batches).  A
-//      generation is at most two rounds: A -- the frontier stamps its unstamped neighbours of value c with the next
+//        word).
+//      A generation is at most two rounds: A -- the frontier stamps its unstamped neighbours of value c with the next
 //      generation and offers its own stamp to the basins it touches (atomicMin at the root); B -- only if a basin was
 //      stamped: the level's drained voxels whose basin carries this generation's stamp hand it, one generation later, to
 //      their unstamped neighbours of value c.  Two shortcuts: a RUN of consecutive small levels is
@@ -64,45 +63,37 @@ namespace {
 constexpr unsigned long long TINF = ~0ull;
 constexpr unsigned long long GEN1 = 1ull << 32;
 
-// The frontier loop of a level runs without the host: every round is one launch of k_sk_round over a fixed grid; the
-// last workgroup to finish turns the counters into the next round's input (phase B, or the next generation, or "level
-// exhausted").  The host queues rounds in batches and reads {done, gen, rounds, n_in} once per batch.
+// The frontier loop of a level runs without the host, in one resident launch (k_sk_level): the last workgroup to finish a
+// round turns the counters into the next round's input (phase B, or the next generation, or "level exhausted").  The host
+// reads {done, gen} when it needs the generation counter -- not between consecutive levels (gnext).
 struct SkState {
-    uint32_t done;      // level exhausted: further rounds return at once   }
-    uint32_t gen;       // G of the voxels on the current input list        } read by the host once per batch (mailbox)
-    uint32_t rounds;    // rounds that did work (statistics)                }
-    uint32_t n_in;      // entries of the current frontier                  }
-    uint32_t phase;     // 0: the coming round is A (frontier), 1: B (basins stamped in this generation relay)
-    uint32_t in_sel;    // which of the two lists is the frontier (the other collects the next generation)
-    uint32_t n_next;    // voxels of the next generation so far
-    uint32_t n_stamped; // basins stamped for the first time by this generation's round A
-    uint32_t ticket;    // workgroups of the running round that have finished
+    uint32_t done;      // level exhausted (3: a resident launch gave up)   } read by the host (mailbox)
+    uint32_t gen;       // G of the level's first, then last, generation    }
+    uint32_t rounds;    // rounds that did work (statistics)
+    uint32_t pad0[3];
+    uint32_t n_next;    // voxels of the next generation so far: every working wave of a round adds to it
+    uint32_t pad1[2];
     uint32_t mixed;     // adjacent tied markers with different labels (see TIES)
     uint32_t gens;      // generation steps (statistics)
     uint32_t brounds;   // B rounds (statistics)
     uint32_t gnext;     // first generation of the NEXT level (= gen + 1 when a level's loop ends): a chain of levels needs no host read
-    // what a workgroup needs to decide whether it takes part in a launch, in ONE word (read with one atomic load):
-    // bits 0..31 entries of the frontier, 32 phase, 33 which list, 34..63 sequence number of the launch it describes
-    unsigned long long ctl;
+    uint32_t pad2[3];
     // k_sk_level's ticket (round 6): bits 48.. workgroups of the running round that have finished, 32..47 how many of them
     // stamped a basin for the first time, 0..31 list entries they appended -- the workgroup that closes the round learns all three
-    // from the ONE returning atomic that tells it it is the last (before: ticket, then a dependent trip for the two counters)
+    // from the ONE returning atomic that tells it it is the last (before: ticket, then a dependent trip for the two counters).
+    // Every word of this line keeps the offset the resident launch was tuned and measured with (the padding is where the
+    // per-round launches' words were): the ticket on the second 64 bytes, away from n_next.  The fields packed into the first
+    // 40 bytes measured 45.5 against 44.5 ms at 512^3 in one sitting of three alternating calls each (spread of a sitting: 1 ms).
     unsigned long long tick64;
-    uint32_t pad1[14];
+    uint32_t pad3[14];
     // the resident launch (k_sk_level) polls its control word from every workgroup: a line of its own, away from the counters
     // the working workgroups add to
     unsigned long long pctl;
     uint32_t ticks[16]; // IVX_WS_TRACE: workgroup 0's time per part of a round, summed over the flood (wall_clock64 ticks of 10 ns)
-    uint32_t joined;    // k_sk_level<.., LOCAL>: workgroups that found themselves on the chosen XCD (their ids: the order they joined in)
-    uint32_t arrived;   //                        workgroups of the launch that have looked (all of them: `joined` is final then)
-    uint32_t pad2[12];
+    uint32_t pad4[14];
 };
-static_assert(sizeof(SkState) == 256 && offsetof(SkState, pctl) == 128, "ctl is 8-byte aligned, pctl starts a 128-byte line");
-
-__host__ __device__ inline unsigned long long sk_ctl(uint32_t seq, uint32_t in_sel, uint32_t phase, uint32_t n_in) {
-    return ((unsigned long long)(seq & 0x3FFFFFFFu) << 34) | ((unsigned long long)(in_sel & 1u) << 33) |
-           ((unsigned long long)(phase & 1u) << 32) | n_in;
-}
+static_assert(sizeof(SkState) == 256 && offsetof(SkState, n_next) == 24 && offsetof(SkState, tick64) == 64 && offsetof(SkState, pctl) == 128,
+              "the list counter and the ticket on different 64-byte halves, pctl starts a 128-byte line");
 
 // control word of the resident launch: bits 0..31 entries of the frontier, 32 phase, 33 which list, 34..53 generations begun
 // since the level's first word (a solo stretch, below, begins several between two words), 54..63 sequence number of the word
@@ -115,6 +106,14 @@ __host__ __device__ inline unsigned long long sk_pctl(uint32_t seq, uint32_t gen
 struct SkLists {
     uint32_t *l[2];
 };
+
+// A level begins (one thread of the launch that stamps its generation 0): the frontier loop starts from list 0, phase A, with
+// the level's `cnt` generation-0 voxels at generation gbase; nothing appended, nobody arrived, the resident launch's first word
+__device__ __forceinline__ void sk_begin_level(SkState *st, uint32_t gbase, uint32_t cnt) {
+    st->done = 0; st->gen = gbase;
+    st->n_next = 0; st->tick64 = 0;
+    st->pctl = sk_pctl(0, 0, 0, 0, cnt);
+}
 
 struct SkKindPred {
     const uint8_t *kind;
@@ -312,18 +311,11 @@ template <typename MT>
 __global__ __launch_bounds__(256) void k_sk_split_assign(const unsigned long long *__restrict__ ekey, const uint32_t *__restrict__ evl, uint32_t cnt_e,
                                                          const unsigned long long *__restrict__ lkey, const uint32_t *__restrict__ lvl, uint32_t cnt_l,
                                                          const MT *__restrict__ mk, unsigned long long *tau, int32_t *runlabel,
-                                                         uint32_t *__restrict__ front, uint32_t roff, uint32_t gbase, uint32_t seq, SkState *st) {
+                                                         uint32_t *__restrict__ front, uint32_t roff, uint32_t gbase, SkState *st) {
     extern __shared__ unsigned long long s_dyn[]; // cnt_l keys, then cnt_l voxels
     const uint32_t nwe = (cnt_e + 255u) / 256u, tid = threadIdx.x;
     if (gbase == 0) gbase = __hip_atomic_load(&st->gnext, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (blockIdx.x == 0 && tid == 0) {
-        const uint32_t cnt = cnt_e + cnt_l;
-        st->done = 0; st->gen = gbase; st->n_in = cnt;
-        st->phase = 0; st->in_sel = 0;
-        st->n_next = 0; st->n_stamped = 0; st->ticket = 0; st->tick64 = 0; st->joined = 0; st->arrived = 0;
-        st->ctl = sk_ctl(seq, 0, 0, cnt);
-        st->pctl = sk_pctl(0, 0, 0, 0, cnt);
-    }
+    if (blockIdx.x == 0 && tid == 0) sk_begin_level(st, gbase, cnt_e + cnt_l);
     uint32_t p, pos;
     unsigned long long K;
     if (blockIdx.x < nwe) {
@@ -374,264 +366,11 @@ __global__ __launch_bounds__(256) void k_sk_split_assign(const unsigned long lon
     front[pos] = p;
 }
 
-// ---- generation 0 of a level in ONE launch (k_sk_gen0): keys -> sorted -> stamps.
-// A level's generation 0 is ~5 x 10^4 (512^3) to ~5 x 10^5 (1024^3) voxels, once per level, 170 levels per flood, every one
-// on the flood's critical path.  As k_sk_keys + a library radix sort (one block sort + ~6 merge launches at this size) +
-// k_sk_assign that was 10 dependent launches at the dispatch floor, ~80 us per level.  Here every workgroup computes the keys
-// of one chunk, sorts (key, voxel) pairs in LDS (bitonic), publishes the sorted KEYS, and -- behind one device-wide barrier --
-// ranks its own keys against every other chunk staged through LDS: position = own index + sum over the other chunks of the
-// keys below (ties: the chunk with the lower index first), which is the position in the sorted whole.  Both lists are sorted,
-// so a lane's consecutive keys continue where the previous one stopped (a gallop of ~2 probes instead of a 12-probe search).
-// The order among equal keys is (chunk, voxel): it never matters -- equal keys carry one label (see TIME above) -- but it is
-// a function of the level's list alone.  All workgroups must be resident (one per compute unit, 2^20 voxels at most; above:
-// the launches of sk_sort_big below); a lost barrier ends the launch with ctl->fail = 1, never a hang.
-constexpr int G0_T = 1024;
-struct SkG0Ctl {
-    uint32_t arrive[2]; // the two barriers of a launch
-    uint32_t nmark;     // markers among the level's generation 0
-    uint32_t exits;     // workgroups that have left: the last one clears the words above for the next launch
-    uint32_t fail;      // a barrier timed out (sticky for the flood)
-    uint32_t ticks[8];  // workgroup 0's time per phase, summed over the flood's launches (wall_clock64 ticks of 10 ns; IVX_WS_TRACE prints them)
-    uint32_t pad[19];
-};
-static_assert(sizeof(SkG0Ctl) == 128, "one line");
-
-// bitonic sort of n2 (a power of two) (key, voxel) pairs in LDS by all threads of the workgroup
-__device__ __forceinline__ void sk_bitonic(unsigned long long *s_key, uint32_t *s_val, uint32_t n2) {
-    for (uint32_t k2 = 2; k2 <= n2; k2 <<= 1)
-        for (uint32_t j = k2 >> 1, lj = 31u - __clz(k2 >> 1); j > 0; j >>= 1, lj--) { // (shifts: j is not a compile-time constant)
-            for (uint32_t t = threadIdx.x; t < (n2 >> 1); t += blockDim.x) {
-                const uint32_t lo = ((t >> lj) << (lj + 1)) | (t & (j - 1u)), hi = lo + j;
-                const bool up = ((lo & k2) == 0);
-                const unsigned long long ka = s_key[lo], kb = s_key[hi];
-                const uint32_t va = s_val[lo], vb = s_val[hi];
-                if (sk_pair_less(kb, vb, ka, va) == up) {
-                    s_key[lo] = kb; s_key[hi] = ka;
-                    s_val[lo] = vb; s_val[hi] = va;
-                }
-            }
-            __syncthreads();
-        }
-}
-
-// key of a generation-0 voxel (see k_sk_keys)
-template <int CONN, typename MT>
-__device__ __forceinline__ unsigned long long sk_key_of(const WsGeom &g, const uint16_t *__restrict__ C, const MT *__restrict__ mk,
-                                                        const uint16_t *__restrict__ I, const uint32_t *__restrict__ comp,
-                                                        const unsigned long long *tau, uint32_t p, uint32_t c, bool *marker) {
-    *marker = mk[p] != 0;
-    if (*marker) return p;
-    unsigned long long K = TINF;
-    const int64_t z = p / g.hw, r = p - z * g.hw, y = r / g.w, x = r - y * g.w;
-#pragma unroll
-    for (int k = 0; k < 27; k++) {
-        if (!has_off<CONN>(g.smask, k)) continue;
-        const int dz = k / 9 - 1, dy = (k / 3) % 3 - 1, dx = k % 3 - 1;
-        const int64_t Z = z + dz, Y = y + dy, X = x + dx;
-        if ((uint64_t)X >= (uint64_t)g.w || (uint64_t)Y >= (uint64_t)g.h || (uint64_t)Z >= (uint64_t)g.d) continue;
-        const int64_t q = (int64_t)p + dz * g.hw + dy * g.w + dx;
-        const uint32_t qc = C[q];
-        if (qc < c) K = min(K, ld64(&tau[(uint32_t)I[q] < qc ? comp[q] : (uint32_t)q]));
-    }
-    return K;
-}
-
-constexpr uint32_t G0_SPIN_LIMIT = 1u << 21;
-
-// device-wide barrier of a launch whose workgroups are all resident.  What a workgroup published before it (agent-scope,
-// write-through stores) has been acknowledged when it arrives; what it reads after it, it reads with agent-scope loads.
-__device__ __forceinline__ bool sk_g0_barrier(uint32_t *word, uint32_t nwg, uint32_t *fail, uint32_t *s_flag) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t ok = 1;
-        __hip_atomic_fetch_add(word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        for (uint32_t spins = 0; __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < nwg; spins++) {
-            if (spins > G0_SPIN_LIMIT) {
-                __hip_atomic_store(fail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                ok = 0;
-                break;
-            }
-            __builtin_amdgcn_s_sleep(4);
-        }
-        *s_flag = ok;
-    }
-    __syncthreads();
-    const bool ok = *s_flag != 0;
-    __syncthreads(); // (the flag word is reused by the next barrier)
-    return ok;
-}
-
-// number of staged keys that sort before K (le: or equal to it), continuing from `from` keys already known to (gallop + bisection)
-__device__ __forceinline__ uint32_t sk_count_from(const unsigned long long *sb, uint32_t ch, uint32_t from, unsigned long long K, bool le) {
-    uint32_t lo = from, step = 1;
-    while (lo + step <= ch) {
-        const unsigned long long x = sb[lo + step - 1];
-        if (!(le ? x <= K : x < K)) break;
-        lo += step;
-        step <<= 1;
-    }
-    for (step >>= 1; step; step >>= 1)
-        if (lo + step <= ch) {
-            const unsigned long long x = sb[lo + step - 1];
-            if (le ? x <= K : x < K) lo += step;
-        }
-    return lo;
-}
-
-// the same count by bisection over the whole chunk (ch a power of two): a lane's first key
-__device__ __forceinline__ uint32_t sk_count_bisect(const unsigned long long *sb, uint32_t ch, unsigned long long K, bool le) {
-    uint32_t lo = 0;
-    for (uint32_t step = ch >> 1; step; step >>= 1) {
-        const unsigned long long x = sb[lo + step - 1];
-        if (le ? x <= K : x < K) lo += step;
-    }
-    const unsigned long long x = sb[lo];
-    return lo + ((le ? x <= K : x < K) ? 1u : 0u);
-}
-
-template <int CONN, typename MT, int IPT>
-__global__ __launch_bounds__(G0_T) void k_sk_gen0(WsGeom g, const uint16_t *__restrict__ C, const MT *__restrict__ mk,
-                                                  const uint16_t *__restrict__ I, const uint32_t *__restrict__ comp, unsigned long long *tau,
-                                                  const uint32_t *__restrict__ elist, unsigned long long *ckey, int32_t *runlabel,
-                                                  uint32_t *front, uint32_t cnt, uint32_t ch, uint32_t c, uint32_t roff, uint32_t gbase,
-                                                  uint32_t seq, SkState *st, SkG0Ctl *ctl) {
-    constexpr int CAP = G0_T * IPT;
-    __shared__ unsigned long long s_key[CAP];
-    __shared__ uint32_t s_val[CAP];
-    __shared__ unsigned long long s_b[2][CAP];
-    __shared__ uint32_t s_flag, s_nm;
-    const uint32_t tid = threadIdx.x, chunk = blockIdx.x, nwg = gridDim.x;
-    const uint32_t base = chunk * ch, nown = min(ch, cnt - base);
-    // gbase 0: the level follows another one of the same chain on the device (nobody writes gnext during this launch)
-    if (gbase == 0) gbase = __hip_atomic_load(&st->gnext, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (chunk == 0 && tid == 0) { // the level's frontier loop starts from list 0, phase A (as k_sk_assign)
-        st->done = 0; st->gen = gbase; st->n_in = cnt;
-        st->phase = 0; st->in_sel = 0;
-        st->n_next = 0; st->n_stamped = 0; st->ticket = 0; st->tick64 = 0; st->joined = 0; st->arrived = 0;
-        st->ctl = sk_ctl(seq, 0, 0, cnt);
-        st->pctl = sk_pctl(0, 0, 0, 0, cnt);
-    }
-    if (tid == 0) s_nm = 0;
-    __syncthreads();
-    unsigned long long tk = chunk == 0 && tid == 0 ? wall_clock64() : 0ull;
-    auto tick = [&](int slot) {
-        if (chunk == 0 && tid == 0) {
-            const unsigned long long now = wall_clock64();
-            atomicAdd(&ctl->ticks[slot], (uint32_t)(now - tk));
-            tk = now;
-        }
-    };
-    // ---- keys of this chunk, sorted in LDS
-    uint32_t n2 = 1;
-    while (n2 < nown) n2 <<= 1;
-    uint32_t nm = 0;
-    for (uint32_t i = tid; i < n2; i += G0_T) {
-        unsigned long long K = TINF;
-        uint32_t p = 0xFFFFFFFFu;
-        if (i < nown) {
-            p = elist[base + i];
-            bool marker;
-            K = sk_key_of<CONN, MT>(g, C, mk, I, comp, tau, p, c, &marker);
-            nm += marker;
-        }
-        s_key[i] = K;
-        s_val[i] = p;
-    }
-    if (nm) atomicAdd(&s_nm, nm);
-    __syncthreads();
-    if (tid == 0 && s_nm && nwg > 1) __hip_atomic_fetch_add(&ctl->nmark, s_nm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    tick(0);
-    sk_bitonic(s_key, s_val, n2);
-    tick(1);
-    uint32_t pos[IPT]; // position of this lane's pairs (sorted positions IPT * tid + k) in the sorted whole
-#pragma unroll
-    for (int k = 0; k < IPT; k++) pos[k] = IPT * tid + k;
-    if (nwg > 1) {
-        for (uint32_t i = tid; i < nown; i += G0_T) __hip_atomic_store(&ckey[base + i], s_key[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (!sk_g0_barrier(&ctl->arrive[0], nwg, &ctl->fail, &s_flag)) return;
-        tick(2);
-        // ---- rank against every other chunk (starting behind the own one: the chunks' readers spread over the chip)
-        unsigned long long pre[IPT];
-        auto fetch = [&](uint32_t oc) {
-            const uint32_t ob = oc * ch, on = min(ch, cnt - ob);
-#pragma unroll
-            for (int e = 0; e < IPT; e++) {
-                const uint32_t i = tid + e * G0_T;
-                pre[e] = i < on ? __hip_atomic_load(&ckey[ob + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : TINF;
-            }
-        };
-        unsigned long long own[IPT];
-#pragma unroll
-        for (int k = 0; k < IPT; k++) own[k] = IPT * tid + k < nown ? s_key[IPT * tid + k] : TINF;
-        uint32_t oc = chunk + 1 == nwg ? 0 : chunk + 1;
-        fetch(oc);
-        int cur = 0;
-        for (uint32_t s = 0; s + 1 < nwg; s++) {
-            unsigned long long *sb = s_b[cur];
-#pragma unroll
-            for (int e = 0; e < IPT; e++)
-                if (tid + e * G0_T < ch) sb[tid + e * G0_T] = pre[e];
-            __syncthreads();
-            const uint32_t this_oc = oc, on = min(ch, cnt - this_oc * ch);
-            oc = oc + 1 == nwg ? 0 : oc + 1;
-            if (s + 2 < nwg) fetch(oc); // in flight during the search
-            const bool le = this_oc < chunk;
-            uint32_t from = 0;
-#pragma unroll
-            for (int k = 0; k < IPT; k++) {
-                if (IPT * tid + k >= nown) break;
-                from = k == 0 ? sk_count_bisect(sb, ch, own[k], le) : sk_count_from(sb, ch, from, own[k], le);
-                pos[k] += min(from, on);
-            }
-            cur ^= 1;
-        }
-        tick(3);
-    }
-    // ---- stamps (G = gbase, R = roff + position), the runs' labels, the first frontier
-    const uint32_t nmark = nwg > 1 ? __hip_atomic_load(&ctl->nmark, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : s_nm;
-    const bool check = nmark >= 2;
-    uint32_t mixed = 0;
-#pragma unroll
-    for (int k = 0; k < IPT; k++) {
-        const uint32_t q = IPT * tid + k;
-        if (q >= nown) break;
-        const uint32_t p = s_val[q];
-        const unsigned long long K = s_key[q];
-        const int m = (int)mk[p];
-        // a run's label: its marker's, or the label of the run its parent belongs to (an earlier level: final)
-        const int32_t l = m ? (int32_t)m : (K == TINF ? 0 : runlabel[(uint32_t)(K & 0xFFFFFFFFull)]);
-        runlabel[roff + pos[k]] = l;
-        tau[p] = ((unsigned long long)gbase << 32) | (unsigned long long)(roff + pos[k]);
-        if (check && nwg > 1) __hip_atomic_store(&front[pos[k]], p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else front[pos[k]] = p;
-        // markers sort first, in raster order: adjacent tied markers of different labels (one chunk: the neighbour is at hand)
-        if (check && nwg == 1 && m && q > 0 && (int)mk[s_val[q - 1]] != m) mixed++;
-    }
-    if (check && nwg > 1) {
-        if (!sk_g0_barrier(&ctl->arrive[1], nwg, &ctl->fail, &s_flag)) return;
-        for (uint32_t r = 1 + chunk * G0_T + tid; r < nmark; r += nwg * G0_T) {
-            const uint32_t p0 = __hip_atomic_load(&front[r - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const uint32_t p1 = __hip_atomic_load(&front[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            mixed += mk[p0] != mk[p1];
-        }
-    }
-    if (mixed) atomicAdd(&st->mixed, mixed);
-    __syncthreads();
-    tick(4);
-    if (tid == 0 && nwg > 1) { // the last workgroup out clears the barrier words for the next launch
-        if (__hip_atomic_fetch_add(&ctl->exits, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nwg - 1) {
-            ctl->arrive[0] = 0; ctl->arrive[1] = 0; ctl->nmark = 0; ctl->exits = 0;
-        }
-    }
-}
-
-// ---- levels of more than 2^20 generation-0 voxels (more chunks than workgroups that are resident at once): the same chunk
-// sort, then merge passes as launches (merge path: every lane finds where its 8 outputs start in the two runs)
+// ---- the chunk sort every generation-0 list starts with (then pairwise ranks, or merge passes as launches: below).
 // 2048 pairs, 256 lanes, eight pairs per lane in registers: a trip through LDS serves up to three compare-exchange steps (the
 // lane fetches the eight pairs whose indices differ in the three bits those steps pair up), 24 trips instead of 66 steps
-// with a barrier each (the plain network, sk_bitonic, is LDS-throughput bound: 30 us per chunk).  One spare slot per eight
-// keeps the strided trips at two-way bank conflicts.
+// with a barrier each (the plain network, one compare-exchange per trip, is LDS-throughput bound: 30 us per chunk).  One spare
+// slot per eight keeps the strided trips at two-way bank conflicts.
 __device__ __forceinline__ uint32_t sc_phys(uint32_t i) { return i + (i >> 3); }
 
 template <int SC_T> // lanes: sorts up to 8 * SC_T pairs (chunks of 512 / 1024 / 2048)
@@ -766,17 +505,11 @@ template <typename MT>
 __global__ __launch_bounds__(256) void k_sk_assign_ranked(const unsigned long long *__restrict__ key, const uint32_t *__restrict__ val,
                                                           const uint32_t *__restrict__ part, uint32_t shares, uint32_t ch, const MT *__restrict__ mk,
                                                           unsigned long long *tau, int32_t *runlabel, uint32_t *__restrict__ front, uint32_t cnt,
-                                                          uint32_t pos_off, uint32_t total, uint32_t roff, uint32_t gbase, uint32_t seq, SkState *st) {
+                                                          uint32_t pos_off, uint32_t total, uint32_t roff, uint32_t gbase, SkState *st) {
     // (cnt entries of a level's `total`, placed from position pos_off on: a level's list may arrive in two sorted parts)
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (gbase == 0) gbase = __hip_atomic_load(&st->gnext, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (i == 0 && pos_off == 0) {
-        st->done = 0; st->gen = gbase; st->n_in = total;
-        st->phase = 0; st->in_sel = 0;
-        st->n_next = 0; st->n_stamped = 0; st->ticket = 0; st->tick64 = 0; st->joined = 0; st->arrived = 0;
-        st->ctl = sk_ctl(seq, 0, 0, total);
-        st->pctl = sk_pctl(0, 0, 0, 0, total);
-    }
+    if (i == 0 && pos_off == 0) sk_begin_level(st, gbase, total);
     if (i >= cnt) return;
     const uint32_t p = val[i];
     uint32_t pos = pos_off + (i & (ch - 1u)); // position inside its chunk + the keys below it in the other chunks (one plane per share)
@@ -880,31 +613,17 @@ struct SkStage {
     uint32_t pushed, stamped; // what this workgroup appended / stamped in the running round (k_sk_level's ticket carries them)
 };
 
-// LOCAL (k_sk_level on ONE XCD, see there): what crosses workgroups is written with workgroup-scope operations -- performed in
-// the XCD's L2, where the line STAYS -- instead of agent-scope ones (write-through to the fabric, line dropped); loads keep the
-// agent-scope form (L1 bypassed, served by the L2) either way.
-template <bool LOCAL> __device__ __forceinline__ uint32_t sk_add32(uint32_t *p, uint32_t v) {
-    if constexpr (LOCAL) return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+// what crosses workgroups inside the resident launch: agent-scope operations (see k_sk_level)
+__device__ __forceinline__ uint32_t sk_add32(uint32_t *p, uint32_t v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ unsigned long long sk_min64(unsigned long long *p, unsigned long long v) {
+    return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-template <bool LOCAL> __device__ __forceinline__ unsigned long long sk_min64(unsigned long long *p, unsigned long long v) {
-    if constexpr (LOCAL) return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+__device__ __forceinline__ unsigned long long sk_add64(unsigned long long *p, unsigned long long v) {
+    return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-template <bool LOCAL> __device__ __forceinline__ unsigned long long sk_add64(unsigned long long *p, unsigned long long v) {
-    if constexpr (LOCAL) return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <bool LOCAL> __device__ __forceinline__ void sk_store32(uint32_t *p, uint32_t v) {
-    if constexpr (LOCAL) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <bool LOCAL> __device__ __forceinline__ void sk_store64(unsigned long long *p, unsigned long long v) {
-    if constexpr (LOCAL) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+__device__ __forceinline__ void sk_store32(uint32_t *p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void sk_store64(unsigned long long *p, unsigned long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-template <bool LOCAL = false>
 __device__ __forceinline__ void stage_push(bool want, uint32_t v, SkStage &sg, uint32_t *glist, uint32_t *gcnt) {
     const unsigned long long b = __ballot(want);
     if (!b) return;
@@ -916,136 +635,41 @@ __device__ __forceinline__ void stage_push(bool want, uint32_t v, SkStage &sg, u
         base = sg.n[wv];
         if (base + n <= WB_CAP) sg.n[wv] = base + n;
         else {
-            base = 0x80000000u | sk_add32<LOCAL>(gcnt, n); // no room (rare): straight to the global list
+            base = 0x80000000u | sk_add32(gcnt, n); // no room (rare): straight to the global list
             atomicAdd(&sg.pushed, n);
         }
     }
     base = __shfl(base, leader, 64);
     if (!want) return;
-    if (base & 0x80000000u) sk_store32<LOCAL>(&glist[(base & 0x7FFFFFFFu) + rank], v);
+    if (base & 0x80000000u) sk_store32(&glist[(base & 0x7FFFFFFFu) + rank], v);
     else sg.buf[wv][base + rank] = v;
 }
 
 // all lanes of the wave are here
-template <bool LOCAL = false>
 __device__ __forceinline__ void stage_flush(SkStage &sg, uint32_t *glist, uint32_t *gcnt) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint32_t n = sg.n[wv];
     if (!n) return;
     uint32_t off = 0;
     if (lane == 0) {
-        off = sk_add32<LOCAL>(gcnt, n);
+        off = sk_add32(gcnt, n);
         atomicAdd(&sg.pushed, n);
     }
     off = __shfl(off, 0, 64);
-    // (agent-scope stores: inside the resident launch the next round's readers sit on other XCDs, behind other L2s -- unless LOCAL)
-    for (uint32_t j = lane; j < n; j += 64) sk_store32<LOCAL>(&glist[off + j], sg.buf[wv][j]);
+    // (agent-scope stores: inside the resident launch the next round's readers sit on other XCDs, behind other L2s)
+    for (uint32_t j = lane; j < n; j += 64) sk_store32(&glist[off + j], sg.buf[wv][j]);
     if (lane == 0) sg.n[wv] = 0;
 }
 
-// stamp the unstamped neighbours of the level's value of voxel `v` (the set bits of its pmask) with `nt`, one generation
-// after v's own stamp.  Lanes walk their own bits; the staged appends take whoever is there.
-__device__ __forceinline__ void sk_offer_plateau(const WsGeom &g, unsigned long long *tau, uint32_t pm, uint32_t v, unsigned long long nt,
-                                                 SkStage &sg, uint32_t *next, SkState *st) {
-    while (pm) {
-        const int k = __ffs(pm) - 1;
-        pm &= pm - 1;
-        const int dz = k / 9 - 1, dy = (k / 3) % 3 - 1, dx = k % 3 - 1;
-        const uint32_t p = (uint32_t)((int64_t)v + dz * g.hw + dy * g.w + dx);
-        bool push_n = false;
-        if (nt < ld64(&tau[p])) push_n = atomicMin(&tau[p], nt) == TINF;
-        stage_push(push_n, p, sg, next, &st->n_next);
-    }
-}
-
-// One round.  Phase A: every frontier voxel (stamp t, generation G) stamps its unstamped neighbours of value c with
+// A level's rounds.  Phase A: every frontier voxel (stamp t, generation G) stamps its unstamped neighbours of value c with
 // t + one generation and offers t to the basins it touches (atomicMin at the basin's root; a basin is stamped by exactly
-// one generation, and all its candidates arrive in this one launch).  Phase B: every drained voxel of the level whose basin
-// carries a stamp of generation G relays it, one generation later, to its unstamped neighbours of value c.  Fixed grid,
-// grid-stride over the list; the last workgroup out sets up the next round.
-__global__ __launch_bounds__(256) void k_sk_round(WsGeom g, const uint32_t *__restrict__ pmask, const uint32_t *__restrict__ zmask,
-                                                  const uint32_t *__restrict__ comp, unsigned long long *tau, SkLists L,
-                                                  const uint32_t *__restrict__ dlist, uint32_t ndl, uint32_t seq, uint32_t per_wg, SkState *st) {
-    // Only the workgroups that have list entries take part (and sign the ticket): a small frontier costs a handful of
-    // atomics, not one per launched workgroup.  A workgroup without work may start after the last working one has already
-    // set the state up for the NEXT launch -- hence one control word that names the launch it describes.
-    if (__hip_atomic_load(&st->done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-    const unsigned long long ctl = __hip_atomic_load(&st->ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if ((uint32_t)(ctl >> 34) != (seq & 0x3FFFFFFFu)) return;
-    const uint32_t phase = (uint32_t)(ctl >> 32) & 1u, in_sel = (uint32_t)(ctl >> 33) & 1u, n_front = (uint32_t)ctl;
-    const uint32_t n_in = phase ? ndl : n_front;
-    const uint32_t nactive = min((uint32_t)gridDim.x, (n_in + per_wg - 1u) / per_wg); // (few signatures: several passes per workgroup)
-    if (blockIdx.x >= nactive) return;
-    const uint32_t gen = st->gen; // (a working workgroup runs before the update: the plain fields are this launch's)
-    const uint32_t *__restrict__ in = phase ? dlist : L.l[in_sel];
-    uint32_t *__restrict__ next = L.l[in_sel ^ 1u];
-    const uint32_t stride = nactive * 256;
-    __shared__ SkStage sg;
-    if (threadIdx.x < 4) sg.n[threadIdx.x] = 0;
-    __syncthreads();
-    uint32_t stamped = 0;
-    for (uint32_t i0 = blockIdx.x * 256; i0 < n_in; i0 += stride) { // (i0 is wave-uniform: the staged pushes stay convergent)
-        const uint32_t i = i0 + threadIdx.x;
-        bool act = i < n_in;
-        const uint32_t v = act ? in[i] : 0u;
-        if (phase == 0) {
-            const unsigned long long t = act ? ld64(&tau[v]) : TINF;
-            sk_offer_plateau(g, tau, act ? pmask[v] : 0u, v, t + GEN1, sg, next, st);
-            uint32_t zm = (ndl && act) ? zmask[v] : 0u; // the basins this voxel touches
-            uint32_t last = ENTRY;
-            while (zm) {
-                const int k = __ffs(zm) - 1;
-                zm &= zm - 1;
-                const int dz = k / 9 - 1, dy = (k / 3) % 3 - 1, dx = k % 3 - 1;
-                const uint32_t root = comp[(uint32_t)((int64_t)v + dz * g.hw + dy * g.w + dx)];
-                if (root == last) continue; // (most neighbours of one voxel share a basin)
-                last = root;
-                if (t < ld64(&tau[root])) stamped += atomicMin(&tau[root], t) == TINF;
-            }
-        } else {
-            unsigned long long tb = TINF;
-            if (act) tb = ld64(&tau[comp[v]]);
-            act = act && (uint32_t)(tb >> 32) == gen; // stamped by this generation (earlier ones have relayed already)
-            sk_offer_plateau(g, tau, act ? pmask[v] : 0u, v, tb + GEN1, sg, next, st);
-        }
-        stage_flush(sg, next, &st->n_next);
-    }
-    if (stamped) atomicAdd(&st->n_stamped, stamped);
-    __shared__ uint32_t s_last;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        s_last = atomicAdd(&st->ticket, 1u) == nactive - 1;
-    }
-    __syncthreads();
-    if (!s_last || threadIdx.x != 0) return;
-    __threadfence();
-    const uint32_t nst = __hip_atomic_load(&st->n_stamped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t nnx = __hip_atomic_load(&st->n_next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    st->ticket = 0;
-    st->rounds += 1;
-    if (phase == 0 && nst) { // basins were stamped: they relay before the generation advances
-        st->phase = 1;
-        st->n_stamped = 0;
-        st->brounds += 1;
-        __hip_atomic_store(&st->ctl, sk_ctl(seq + 1u, in_sel, 1, n_front), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else if (nnx) { // next generation
-        st->phase = 0;
-        st->n_in = nnx;
-        st->n_next = 0;
-        st->gen = gen + 1;
-        st->gens += 1;
-        st->in_sel = in_sel ^ 1u;
-        __hip_atomic_store(&st->ctl, sk_ctl(seq + 1u, in_sel ^ 1u, 0, nnx), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-        st->done = 1;
-    }
-}
-
-// The same rounds in ONE launch per level: the grid stays resident (one workgroup per compute unit) and a round boundary is
+// one generation, and all its candidates arrive in this one round).  Phase B: every drained voxel of the level whose basin
+// carries a stamp of generation G relays it, one generation later, to its unstamped neighbours of value c.
+// All of them in ONE launch per level: the grid stays resident (one workgroup per compute unit) and a round boundary is
 // a device-wide hand-over through the control word instead of a kernel boundary -- the last working workgroup of round r
-// publishes the control word of round r + 1 (or SEQ_DONE), everybody else polls it.  A level of the 512^3 bench has ~6
-// generations = ~10 rounds: as launches (queued 16 at a time) they cost 8.8 us each, working or not.
+// publishes the control word of round r + 1 (or PSEQ_DONE), everybody else polls it.  Only the workgroups that have list
+// entries take part in a round (and sign the ticket).  A level of the 512^3 bench has ~6 generations = ~10 rounds: as
+// separate launches (queued 16 at a time) they cost 8.8 us each, working or not.
 // Everything that crosses workgroups inside the launch -- stamps, counters, control word AND the list entries -- is an
 // agent-scope atomic access (sc1 on gfx950: served at the point all XCDs share), so a round boundary needs no L2 write-back /
 // invalidate: a workgroup waits for its own stores (s_waitcnt) and signs the ticket.  (With __threadfence() pairs instead,
@@ -1055,9 +679,10 @@ constexpr uint32_t SK_SPIN_LIMIT = 1u << 22; // polls of ~0.5 us: a lost hand-ov
 __device__ __forceinline__ uint32_t ld32(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st32(uint32_t *p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// the offers of one voxel with every neighbour in flight at once (the loop over the set bits in sk_offer_plateau is a chain of
-// dependent round trips, one per neighbour; inside the resident launch a round IS its chain of round trips)
-template <int CONN, bool LOCAL = false>
+// stamp the unstamped neighbours of the level's value of voxel `v` (the set bits of its pmask) with `nt`, one generation after
+// v's own stamp: every neighbour's offer in flight at once (a loop over the set bits is a chain of dependent round trips, one
+// per neighbour; inside the resident launch a round IS its chain of round trips), then the staged appends
+template <int CONN>
 __device__ __forceinline__ void sk_offer_plateau_wide(const WsGeom &g, unsigned long long *tau, uint32_t pm, uint32_t v, unsigned long long nt,
                                                       SkStage &sg, uint32_t *next, SkState *st) {
     unsigned long long old[27];
@@ -1066,14 +691,14 @@ __device__ __forceinline__ void sk_offer_plateau_wide(const WsGeom &g, unsigned 
         old[k] = 0ull;
         if (!has_off<CONN>(g.smask, k)) continue;
         const int dz = k / 9 - 1, dy = (k / 3) % 3 - 1, dx = k % 3 - 1;
-        if ((pm >> k) & 1u) old[k] = sk_min64<LOCAL>(&tau[(uint32_t)((int64_t)v + dz * g.hw + dy * g.w + dx)], nt);
+        if ((pm >> k) & 1u) old[k] = sk_min64(&tau[(uint32_t)((int64_t)v + dz * g.hw + dy * g.w + dx)], nt);
     }
 #pragma unroll
     for (int k = 0; k < 27; k++) {
         if (!has_off<CONN>(g.smask, k)) continue;
         const int dz = k / 9 - 1, dy = (k / 3) % 3 - 1, dx = k % 3 - 1;
         if (!__ballot((pm >> k) & 1u)) continue; // (wave-uniform)
-        stage_push<LOCAL>(old[k] == TINF, (uint32_t)((int64_t)v + dz * g.hw + dy * g.w + dx), sg, next, &st->n_next);
+        stage_push(old[k] == TINF, (uint32_t)((int64_t)v + dz * g.hw + dy * g.w + dx), sg, next, &st->n_next);
     }
 }
 
@@ -1086,7 +711,7 @@ __device__ __forceinline__ void sk_offer_plateau_wide(const WsGeom &g, unsigned 
 constexpr uint32_t SK_SOLO_MAX = 256; // list entries up to which ONE workgroup takes the round without a hand-over (one pass)
 
 // one round's share of a workgroup: list entries wg * 256 + k * nactive * 256 (the whole workgroup is here)
-template <int CONN, bool LOCAL>
+template <int CONN>
 __device__ __forceinline__ void sk_level_round(const WsGeom &g, const uint32_t *__restrict__ pmask, const uint32_t *__restrict__ zmask,
                                                const uint32_t *__restrict__ comp, unsigned long long *tau, const SkLists &L,
                                                const uint32_t *dlist, const uint32_t *__restrict__ droot, uint32_t ndl, SkState *st, SkStage &sg,
@@ -1134,7 +759,7 @@ __device__ __forceinline__ void sk_level_round(const WsGeom &g, const uint32_t *
                 old[k] = 0ull;
                 if (!has_off<CONN>(g.smask, k)) continue;
                 const int dz = k / 9 - 1, dy = (k / 3) % 3 - 1, dx = k % 3 - 1;
-                if ((pm >> k) & 1u) old[k] = sk_min64<LOCAL>(&tau[(uint32_t)((int64_t)v + dz * g.hw + dy * g.w + dx)], nt);
+                if ((pm >> k) & 1u) old[k] = sk_min64(&tau[(uint32_t)((int64_t)v + dz * g.hw + dy * g.w + dx)], nt);
             }
             uint32_t last = ENTRY;
 #pragma unroll
@@ -1143,14 +768,14 @@ __device__ __forceinline__ void sk_level_round(const WsGeom &g, const uint32_t *
                 if (!has_off<CONN>(g.smask, k)) continue;
                 if (root[k] == ENTRY || root[k] == last) continue; // (most neighbours of one voxel share a basin)
                 last = root[k];
-                oldr[k] = sk_min64<LOCAL>(&tau[root[k]], t);
+                oldr[k] = sk_min64(&tau[root[k]], t);
             }
 #pragma unroll
             for (int k = 0; k < 27; k++) {
                 if (!has_off<CONN>(g.smask, k)) continue;
                 const int dz = k / 9 - 1, dy = (k / 3) % 3 - 1, dx = k % 3 - 1;
                 if (!__ballot((pm >> k) & 1u)) continue; // (wave-uniform)
-                stage_push<LOCAL>(old[k] == TINF, (uint32_t)((int64_t)v + dz * g.hw + dy * g.w + dx), sg, next, &st->n_next);
+                stage_push(old[k] == TINF, (uint32_t)((int64_t)v + dz * g.hw + dy * g.w + dx), sg, next, &st->n_next);
             }
             if (SK_TICKS && tr) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); SK_TICK(1) }
 #pragma unroll
@@ -1164,10 +789,10 @@ __device__ __forceinline__ void sk_level_round(const WsGeom &g, const uint32_t *
             if (act) tb = ld64(&tau[droot[i]]); // (the root travels with the list: no gather into comp[] on the relay's critical path)
             act = act && (uint32_t)(tb >> 32) == gen;
             if (SK_TICKS && tr) { SK_TICK(0) }
-            sk_offer_plateau_wide<CONN, LOCAL>(g, tau, act ? pmask[v] : 0u, v, tb + GEN1, sg, next, st);
+            sk_offer_plateau_wide<CONN>(g, tau, act ? pmask[v] : 0u, v, tb + GEN1, sg, next, st);
             if (SK_TICKS && tr) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); SK_TICK(1) }
         }
-        stage_flush<LOCAL>(sg, next, &st->n_next);
+        stage_flush(sg, next, &st->n_next);
         if (SK_TICKS && tr) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); SK_TICK(3) }
     }
     if (stamped) atomicAdd(&sg.stamped, stamped); // (LDS: the ticket carries it)
@@ -1189,16 +814,7 @@ __device__ __forceinline__ void sk_level_round(const WsGeom &g, const uint32_t *
 // A round's time is its chain of dependent DRAM-latency accesses (~1.5 us each, agent-scope or not: pmask / zmask / comp are
 // random reads of 0.5 GB arrays) -- voxel -> masks and stamp -> basin roots -> atomics, twice per generation with the relay
 // -- and 1 742 generations times that chain is the level chain's floor; who runs the round hardly matters.
-// LOCAL (round 6): the level's rounds on ONE XCD.  A round is a chain of dependent accesses to the stamps, the lists and the
-// counters; at agent scope each of them is a trip over the fabric (the writer's L2 drops the line: the next reader misses too).
-// The workgroups that find themselves on XCD 0 (HW_REG_XCC_ID, read at run time -- which workgroup lands where is not promised,
-// so nobody assumes it) share one L2: between them a workgroup-scope atomic IS coherent (atomics execute in the L2, loads
-// bypass the L1), and the level's working set stays in that L2 from round to round.  The others leave at once.  The launch
-// is eight times as wide so that an eighth of it is enough; kernel boundaries make the result visible to everybody else.
-// MEASURED (512^3, opt-in IVX_SK_LOCAL=1, same labels): level chain 44.6 - 46.8 ms against 39.1 with the rounds spread over all
-// eight XCDs at agent scope -- 32 compute units and one L2's atomic unit serve the mid-sized rounds more slowly than the fabric
-// trips cost.  Kept as an A/B, not the default.
-template <int CONN, bool LOCAL>
+template <int CONN>
 __global__ __launch_bounds__(256) void k_sk_level(WsGeom g, const uint32_t *__restrict__ pmask, const uint32_t *__restrict__ zmask,
                                                   const uint32_t *__restrict__ comp, unsigned long long *tau, SkLists L,
                                                   const uint32_t *dlist, const uint32_t *__restrict__ droot, uint32_t ndl, uint32_t per_wg,
@@ -1206,36 +822,8 @@ __global__ __launch_bounds__(256) void k_sk_level(WsGeom g, const uint32_t *__re
     __shared__ SkStage sg;
     __shared__ unsigned long long s_ctl;
     __shared__ uint32_t s_last, s_next[4], s_tot[2], s_keep; // s_next: phase, list, entries, 1 = level exhausted
-    uint32_t my_wg = blockIdx.x, n_wg = gridDim.x;
-    if (LOCAL) {
-        __shared__ uint32_t s_id[2];
-        if (threadIdx.x == 0) {
-            uint32_t xcc;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-            const bool mine = (xcc & 7u) == 0u;
-            uint32_t id = 0xFFFFFFFFu, n = 0;
-            if (mine) id = __hip_atomic_fetch_add(&st->joined, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (returned: performed)
-            __hip_atomic_fetch_add(&st->arrived, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (mine) {
-                for (uint32_t spins = 0; ld32(&st->arrived) < gridDim.x; spins++) {
-                    if (spins > SK_SPIN_LIMIT) { // (a workgroup of the launch never started: give up cleanly)
-                        st32(&st->done, 3u);
-                        id = 0xFFFFFFFFu;
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(4);
-                }
-                n = ld32(&st->joined);
-            }
-            s_id[0] = id;
-            s_id[1] = n;
-        }
-        __syncthreads();
-        if (s_id[0] == 0xFFFFFFFFu) return;
-        my_wg = s_id[0];
-        n_wg = s_id[1];
-    }
-    const uint32_t gen0 = ld32(&st->gen); // (k_sk_assign's launch wrote it)
+    const uint32_t my_wg = blockIdx.x, n_wg = gridDim.x;
+    const uint32_t gen0 = ld32(&st->gen); // (the stamping launch wrote it: sk_begin_level)
     uint32_t want = 0;                    // sequence number of the next word this workgroup has not seen
     for (;;) {
         if (threadIdx.x == 0) {
@@ -1267,11 +855,11 @@ __global__ __launch_bounds__(256) void k_sk_level(WsGeom g, const uint32_t *__re
         const uint32_t n_in = phase ? ndl : n_front;
         const uint32_t nactive = min(n_wg, (n_in + per_wg - 1u) / per_wg);
         if (my_wg < nactive) {
-            sk_level_round<CONN, LOCAL>(g, pmask, zmask, comp, tau, L, dlist, droot, ndl, st, sg, phase, in_sel, n_front, gen, my_wg, nactive);
+            sk_level_round<CONN>(g, pmask, zmask, comp, tau, L, dlist, droot, ndl, st, sg, phase, in_sel, n_front, gen, my_wg, nactive);
             const unsigned long long tt0 = SK_TICKS && my_wg == 0 && threadIdx.x == 0 ? wall_clock64() : 0ull;
             if (threadIdx.x == 0) {
                 const uint32_t mine_p = sg.pushed, mine_s = sg.stamped ? 1u : 0u;
-                const unsigned long long old = sk_add64<LOCAL>(&st->tick64, (1ull << 48) | ((unsigned long long)mine_s << 32) | mine_p);
+                const unsigned long long old = sk_add64(&st->tick64, (1ull << 48) | ((unsigned long long)mine_s << 32) | mine_p);
                 s_last = (uint32_t)(old >> 48) == nactive - 1;
                 s_tot[0] = (uint32_t)old + mine_p;                       // list entries the whole round appended
                 s_tot[1] = ((uint32_t)(old >> 32) & 0xFFFFu) + mine_s;   // workgroups of it that stamped a basin
@@ -1290,14 +878,14 @@ __global__ __launch_bounds__(256) void k_sk_level(WsGeom g, const uint32_t *__re
                         // (the round just closed: the ticket's totals; a round of the solo stretch: this workgroup's own counts)
                         const uint32_t nst = first ? s_tot[1] : (sg.stamped ? 1u : 0u);
                         const uint32_t nnx = first ? s_tot[0] : s_keep + sg.pushed;
-                        sk_add32<LOCAL>(&st->rounds, 1u);
+                        sk_add32(&st->rounds, 1u);
                         if (phase == 0 && nst) { // basins were stamped: they relay before the generation advances
-                            sk_add32<LOCAL>(&st->brounds, 1u);
+                            sk_add32(&st->brounds, 1u);
                             s_next[0] = 1u; s_next[1] = in_sel; s_next[2] = n_front; s_next[3] = 0u;
                             s_keep = nnx;
                         } else if (nnx) { // next generation
-                            sk_store32<LOCAL>(&st->n_next, 0u);
-                            sk_add32<LOCAL>(&st->gens, 1u);
+                            sk_store32(&st->n_next, 0u);
+                            sk_add32(&st->gens, 1u);
                             s_next[0] = 0u; s_next[1] = in_sel ^ 1u; s_next[2] = nnx; s_next[3] = 0u;
                             s_keep = 0u;
                         } else {
@@ -1317,7 +905,7 @@ __global__ __launch_bounds__(256) void k_sk_level(WsGeom g, const uint32_t *__re
                         cum++;
                     }
                     if (!solo) break;
-                    sk_level_round<CONN, LOCAL>(g, pmask, zmask, comp, tau, L, dlist, droot, ndl, st, sg, phase, in_sel, n_front, gen, 0u, 1u);
+                    sk_level_round<CONN>(g, pmask, zmask, comp, tau, L, dlist, droot, ndl, st, sg, phase, in_sel, n_front, gen, 0u, 1u);
                 }
                 if (threadIdx.x == 0) {
                     unsigned long long nctl;
@@ -1332,9 +920,9 @@ __global__ __launch_bounds__(256) void k_sk_level(WsGeom g, const uint32_t *__re
                     } else {
                         nctl = sk_pctl(want, cum, in_sel, phase, n_front);
                     }
-                    sk_store64<LOCAL>(&st->tick64, (unsigned long long)s_keep); // (no arrivals yet; a relay continues its generation's count)
+                    sk_store64(&st->tick64, (unsigned long long)s_keep); // (no arrivals yet; a relay continues its generation's count)
                     __builtin_amdgcn_s_waitcnt(0);
-                    sk_store64<LOCAL>(&st->pctl, nctl);
+                    sk_store64(&st->pctl, nctl);
                 }
             }
         }
@@ -1756,7 +1344,6 @@ struct SkBufs {
     int32_t *runlabel;
     WsState *wst;
     SkState *st;
-    SkG0Ctl *g0ctl;
     size_t bytes;
 };
 
@@ -1789,7 +1376,6 @@ static void sk_layout(const WsGeom &g, char *base, SkBufs *b) {
     b->pending = (uint8_t *)take((size_t)g.ntiles);
     b->wst = (WsState *)take(sizeof(WsState));
     b->st = (SkState *)take(sizeof(SkState));
-    b->g0ctl = (SkG0Ctl *)take(sizeof(SkG0Ctl));
     b->total = (uint32_t *)take(256);
     b->bytes = o;
 }
@@ -1814,102 +1400,258 @@ static size_t sk_layout2(uint64_t ngen0, uint32_t maxcnt, bool split, char *base
     return o;
 }
 
-template <typename MT>
-static int sk_run(const WsGeom &g, const uint16_t *I, const MT *mk, MT *out, int32_t *out32, uint8_t *out8, uint16_t *cost_out,
-                  int64_t *stats, hipStream_t st) {
-    const int conn = conn_of(g.smask);
-    const int64_t nblk = cdiv(g.n, 2048);
-    const int gl = (int)cdiv(g.n, 256);
-    SkBufs b;
-    sk_layout(g, nullptr, &b);
-    void *mem = nullptr;
-    IVX_REQUIRE(ws_get_s(WS_WSIFT, st, b.bytes, &mem) == IVX_OK, IVX_ENOMEM, "watershed: %zu bytes of scratch", b.bytes);
-    sk_layout(g, (char *)mem, &b);
+// Every switch of this flood (diagnostics, A/B measurements, tests; none changes a result), read once at the top of a call.
+struct SkKnobs {
+    // The levels that hold the bulk of the volume first, as ordinary region-growing floods (ivx_dev_sk_cost_levels):
+    // the zero plateau of a windowed gradient -- ~95 % of the voxels -- is ONE flood; the relaxation keeps the rest.
+    // IVX_SK_LEVELS = most levels (0: off), IVX_SK_LEVELS_FRAC, IVX_SK_LEVELS_MIN (voxels) as for the IFT branch.
+    int lv_max;       // (512^3, windowed: cost map 9.7 ms without, 7.6 with one level, 5.7 with three)
+    double lv_frac;
+    int64_t lv_min;
+    bool relax_all;   // IVX_SK_RELAX_ALL=1: after those floods every tile looks once, as in rounds 2 - 5 (default: only tiles that still hold a voxel without a cost)
+    // A level's generation 0 is keyed, sorted and stamped by our own kernels -- no library on this path:
+    //   up to 128 chunks (the default): k_sk_keys -> k_sk_sort_chunks -> k_sk_rank_pairs -> k_sk_assign_ranked;
+    //   more: k_sk_keys -> k_sk_sort_chunks -> k_sk_merge_pass x log2(chunks) -> k_sk_assign_ranked;
+    //   IVX_SK_SORT=merge: every level through the merge passes (tests, A/B);
+    //   IVX_SK_CHUNK = n (a power of two up to 2048): the chunk length (tests: many chunks on small volumes), 0: not set.
+    bool sort_merge;
+    uint32_t ch_env;
+    // chunks of 1024 voxels (the chunk sort is bound by one compute unit's instruction rate: 15 us for 1024 pairs, 31 for 2048)
+    // until the pairwise ranks outweigh that -- their work grows with voxels x chunks; IVX_SK_CHUNK_SWITCH, _PAIR_CHUNKS, _PAIR_WGS: A/B
+    uint32_t ch_switch;
+    int64_t pair_chunks, pair_wgs;
+    // The early / late split (k_sk_classify): a level's early part is keyed and sorted on a second stream while the level
+    // below is being flooded; behind that level only the late part is keyed (k_sk_keys) and everything stamped in one launch
+    // (k_sk_split_assign).  IVX_SK_SPLIT=0: every level's generation 0 as one list on the chain's own stream (A/B, tests).
+    bool split;
+    uint32_t late_max; // IVX_SK_LATE_MAX: longest late part ranked by brute force (tests: 0 = every late part through the sort)
+    bool late_recs;    // IVX_SK_LATE_RECS=0: the late keys chase the neighbours themselves (default: key records made beside the level below)
+    bool small_recs;   // IVX_SK_SMALL_RECS=0: the same for a run of small levels
+    bool small_on;     // IVX_SK_SMALL=0: never take the one-workgroup path (A/B measurements)
+    uint64_t tile_min; // IVX_SK_TILE_LEVEL: voxels from which a basin-free level is relaxed tile-wise (A/B; 0 = never)
+    bool plane;        // IVX_SK_PLANE=0: the tile-wise relaxation reads C and I per cell instead of the level's bit plane
+    uint32_t per_wg;   // IVX_SK_PER_WG: list entries per working workgroup (A/B; round 6: 1024 -> 256 = one pass per workgroup, 49.8 -> 44.7 ms of level chain at 512^3)
+    uint32_t solo_max; // IVX_SK_SOLO: most list entries one workgroup takes alone inside a resident launch (0: never; A/B)
+    int64_t res_per_cu; // IVX_SK_RES_PER_CU: resident workgroups per compute unit (1 .. 4)
+    bool res_tuned;    // IVX_SK_PER_WG or IVX_SK_RES_PER_CU was set at all: the launch is sized as asked (see sk_run_resident_level)
+    bool trace;        // IVX_WS_TRACE: a line per level on stderr (and a host read per level)
+    uint32_t chunk_len(uint32_t cnt) const { return ch_env ? ch_env : cnt <= ch_switch ? 1024u : 2048u; }
+};
 
-    WsTimer tm;
-    tm.on = stats != nullptr;
-    tm.mark(st);
-    // ---- 1. costs ------------------------------------------------------------------------------------------
+static SkKnobs sk_read_knobs() {
+    auto off = [](const char *name) { const char *e = getenv(name); return e && e[0] == '0'; };
+    SkKnobs k;
+    const char *e1 = getenv("IVX_SK_LEVELS"), *e2 = getenv("IVX_SK_LEVELS_FRAC"), *e3 = getenv("IVX_SK_LEVELS_MIN");
+    k.lv_max = e1 ? atoi(e1) : 3;
+    k.lv_frac = e2 ? atof(e2) : 0.99;
+    k.lv_min = e3 ? atoll(e3) : ((int64_t)1 << 21);
+    const char *era = getenv("IVX_SK_RELAX_ALL");
+    k.relax_all = era && era[0] == '1';
+    const char *ech = getenv("IVX_SK_CHUNK"), *eso2 = getenv("IVX_SK_SORT");
+    k.ch_env = ech ? (uint32_t)atoi(ech) : 0u;
+    if (k.ch_env < 2 || k.ch_env > 2048 || (k.ch_env & (k.ch_env - 1))) k.ch_env = 0;
+    k.sort_merge = eso2 && eso2[0] == 'm';
+    const char *e_sw = getenv("IVX_SK_CHUNK_SWITCH"), *e_pc = getenv("IVX_SK_PAIR_CHUNKS"), *e_pw = getenv("IVX_SK_PAIR_WGS");
+    k.ch_switch = e_sw ? (uint32_t)atoll(e_sw) : (1u << 17);
+    k.pair_chunks = e_pc ? atoll(e_pc) : 128;
+    k.pair_wgs = e_pw ? std::max<int64_t>(atoll(e_pw), 1) : 2048;
+    k.split = !off("IVX_SK_SPLIT");
+    const char *elm = getenv("IVX_SK_LATE_MAX");
+    k.late_max = elm ? std::min<uint32_t>((uint32_t)atoll(elm), LATE_MAX) : LATE_MAX;
+    k.late_recs = !off("IVX_SK_LATE_RECS");
+    k.small_recs = !off("IVX_SK_SMALL_RECS");
+    k.small_on = !off("IVX_SK_SMALL");
+    const char *tenv = getenv("IVX_SK_TILE_LEVEL");
+    k.tile_min = tenv ? (uint64_t)atoll(tenv) : ((uint64_t)1 << 16);
+    k.plane = !off("IVX_SK_PLANE");
+    const char *epb = getenv("IVX_SK_PER_WG"), *eso = getenv("IVX_SK_SOLO"), *erc = getenv("IVX_SK_RES_PER_CU");
+    k.per_wg = epb && atoi(epb) >= 32 ? (uint32_t)atoi(epb) : 256u;
+    k.solo_max = eso ? (uint32_t)atoi(eso) : SK_SOLO_MAX;
+    k.res_per_cu = erc && atoi(erc) >= 1 && atoi(erc) <= 4 ? atoi(erc) : 1;
+    k.res_tuned = epb || erc;
+    k.trace = getenv("IVX_WS_TRACE") != nullptr;
+    return k;
+}
+
+// kind[] is dead once the buckets are made (k_sk_bucket3's scatter pass is its last reader); three scratch regions live in its
+// n bytes afterwards, in this order:
+//   [0, 8 ceil(n / 64))                        the bit plane of a tile-wise level (k_sk_level_plane)
+//   [rec_off, rec_off + 32 esum)               the key records of a run of small levels (rec_off: behind the plane, 256-aligned)
+//   [n - 2 late_bytes, n) rounded down to 256  two sets of late-part key records (one being made while the other is read)
+// The small records stop 512 bytes short of the late sets whether those are in use or not, and the late sets need 4 MB + 1 KB
+// between the plane and themselves: no two regions overlap.
+struct SkCarve {
+    uint8_t *kind = nullptr;
+    size_t n = 0, rec_off = 0, late_bytes = 0;
+    bool small_ok = false;
+    unsigned long long *plane = nullptr;      // nullptr: the relaxation reads C and I per cell
+    uint32_t *late_recs[2] = {nullptr, nullptr}; // nullptr: the late keys chase the neighbours themselves
+    uint32_t *small_recs(uint32_t esum) const { // nullptr: the run's workgroup finds the places itself
+        return small_ok && esum && rec_off + (size_t)esum * 32 + 2 * late_bytes + 512 <= n ? (uint32_t *)(kind + rec_off) : nullptr;
+    }
+};
+static SkCarve sk_carve_kind(const WsGeom &g, const SkKnobs &k, int conn, uint8_t *kind, const uint16_t *I, const uint16_t *C) {
+    SkCarve cv;
+    cv.kind = kind;
+    cv.n = (size_t)g.n;
+    if (k.plane && (((uintptr_t)I | (uintptr_t)C) & 15) == 0) cv.plane = (unsigned long long *)kind;
+    cv.rec_off = (cv.n / 8 + 511) & ~(size_t)255;
+    cv.late_bytes = ((size_t)k.late_max * 32 + 255) & ~(size_t)255;
+    cv.small_ok = k.small_recs && conn == 6; // (the records hold six places)
+    if (k.late_recs && k.split && conn == 6 && cv.n >= cv.n / 8 + 1024 + 2 * cv.late_bytes + ((size_t)1 << 22))
+        for (int q = 0; q < 2; q++) cv.late_recs[q] = (uint32_t *)(kind + ((cv.n - (size_t)(2 - q) * cv.late_bytes) & ~(size_t)255));
+    return cv;
+}
+
+// the second stream (the early parts' sorts) and the events that order it against the chain
+struct SkSide {
+    hipStream_t stream = nullptr;
+    hipEvent_t done[4] = {nullptr, nullptr, nullptr, nullptr}, early[2] = {nullptr, nullptr};
+};
+template <typename MT>
+static int sk_side_stream(SkSide **out) {
+    static thread_local SkSide side;
+    if (!side.stream) {
+        IVX_HIP(hipStreamCreateWithFlags(&side.stream, hipStreamNonBlocking));
+        for (auto &e : side.done) IVX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        for (auto &e : side.early) IVX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        // (one instantiation per marker type)
+        IVX_HIP(hipFuncSetAttribute((const void *)k_sk_split_assign<MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LATE_MAX * 12)));
+    }
+    *out = &side;
+    return IVX_OK;
+}
+
+// what the stages of one call share
+template <typename MT>
+struct SkCtx {
+    WsGeom g;
+    int conn;
+    const uint16_t *I;
+    const MT *mk;
+    hipStream_t st;
+    SkKnobs k;
+    SkBufs b;
+    SkCarve carve;
+    SkSide *side = nullptr;
+    int ncu = 0;
+    // from the cost map
+    uint32_t M = 0, imax = 0, nlev = 0; // markers; the image's largest value; levels that can hold voxels: 0 .. imax
+    int64_t rounds = 0, visits = 0;
+    // from the buckets
+    std::vector<uint32_t> lhist, hist, hist_l, dhist, mbits; // per level: voxels, generation 0 (all of it, its late part), drained voxels; levels that hold markers (bits)
+    uint64_t ngen0 = 0;
+    const uint32_t *droot_d = nullptr; // the drained entries' roots, beside b.dlist
+    // statistics of the level chain
+    int64_t nlevels = 0, ntile_rounds = 0, nsmall_runs = 0, nsplit = 0;
+
+    bool is_small(uint32_t c) const { return k.small_on && hist[c] <= (uint32_t)SMALL_GEN0 && lhist[c] <= SMALL_TOTAL; }
+    bool is_tile_level(uint32_t c) const { return dhist[c] == 0 && k.tile_min && lhist[c] >= k.tile_min; }
+    bool has_markers(uint32_t c) const { return (mbits[c >> 5] >> (c & 31u)) & 1u; }
+};
+
+// Where the level chain stands: positions in the lists, the generation counter, and the early part that is on its way.
+struct SkCursor {
+    uint32_t start = 0, dstart = 0, roff = 0; // the level's stretch of elist / of dlist, its first run label
+    // One resident launch per level and no host read between consecutive levels -- the next level's first generation travels
+    // on the device (SkState::gnext); `gknown` says whether the host's gbase is current.
+    uint32_t gbase = 1;
+    bool gknown = true;
+    uint32_t ndone = 0;                             // events recorded on the chain's stream so far (a ring of four)
+    uint32_t early_of = 0xFFFFFFFFu, early_cnt = 0; // the level whose early part is (being) sorted on the side stream, in set early_set
+    int early_set = 0, next_set = 0;
+
+    void advance(uint32_t cnt, uint32_t ndl) {
+        roff += cnt;
+        start += cnt;
+        dstart += ndl;
+    }
+    // the chain's last launch has finished: fetch the generation counter (resident: that launch was a k_sk_level)
+    int read_state(const SkState *dst, hipStream_t st, bool resident) {
+        uint32_t mseq = 0, msg[2] = {0, 0}; // {done, gen}
+        int rc = mailbox_publish(&dst->done, 2, st, &mseq);
+        if (rc != IVX_OK) return rc;
+        rc = mailbox_wait(mseq, st, msg, 2);
+        if (rc != IVX_OK) return rc;
+        IVX_REQUIRE(!resident || msg[0] == 1, IVX_EINVAL, "watershed: a level's resident launch lost its hand-over (state %u)", msg[0]);
+        gbase = msg[1] + 1;
+        gknown = true;
+        return IVX_OK;
+    }
+    int sync_gbase(const SkState *dst, hipStream_t st) { return gknown ? IVX_OK : read_state(dst, st, true); }
+};
+
+// ---- 1. costs: x.M markers (0: nothing else is filled in), the image's largest value
+template <typename MT>
+static int sk_cost_map(SkCtx<MT> &x) {
+    const WsGeom &g = x.g;
+    const SkBufs &b = x.b;
+    hipStream_t st = x.st;
+    const int64_t nblk = cdiv(g.n, 2048);
     IVX_HIP(hipMemsetAsync(b.wst, 0, sizeof(WsState), st));
     IVX_HIP(hipMemsetAsync(b.st, 0, sizeof(SkState), st));
-    IVX_HIP(hipMemsetAsync(b.g0ctl, 0, sizeof(SkG0Ctl), st));
     IVX_HIP(hipMemsetAsync(b.dirty, 0, (size_t)g.ntiles, st));
-    hipLaunchKernelGGL((k_ws_init<MT, true>), dim3((unsigned)nblk), dim3(256), 0, st, g, mk, I, b.C, b.dirty, b.bcount, b.wst);
+    hipLaunchKernelGGL((k_ws_init<MT, true>), dim3((unsigned)nblk), dim3(256), 0, st, g, x.mk, x.I, b.C, b.dirty, b.bcount, b.wst);
     IVX_LAUNCH_CHECK();
     {
         const int rc = scan_u32_exclusive(b.bcount, nblk, b.bsum, b.total, st);
         if (rc != IVX_OK) return rc;
     }
-    uint32_t M = 0;
     WsState hw;
-    IVX_HIP(hipMemcpyAsync(&M, b.total, 4, hipMemcpyDeviceToHost, st));
+    IVX_HIP(hipMemcpyAsync(&x.M, b.total, 4, hipMemcpyDeviceToHost, st));
     IVX_HIP(hipMemcpyAsync(&hw, b.wst, sizeof(hw), hipMemcpyDeviceToHost, st));
     IVX_HIP(hipStreamSynchronize(st));
     IVX_REQUIRE(!hw.overflow, IVX_EINVAL, "watershed: image value 65535 is reserved (the reference's gradient images stay far below)");
-    if (M == 0) { // no marker: nothing is ever queued, every label stays 0
-        if (out) IVX_HIP(hipMemsetAsync(out, 0, (size_t)g.n * sizeof(MT), st));
-        if (out32) IVX_HIP(hipMemsetAsync(out32, 0, (size_t)g.n * 4, st));
-        if (out8) IVX_HIP(hipMemsetAsync(out8, 0, (size_t)g.n, st));
-        if (cost_out) IVX_HIP(hipMemsetAsync(cost_out, 0xFF, (size_t)g.n * 2, st));
-        if (stats) memset(stats, 0, 16 * sizeof(int64_t));
-        return IVX_OK;
-    }
-    const uint32_t nlev = std::min<uint32_t>(hw.imax + 2u, 65536u); // levels that can hold voxels: 0 .. the image's largest value
-    int64_t rounds = 0, visits = 0;
-    {
-        // The levels that hold the bulk of the volume first, as ordinary region-growing floods (ivx_dev_sk_cost_levels):
-        // the zero plateau of a windowed gradient -- ~95 % of the voxels -- is ONE flood; the relaxation keeps the rest.
-        // IVX_SK_LEVELS = most levels (0: off), IVX_SK_LEVELS_FRAC, IVX_SK_LEVELS_MIN (voxels) as for the IFT branch.
-        const char *e1 = getenv("IVX_SK_LEVELS"), *e2 = getenv("IVX_SK_LEVELS_FRAC"), *e3 = getenv("IVX_SK_LEVELS_MIN");
-        const int lv_max = e1 ? atoi(e1) : 3;          // (512^3, windowed: cost map 9.7 ms without, 7.6 with one level, 5.7 with three)
-        const double lv_frac = e2 ? atof(e2) : 0.99;
-        const int64_t lv_min = e3 ? atoll(e3) : ((int64_t)1 << 21);
-        if (lv_max > 0 && g.w % 64 == 0 && g.n >= lv_min && (((uintptr_t)I | (uintptr_t)mk) & 15) == 0) {
-            uint8_t s27[27];
-            for (int k = 0; k < 27; k++) s27[k] = (uint8_t)(k == 13 || ((g.smask >> k) & 1u));
-            int levels_done = 0;
-            int64_t lvox = 0, lrounds = 0;
-            const int rc = ivx_dev_sk_cost_levels(I, sizeof(MT) == 2 ? IVX_I16 : IVX_I8, mk, g.d, g.h, g.w, s27, b.C, lv_max, lv_frac,
-                                                  &levels_done, &lvox, &lrounds, st);
-            if (rc != IVX_OK) return rc;
-            // the levels' costs are final: only tiles that still hold a voxel without a cost have work (IVX_SK_RELAX_ALL=1: every tile
-            // looks once, as in rounds 2 - 5 -- A/B)
-            static const bool relax_all = []() { const char *e = getenv("IVX_SK_RELAX_ALL"); return e && e[0] == '1'; }();
-            if (relax_all) {
-                IVX_HIP(hipMemsetAsync(b.dirty, 1, (size_t)g.ntiles, st));
-            } else {
-                IVX_HIP(hipMemsetAsync(b.dirty, 0, (size_t)g.ntiles, st));
-                hipLaunchKernelGGL(k_ws_mark_open_tiles, dim3((unsigned)cdiv(g.n / 8, 256)), dim3(256), 0, st, g, b.C, b.dirty);
-                IVX_LAUNCH_CHECK();
-            }
-        }
-        const int rc = ws_cost_rounds<true>(g, conn, I, b.C, b.tlist, b.dirty, b.pending, b.wst, st, &rounds, &visits);
+    if (x.M == 0) return IVX_OK;
+    x.imax = hw.imax;
+    x.nlev = std::min<uint32_t>(hw.imax + 2u, 65536u);
+    if (x.k.lv_max > 0 && g.w % 64 == 0 && g.n >= x.k.lv_min && (((uintptr_t)x.I | (uintptr_t)x.mk) & 15) == 0) {
+        uint8_t s27[27];
+        for (int k = 0; k < 27; k++) s27[k] = (uint8_t)(k == 13 || ((g.smask >> k) & 1u));
+        int levels_done = 0;
+        int64_t lvox = 0, lrounds = 0;
+        const int rc = ivx_dev_sk_cost_levels(x.I, sizeof(MT) == 2 ? IVX_I16 : IVX_I8, x.mk, g.d, g.h, g.w, s27, b.C, x.k.lv_max, x.k.lv_frac,
+                                              &levels_done, &lvox, &lrounds, st);
         if (rc != IVX_OK) return rc;
+        // the levels' costs are final: only tiles that still hold a voxel without a cost have work
+        if (x.k.relax_all) {
+            IVX_HIP(hipMemsetAsync(b.dirty, 1, (size_t)g.ntiles, st));
+        } else {
+            IVX_HIP(hipMemsetAsync(b.dirty, 0, (size_t)g.ntiles, st));
+            hipLaunchKernelGGL(k_ws_mark_open_tiles, dim3((unsigned)cdiv(g.n / 8, 256)), dim3(256), 0, st, g, b.C, b.dirty);
+            IVX_LAUNCH_CHECK();
+        }
     }
-    if (cost_out) IVX_HIP(hipMemcpyAsync(cost_out, b.C, (size_t)g.n * 2, hipMemcpyDeviceToDevice, st));
+    return ws_cost_rounds<true>(g, x.conn, x.I, b.C, b.tlist, b.dirty, b.pending, b.wst, st, &x.rounds, &x.visits);
+}
 
-    tm.mark(st);
-    // ---- 2. generation 0 and the drained basins, bucketed by level ------------------------------------------
+// ---- 2. generation 0 and the drained basins, bucketed by level; the histograms on the host; the scratch sized by them
+template <typename MT>
+static int sk_bucket_levels(SkCtx<MT> &x) {
+    const WsGeom &g = x.g;
+    SkBufs &b = x.b;
+    hipStream_t st = x.st;
+    const uint32_t nlev = x.nlev;
     const unsigned gbk = (unsigned)cdiv(g.n, 256 * BK_CH);
-    std::vector<uint32_t> lhist(65536); // voxels per level (a level that holds much of the volume is relaxed tile-wise)
+    x.lhist.assign(65536, 0); // voxels per level (a level that holds much of the volume is relaxed tile-wise)
     IVX_HIP(hipMemsetAsync(b.lhist, 0, 65536 * 4, st));
     // LDS counters of the bucket passes: the levels that exist (no cost is above the image's largest value), whole 64s, BK_LB at most
-    const int bk_lb = (int)std::min<uint32_t>(((hw.imax + 1u) + 63u) & ~63u, (uint32_t)BK_LB);
+    const int bk_lb = (int)std::min<uint32_t>(((x.imax + 1u) + 63u) & ~63u, (uint32_t)BK_LB);
     hipLaunchKernelGGL((k_ws_bucket<SkLevelPred, false>), dim3(gbk), dim3(256), (size_t)bk_lb * 4, st, g.n, b.C, SkLevelPred{}, b.lhist, b.elist, bk_lb);
     IVX_LAUNCH_CHECK();
-    IVX_HIP(hipMemcpyAsync(lhist.data(), b.lhist, (size_t)nlev * 4, hipMemcpyDeviceToHost, st)); // (only the levels the image has)
+    IVX_HIP(hipMemcpyAsync(x.lhist.data(), b.lhist, (size_t)nlev * 4, hipMemcpyDeviceToHost, st)); // (only the levels the image has)
     hipLaunchKernelGGL(k_sk_prevlevel, dim3(1), dim3(1024), 0, st, b.lhist, b.prevl);
     IVX_LAUNCH_CHECK();
     IVX_HIP(hipMemsetAsync(b.mbits, 0, 2048 * 4, st));
-    WS_CONN_SWITCH(conn, hipLaunchKernelGGL((k_sk_classify<CC, MT>), dim3((unsigned)g.ntiles), dim3(256), 0, st, g, I, b.C, mk, b.kind, b.comp,
-                                              b.zmask, b.pmask, b.mbits, b.prevl));
+    WS_CONN_SWITCH(x.conn, hipLaunchKernelGGL((k_sk_classify<CC, MT>), dim3((unsigned)g.ntiles), dim3(256), 0, st, g, x.I, b.C, x.mk, b.kind, b.comp,
+                                                b.zmask, b.pmask, b.mbits, b.prevl));
     IVX_LAUNCH_CHECK();
     {
-        const int rc = ws_zone_union(g, conn, b.zmask, b.comp, st);
+        const int rc = ws_zone_union(g, x.conn, b.zmask, b.comp, st);
         if (rc != IVX_OK) return rc;
     }
     IVX_HIP(hipMemsetAsync(b.hist, 0, (size_t)BK3_N * 4, st));
-    std::vector<uint32_t> hist3(BK3_N), dhist(65536);
+    std::vector<uint32_t> hist3(BK3_N);
     { // generation 0 (a level's early part, then its late part) and, behind all of it, the drained voxels: ONE list, two passes
         hipLaunchKernelGGL(k_sk_bucket3<false>, dim3(gbk), dim3(256), (size_t)bk_lb * 12, st, g.n, b.C, b.kind, b.hist, b.elist, b.comp, (uint32_t *)nullptr, bk_lb);
         IVX_LAUNCH_CHECK();
@@ -1922,489 +1664,382 @@ static int sk_run(const WsGeom &g, const uint16_t *I, const MT *mk, MT *out, int
         hipLaunchKernelGGL(k_sk_bucket3<true>, dim3(gbk), dim3(256), (size_t)bk_lb * 12, st, g.n, b.C, b.kind, b.cursor, b.elist, b.comp, b.droot, bk_lb);
         IVX_LAUNCH_CHECK();
     }
-    std::vector<uint32_t> mbits(2048); // levels that hold markers
-    IVX_HIP(hipMemcpyAsync(mbits.data(), b.mbits, 2048 * 4, hipMemcpyDeviceToHost, st));
+    x.mbits.assign(2048, 0); // levels that hold markers
+    IVX_HIP(hipMemcpyAsync(x.mbits.data(), b.mbits, 2048 * 4, hipMemcpyDeviceToHost, st));
     hipLaunchKernelGGL(k_sk_fill64, dim3(2048), dim3(256), 0, st, b.tau, g.n, TINF);
     IVX_LAUNCH_CHECK();
     IVX_HIP(hipStreamSynchronize(st)); // the histograms are on the host now
-    std::vector<uint32_t> hist(65536), hist_l(65536); // generation 0 per level: all of it, its late part
+    x.hist.assign(65536, 0); // generation 0 per level: all of it,
+    x.hist_l.assign(65536, 0); // its late part
+    x.dhist.assign(65536, 0);
     uint64_t ngen0_all = 0;
     for (uint32_t c = 0; c < nlev; c++) {
-        hist[c] = hist3[2 * c] + hist3[2 * c + 1];
-        hist_l[c] = hist3[2 * c + 1];
-        dhist[c] = hist3[BK3_D0 + c];
-        ngen0_all += hist[c];
+        x.hist[c] = hist3[2 * c] + hist3[2 * c + 1];
+        x.hist_l[c] = hist3[2 * c + 1];
+        x.dhist[c] = hist3[BK3_D0 + c];
+        ngen0_all += x.hist[c];
     }
     b.dlist = b.elist + ngen0_all; // (the drained voxels' stretches follow generation 0's in the one list)
-    const uint32_t *droot_d = b.droot + ngen0_all;
-    uint64_t ngen0 = 0;
+    x.droot_d = b.droot + ngen0_all;
     uint32_t maxcnt = 0;
     for (uint32_t c = 0; c < 65535; c++) { // (65535 = never reached: no generation 0 there)
-        ngen0 += hist[c];
-        maxcnt = std::max(maxcnt, hist[c]);
+        x.ngen0 += x.hist[c];
+        maxcnt = std::max(maxcnt, x.hist[c]);
     }
-    IVX_REQUIRE(ngen0 < 0xFFFFFFF0ull, IVX_EINVAL, "watershed: more than 2^32 queue entries");
-    int ncu = 0;
+    IVX_REQUIRE(x.ngen0 < 0xFFFFFFF0ull, IVX_EINVAL, "watershed: more than 2^32 queue entries");
     {
         int dev = 0;
         IVX_HIP(hipGetDevice(&dev));
-        IVX_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+        IVX_HIP(hipDeviceGetAttribute(&x.ncu, hipDeviceAttributeMultiprocessorCount, dev));
     }
-    // A level's generation 0 is keyed, sorted and stamped by our own kernels -- no library on this path:
-    //   up to 128 chunks of 2048 voxels (the default): k_sk_keys -> k_sk_sort_chunks -> k_sk_rank_pairs -> k_sk_assign_ranked;
-    //   more: k_sk_keys -> k_sk_sort_chunks -> k_sk_merge_pass x log2(chunks) -> k_sk_assign;
-    //   IVX_SK_SORT=fused: everything in ONE launch with a device-wide barrier (k_sk_gen0; measured slower: DESIGN.md section 8),
-    //   IVX_SK_SORT=merge: every level through the merge passes (tests, A/B);
-    //   IVX_SK_CHUNK = n (a power of two up to 2048): the chunk length (tests: many chunks on small volumes).
-    const char *ech = getenv("IVX_SK_CHUNK"), *eso2 = getenv("IVX_SK_SORT");
-    uint32_t ch_env = ech ? (uint32_t)atoi(ech) : 0u;
-    if (ch_env < 2 || ch_env > 2048 || (ch_env & (ch_env - 1))) ch_env = 0;
-    const bool sort_merge = eso2 && eso2[0] == 'm', sort_fused = eso2 && eso2[0] == 'f';
-    const uint32_t g0_wgs = (uint32_t)std::max(ncu, 8);
-    // chunks of 1024 voxels (the chunk sort is bound by one compute unit's instruction rate: 15 us for 1024 pairs, 31 for 2048)
-    // until the pairwise ranks outweigh that -- their work grows with voxels x chunks; IVX_SK_CHUNK_SWITCH, _PAIR_CHUNKS, _PAIR_WGS: A/B
-    const char *e_sw = getenv("IVX_SK_CHUNK_SWITCH"), *e_pc = getenv("IVX_SK_PAIR_CHUNKS"), *e_pw = getenv("IVX_SK_PAIR_WGS");
-    const uint32_t ch_switch = e_sw ? (uint32_t)atoll(e_sw) : (1u << 17);
-    const int64_t PAIR_CHUNKS = e_pc ? atoll(e_pc) : 128, PAIR_WGS = e_pw ? std::max<int64_t>(atoll(e_pw), 1) : 2048;
-    auto chunk_len = [&](uint32_t cnt) -> uint32_t { return ch_env ? ch_env : cnt <= ch_switch ? 1024u : 2048u; };
-    auto g0_chunk = [&](uint32_t cnt) -> uint32_t { // chunk length of the one-launch path, 0: not for this level
-        if (!sort_fused) return 0u;
-        if (ch_env) return cdiv((int64_t)cnt, ch_env) <= (int64_t)g0_wgs ? ch_env : 0u;
-        if (cdiv((int64_t)cnt, 2048) <= (int64_t)g0_wgs) return 2048u;
-        if (cdiv((int64_t)cnt, 4096) <= (int64_t)g0_wgs) return 4096u;
-        return 0u;
-    };
-    // The early / late split (k_sk_classify): a level's early part is keyed and sorted on a second stream while the level
-    // below is being flooded; behind that level only the late part is keyed (k_sk_keys) and everything stamped in one launch
-    // (k_sk_split_assign).  IVX_SK_SPLIT=0: every level's generation 0 as one list on the chain's own stream (A/B, tests).
-    const char *esp = getenv("IVX_SK_SPLIT");
-    const char *penv0 = getenv("IVX_SK_PERSIST");
-    const bool split_on = !(esp && esp[0] == '0') && !sort_fused && !(penv0 && penv0[0] == '0');
-    const char *elm = getenv("IVX_SK_LATE_MAX"); // longest late part ranked by brute force (tests: 0 = every late part through the sort)
-    const uint32_t late_max = elm ? std::min<uint32_t>((uint32_t)atoll(elm), LATE_MAX) : LATE_MAX;
-    {
-        void *mem2 = nullptr;
-        const size_t need = sk_layout2(ngen0, maxcnt, split_on, nullptr, &b);
-        IVX_REQUIRE(ws_get_s(WS_WSSK, st, need, &mem2) == IVX_OK, IVX_ENOMEM, "watershed: %zu bytes of scratch", need);
-        sk_layout2(ngen0, maxcnt, split_on, (char *)mem2, &b);
-    }
-    // keys -> sorted chunks -> (pairwise ranks | merge passes) of one list on one stream; what comes back is read as
-    // "position of entry i = (i & (ch - 1)) + sum over the share planes" (merge passes: no planes, ch covers the whole list)
-    struct SortOut {
-        const unsigned long long *key;
-        const uint32_t *val, *part;
-        unsigned shares;
-        uint32_t ch;
-    };
-    auto sort_list = [&](hipStream_t s, SkSortBufs &w, const uint32_t *el, uint32_t cnt, uint32_t climit, SortOut *out) -> int {
-        const unsigned gb = (unsigned)cdiv(cnt, 256);
-        WS_CONN_SWITCH(conn, hipLaunchKernelGGL((k_sk_keys<CC, MT>), dim3(gb), dim3(256), 0, s, g, b.C, mk, I, b.comp, b.tau, el, w.key_a, w.val_a, cnt, climit));
-        IVX_LAUNCH_CHECK();
-        const uint32_t chb = chunk_len(cnt);
-        const int64_t nch = cdiv((int64_t)cnt, chb);
-        const bool pairs = !sort_merge && (nch <= PAIR_CHUNKS || ch_env);
-        unsigned long long *ka = w.key_a, *kb = w.key_b;
-        uint32_t *va = w.val_a, *vb = w.val_b;
-        if (chb <= 512) hipLaunchKernelGGL(k_sk_sort_chunks<64>, dim3((unsigned)nch), dim3(64), 0, s, ka, va, kb, vb, cnt, chb);
-        else if (chb <= 1024) hipLaunchKernelGGL(k_sk_sort_chunks<128>, dim3((unsigned)nch), dim3(128), 0, s, ka, va, kb, vb, cnt, chb);
-        else hipLaunchKernelGGL(k_sk_sort_chunks<256>, dim3((unsigned)nch), dim3(256), 0, s, ka, va, kb, vb, cnt, chb);
-        IVX_LAUNCH_CHECK();
-        std::swap(ka, kb);
-        std::swap(va, vb);
-        out->part = w.rank;
-        if (pairs) {
-            unsigned shares = 0;
-            if (nch > 1) { // (chunk, share of the other chunks): a thousand or two workgroups
-                shares = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nch - 1, PAIR_WGS / nch), (int64_t)(PLANE_CAP / cnt)));
-                if (chb <= 512) hipLaunchKernelGGL(k_sk_rank_pairs<2>, dim3((unsigned)nch, shares), dim3(256), 0, s, ka, w.rank, cnt, chb);
-                else if (chb <= 1024) hipLaunchKernelGGL(k_sk_rank_pairs<4>, dim3((unsigned)nch, shares), dim3(256), 0, s, ka, w.rank, cnt, chb);
-                else hipLaunchKernelGGL(k_sk_rank_pairs<8>, dim3((unsigned)nch, shares), dim3(256), 0, s, ka, w.rank, cnt, chb);
-                IVX_LAUNCH_CHECK();
-            }
-            out->shares = shares;
-            out->ch = chb;
-        } else { // too many chunks to rank pairwise: merge passes
-            for (uint64_t run = chb; run < cnt; run *= 2) {
-                const uint32_t tile = (uint32_t)std::min<uint64_t>(MP_TILE, 2 * run);
-                hipLaunchKernelGGL(k_sk_merge_pass, dim3((unsigned)cdiv((int64_t)cnt, tile)), dim3(256), 0, s, ka, va, kb, vb, cnt, (uint32_t)run, tile);
-                IVX_LAUNCH_CHECK();
-                std::swap(ka, kb);
-                std::swap(va, vb);
-            }
-            out->shares = 0;
-            out->ch = 0x80000000u; // (a power of two above every list: position = index)
-        }
-        out->key = ka;
-        out->val = va;
-        return IVX_OK;
-    };
+    void *mem2 = nullptr;
+    const size_t need = sk_layout2(x.ngen0, maxcnt, x.k.split, nullptr, &b);
+    IVX_REQUIRE(ws_get_s(WS_WSSK, st, need, &mem2) == IVX_OK, IVX_ENOMEM, "watershed: %zu bytes of scratch", need);
+    sk_layout2(x.ngen0, maxcnt, x.k.split, (char *)mem2, &b);
+    x.carve = sk_carve_kind(g, x.k, x.conn, b.kind, x.I, b.C);
+    if (x.k.split) return sk_side_stream<MT>(&x.side);
+    return IVX_OK;
+}
 
-    tm.mark(st);
-    // ---- 3. the level chain ----------------------------------------------------------------------------------
-    int64_t nlevels = 0, ntile_rounds = 0, nsmall_runs = 0;
-    const bool trace = getenv("IVX_WS_TRACE") != nullptr;
-    const char *epb = getenv("IVX_SK_PER_WG"); // list entries per working workgroup (A/B measurements)
-    const uint32_t per_wg = epb && atoi(epb) >= 32 ? (uint32_t)atoi(epb) : 256u; // (round 6: 1024 -> 256 = one pass per workgroup, 49.8 -> 44.7 ms of level chain at 512^3)
-    const char *eso = getenv("IVX_SK_SOLO"); // most list entries one workgroup takes alone inside a resident launch (0: never; A/B)
-    const uint32_t solo_max = eso ? (uint32_t)atoi(eso) : SK_SOLO_MAX;
-    const char *elo = getenv("IVX_SK_LOCAL"), *elw = getenv("IVX_SK_LOCAL_WGS"); // the level's rounds on one XCD (k_sk_level<.., LOCAL>); A/B
-    const bool level_local = elo && elo[0] == '1';
-    const int64_t local_wgs = elw && atoi(elw) >= 1 ? std::min(atoi(elw), 128) : 128; // workgroups wanted on that XCD (32 CUs; 256 -- a launch of 2 048 -- never got all its workgroups started beside the side stream)
-    const char *erc = getenv("IVX_SK_RES_PER_CU");
-    const int64_t res_per_cu = erc && atoi(erc) >= 1 && atoi(erc) <= 4 ? atoi(erc) : 1;
-    uint32_t start = 0, dstart = 0, roff = 0, gbase = 1, seq = 0;
-    // IVX_SK_PERSIST=0: a level's rounds as separate launches (k_sk_round, queued in batches; A/B measurements).  Default: one
-    // resident launch per level (k_sk_level) and no host read between consecutive levels -- the next level's first
-    // generation travels on the device (SkState::gnext); `gknown` says whether the host's gbase is current.
-    const char *penv = getenv("IVX_SK_PERSIST");
-    const bool persist = !(penv && penv[0] == '0');
-    bool gknown = true;
-    auto sync_gbase = [&]() -> int { // the chain's last level has finished: fetch the generation counter
-        if (gknown) return IVX_OK;
-        uint32_t mseq = 0, msg[4] = {0, 0, 0, 0};
-        int rc = mailbox_publish(&b.st->done, 4, st, &mseq);
+// keys -> sorted chunks -> (pairwise ranks | merge passes) of one list on one stream; what comes back is read as
+// "position of entry i = (i & (ch - 1)) + sum over the share planes" (merge passes: no planes, ch covers the whole list)
+struct SortOut {
+    const unsigned long long *key;
+    const uint32_t *val, *part;
+    unsigned shares;
+    uint32_t ch;
+};
+template <typename MT>
+static int sk_sort_list(const SkCtx<MT> &x, hipStream_t s, const SkSortBufs &w, const uint32_t *el, uint32_t cnt, uint32_t climit, SortOut *out) {
+    const SkBufs &b = x.b;
+    const unsigned gb = (unsigned)cdiv(cnt, 256);
+    WS_CONN_SWITCH(x.conn, hipLaunchKernelGGL((k_sk_keys<CC, MT>), dim3(gb), dim3(256), 0, s, x.g, b.C, x.mk, x.I, b.comp, b.tau, el, w.key_a, w.val_a, cnt, climit));
+    IVX_LAUNCH_CHECK();
+    const uint32_t chb = x.k.chunk_len(cnt);
+    const int64_t nch = cdiv((int64_t)cnt, chb);
+    const bool pairs = !x.k.sort_merge && (nch <= x.k.pair_chunks || x.k.ch_env);
+    unsigned long long *ka = w.key_a, *kb = w.key_b;
+    uint32_t *va = w.val_a, *vb = w.val_b;
+    if (chb <= 512) hipLaunchKernelGGL(k_sk_sort_chunks<64>, dim3((unsigned)nch), dim3(64), 0, s, ka, va, kb, vb, cnt, chb);
+    else if (chb <= 1024) hipLaunchKernelGGL(k_sk_sort_chunks<128>, dim3((unsigned)nch), dim3(128), 0, s, ka, va, kb, vb, cnt, chb);
+    else hipLaunchKernelGGL(k_sk_sort_chunks<256>, dim3((unsigned)nch), dim3(256), 0, s, ka, va, kb, vb, cnt, chb);
+    IVX_LAUNCH_CHECK();
+    std::swap(ka, kb);
+    std::swap(va, vb);
+    out->part = w.rank;
+    if (pairs) {
+        unsigned shares = 0;
+        if (nch > 1) { // (chunk, share of the other chunks): a thousand or two workgroups
+            shares = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nch - 1, x.k.pair_wgs / nch), (int64_t)(PLANE_CAP / cnt)));
+            if (chb <= 512) hipLaunchKernelGGL(k_sk_rank_pairs<2>, dim3((unsigned)nch, shares), dim3(256), 0, s, ka, w.rank, cnt, chb);
+            else if (chb <= 1024) hipLaunchKernelGGL(k_sk_rank_pairs<4>, dim3((unsigned)nch, shares), dim3(256), 0, s, ka, w.rank, cnt, chb);
+            else hipLaunchKernelGGL(k_sk_rank_pairs<8>, dim3((unsigned)nch, shares), dim3(256), 0, s, ka, w.rank, cnt, chb);
+            IVX_LAUNCH_CHECK();
+        }
+        out->shares = shares;
+        out->ch = chb;
+    } else { // too many chunks to rank pairwise: merge passes
+        for (uint64_t run = chb; run < cnt; run *= 2) {
+            const uint32_t tile = (uint32_t)std::min<uint64_t>(MP_TILE, 2 * run);
+            hipLaunchKernelGGL(k_sk_merge_pass, dim3((unsigned)cdiv((int64_t)cnt, tile)), dim3(256), 0, s, ka, va, kb, vb, cnt, (uint32_t)run, tile);
+            IVX_LAUNCH_CHECK();
+            std::swap(ka, kb);
+            std::swap(va, vb);
+        }
+        out->shares = 0;
+        out->ch = 0x80000000u; // (a power of two above every list: position = index)
+    }
+    out->key = ka;
+    out->val = va;
+    return IVX_OK;
+}
+
+// the early part of the level that follows c, if that level is a candidate: called when c's stamps are queued, before its flood
+template <typename MT>
+static int sk_queue_early_after(SkCtx<MT> &x, SkCursor &cur, uint32_t c) {
+    if (!x.k.split) return IVX_OK;
+    const SkBufs &b = x.b;
+    SkSide &side = *x.side;
+    uint32_t cn = c + 1;
+    while (cn < 65535 && !x.hist[cn]) cn++;
+    if (cn >= 65535) return IVX_OK;
+    const uint32_t ce = x.hist[cn] - x.hist_l[cn], cl = x.hist_l[cn];
+    if (x.is_small(cn) || x.is_tile_level(cn) || ce == 0 || cl > x.hist[cn] / 2) return IVX_OK; // (mostly late: nothing to gain)
+    const uint32_t sn = cur.start + x.hist[c]; // where level cn's stretch of the list begins (levels between c and cn are empty)
+    // levels below c are final -- and c's own generation 0 (the chain's critical stretch) has the chip to itself: the side
+    // stream starts when c's flood does
+    IVX_HIP(hipEventRecord(side.done[cur.ndone % 4], x.st));
+    cur.ndone++;
+    IVX_HIP(hipStreamWaitEvent(side.stream, side.done[(cur.ndone - 1) % 4], 0));
+    SortOut so;
+    const int rc = sk_sort_list(x, side.stream, b.sort[1], b.elist + sn, ce, c, &so); // (neighbours below c count: c itself is being flooded)
+    if (rc != IVX_OK) return rc;
+    const int set = cur.next_set;
+    hipLaunchKernelGGL(k_sk_scatter_sorted, dim3((unsigned)cdiv(ce, 256)), dim3(256), 0, side.stream, so.key, so.val, so.part, so.shares, so.ch,
+                       b.ekey[set], b.eval[set], ce);
+    IVX_LAUNCH_CHECK();
+    if (x.carve.late_recs[set] && cl && cl <= x.k.late_max) { // the late part's key records (k_sk_small_recs), for the chain's k_sk_keys_rec
+        hipLaunchKernelGGL(k_sk_small_recs<MT>, dim3((unsigned)cdiv(cl, 256)), dim3(256), 0, side.stream, x.g, b.C, x.mk, x.I, b.comp,
+                           b.elist + sn + ce, cl, x.carve.late_recs[set]);
+        IVX_LAUNCH_CHECK();
+    }
+    IVX_HIP(hipEventRecord(side.early[set], side.stream));
+    cur.early_of = cn;
+    cur.early_cnt = ce;
+    cur.early_set = set;
+    cur.next_set ^= 1;
+    return IVX_OK;
+}
+
+// generation 0 of level c: keys, sort, stamps (T, run labels, first frontier in lists[0]), the tied-marker count
+template <typename MT>
+static int sk_stamp_gen0(SkCtx<MT> &x, const SkCursor &cur, uint32_t c) {
+    const SkBufs &b = x.b;
+    hipStream_t st = x.st;
+    const MT *mk = x.mk;
+    const uint32_t cnt = x.hist[c], start = cur.start, roff = cur.roff;
+    const uint32_t g0_gbase = cur.gknown ? cur.gbase : 0u; // (0: the stamping launch reads SkState::gnext)
+    const unsigned gb = (unsigned)cdiv(cnt, 256);
+    if (cur.early_of == c) { // this level's early part is on its way (queued when the level below started)
+        const uint32_t ce = cur.early_cnt, cl = cnt - ce;
+        const int set = cur.early_set;
+        x.nsplit++;
+        if (cl <= x.k.late_max) { // late keys, then every stamp in one launch (the late pairs ranked by brute force in LDS)
+            IVX_HIP(hipStreamWaitEvent(st, x.side->early[set], 0)); // (long since: the side stream worked beside the level below)
+            if (cl && x.carve.late_recs[set]) {
+                hipLaunchKernelGGL(k_sk_keys_rec, dim3((unsigned)cdiv(cl, 256)), dim3(256), 0, st, x.carve.late_recs[set], b.tau, b.sort[0].key_a,
+                                   b.sort[0].val_a, cl);
+                IVX_LAUNCH_CHECK();
+            } else if (cl) {
+                WS_CONN_SWITCH(x.conn, hipLaunchKernelGGL((k_sk_keys<CC, MT>), dim3((unsigned)cdiv(cl, 256)), dim3(256), 0, st, x.g, b.C, mk, x.I, b.comp,
+                                                            b.tau, b.elist + start + ce, b.sort[0].key_a, b.sort[0].val_a, cl, c));
+                IVX_LAUNCH_CHECK();
+            }
+            const unsigned nwg = (unsigned)(cdiv(ce, 256) + cdiv(cl, LATE_PER_WG));
+            hipLaunchKernelGGL(k_sk_split_assign<MT>, dim3(nwg), dim3(256), (size_t)cl * 12, st, b.ekey[set], b.eval[set], ce, b.sort[0].key_a,
+                               b.sort[0].val_a, cl, mk, b.tau, b.runlabel, b.lists[0], roff, g0_gbase, b.st);
+            IVX_LAUNCH_CHECK();
+        } else { // a late part too long for that (1024^3: 16 000 of a level's 360 000): sorted like any list, placed behind the early part
+            SortOut so;
+            const int rc = sk_sort_list(x, st, b.sort[0], b.elist + start + ce, cl, c, &so);
+            if (rc != IVX_OK) return rc;
+            IVX_HIP(hipStreamWaitEvent(st, x.side->early[set], 0));
+            hipLaunchKernelGGL(k_sk_assign_ranked<MT>, dim3((unsigned)cdiv(ce, 256)), dim3(256), 0, st, b.ekey[set], b.eval[set],
+                               (const uint32_t *)nullptr, 0u, 0x80000000u, mk, b.tau, b.runlabel, b.lists[0], ce, 0u, cnt, roff, g0_gbase, b.st);
+            IVX_LAUNCH_CHECK();
+            hipLaunchKernelGGL(k_sk_assign_ranked<MT>, dim3((unsigned)cdiv(cl, 256)), dim3(256), 0, st, so.key, so.val, so.part, so.shares, so.ch, mk,
+                               b.tau, b.runlabel, b.lists[0], cl, ce, cnt, roff, g0_gbase, b.st);
+            IVX_LAUNCH_CHECK();
+        }
+    } else {
+        SortOut so;
+        const int rc = sk_sort_list(x, st, b.sort[0], b.elist + start, cnt, c, &so);
         if (rc != IVX_OK) return rc;
-        rc = mailbox_wait(mseq, st, msg, 4);
+        hipLaunchKernelGGL(k_sk_assign_ranked<MT>, dim3(gb), dim3(256), 0, st, so.key, so.val, so.part, so.shares, so.ch, mk, b.tau, b.runlabel,
+                           b.lists[0], cnt, 0u, cnt, roff, g0_gbase, b.st);
+        IVX_LAUNCH_CHECK();
+    }
+    if (x.has_markers(c)) {
+        hipLaunchKernelGGL(k_sk_mixed<MT>, dim3(gb), dim3(256), 0, st, b.lists[0], mk, cnt, b.st);
+        IVX_LAUNCH_CHECK();
+    }
+    return IVX_OK;
+}
+
+// a run of consecutive small levels from c on: one launch of one workgroup; *c_hi: the run's last level
+template <typename MT>
+static int sk_run_small_levels(SkCtx<MT> &x, SkCursor &cur, uint32_t c, uint32_t *c_hi_out) {
+    const SkBufs &b = x.b;
+    hipStream_t st = x.st;
+    {
+        const int rc = cur.sync_gbase(b.st, st);
         if (rc != IVX_OK) return rc;
-        IVX_REQUIRE(msg[0] == 1, IVX_EINVAL, "watershed: a level's resident launch lost its hand-over (state %u)", msg[0]);
-        gbase = msg[1] + 1;
-        gknown = true;
-        return IVX_OK;
-    };
+    }
+    uint32_t c_hi = c, esum = 0, dsum = 0, nlv = 0;
+    for (uint32_t q = c; q < 65535 && (x.hist[q] == 0 || x.is_small(q)); q++)
+        if (x.hist[q]) c_hi = q;
+    for (uint32_t q = c; q <= c_hi; q++) {
+        nlv += x.hist[q] != 0;
+        esum += x.hist[q];
+        dsum += x.dhist[q];
+    }
+    SkSmallArgs sa{nullptr, 0u, b.C, x.I, b.comp, b.pmask, b.zmask, b.elist, /* dcursor holds positions in the one list: */ b.elist, b.hist, b.cursor, b.dhist, b.dcursor, b.tau, b.runlabel,
+                   b.lists[0], b.lists[1], b.st};
+    if (uint32_t *rec = x.carve.small_recs(esum)) { // key records of the run's entries
+        hipLaunchKernelGGL(k_sk_small_recs<MT>, dim3((unsigned)cdiv(esum, 256)), dim3(256), 0, st, x.g, b.C, x.mk, x.I, b.comp, b.elist + cur.start, esum, rec);
+        IVX_LAUNCH_CHECK();
+        sa.rec = rec;
+        sa.run_start = cur.start;
+    }
+    hipLaunchKernelGGL(k_sk_levels_small<MT>, dim3(1), dim3(1024), 0, st, x.g, sa, x.mk, c, c_hi, cur.gbase, cur.roff);
+    IVX_LAUNCH_CHECK();
+    const int rc = cur.read_state(b.st, st, false);
+    if (rc != IVX_OK) return rc;
+    cur.advance(esum, dsum);
+    x.nlevels += nlv;
+    x.nsmall_runs++;
+    if (x.k.trace) fprintf(stderr, "sk levels %u..%u (%u levels) in one workgroup -> generation %u\n", c, c_hi, nlv, cur.gbase - 1);
+    *c_hi_out = c_hi;
+    return IVX_OK;
+}
+
+// a basin-free level that is not small, stamped already: relaxed tile-wise (k_sk_plateau_relax)
+template <typename MT>
+static int sk_run_tile_level(SkCtx<MT> &x, SkCursor &cur, uint32_t c) {
+    const WsGeom &g = x.g;
+    const SkBufs &b = x.b;
+    hipStream_t st = x.st;
+    const uint32_t cnt = x.hist[c];
+    hipLaunchKernelGGL(k_sk_mark_tiles, dim3((unsigned)cdiv(cnt, 256)), dim3(256), 0, st, g, b.lists[0], cnt, b.dirty);
+    IVX_LAUNCH_CHECK();
+    const unsigned long long *P = x.carve.plane; // the level's voxels as a bit plane
+    if (P) {
+        hipLaunchKernelGGL(k_sk_level_plane, dim3((unsigned)cdiv(cdiv(g.n, 64) * 8, 256)), dim3(256), 0, st, b.C, x.I, g.n, c, x.carve.plane);
+        IVX_LAUNCH_CHECK();
+    }
+    // Rounds of dirty tiles.  The host never stands between two rounds' kernels: a round's relaxation is launched with a grid
+    // guessed from the previous round's list (1.5 x + 64: the wave front grows slowly) BEFORE the host has read how long this
+    // round's list is -- the read then overlaps the kernel (110 us), and a list longer than the guess gets a second launch
+    // behind it.  (Rounds 1 - 5: list length read first, 20 us of host round trip per round, 61 / 125 rounds per flood.)
+    uint32_t guess = 0;
+    int parity = 0; // (both list counters are zero between two loops: a loop ends on an empty list, which cleared the other one)
+    for (;;) {
+        uint32_t mseq = 0, nl = 0, *lcur = nullptr;
+        int rc = ws_build_list_publish(g.ntiles, b.dirty, b.tlist, b.wst, parity, st, &mseq, &lcur); // (list, count and mailbox in one launch)
+        if (rc != IVX_OK) return rc;
+        parity ^= 1;
+        if (guess) {
+            WS_CONN_SWITCH(x.conn, hipLaunchKernelGGL(k_sk_plateau_relax<CC>, dim3(guess), dim3(256), 0, st, g, x.I, b.C, b.tau, b.tlist, b.dirty, c, b.st,
+                                                        lcur, 0u, P));
+            IVX_LAUNCH_CHECK();
+        }
+        rc = mailbox_wait(mseq, st, &nl, 1);
+        if (rc != IVX_OK) return rc;
+        if (!nl) break; // (a guessed launch of this round found an empty list and returned)
+        x.ntile_rounds++;
+        if (nl > guess) {
+            WS_CONN_SWITCH(x.conn, hipLaunchKernelGGL(k_sk_plateau_relax<CC>, dim3(nl - guess), dim3(256), 0, st, g, x.I, b.C, b.tau, b.tlist, b.dirty, c,
+                                                        b.st, lcur, guess, P));
+            IVX_LAUNCH_CHECK();
+        }
+        guess = (uint32_t)std::min<int64_t>(g.ntiles, (int64_t)nl + nl / 2 + 64);
+    }
+    return cur.read_state(b.st, st, false);
+}
+
+// a level's rounds, stamped already: one resident launch; the host moves on without reading anything
+template <typename MT>
+static int sk_run_resident_level(SkCtx<MT> &x, SkCursor &cur, uint32_t c) {
+    const SkBufs &b = x.b;
+    const uint32_t cnt = x.hist[c], ndl = x.dhist[c];
     SkLists lists;
     for (int i = 0; i < 2; i++) lists.l[i] = b.lists[i];
-    const char *senv = getenv("IVX_SK_SMALL"); // 0: never take the one-workgroup path (A/B measurements)
-    const bool small_on = !(senv && senv[0] == '0');
-    auto is_small = [&](uint32_t c) { return small_on && hist[c] <= (uint32_t)SMALL_GEN0 && lhist[c] <= SMALL_TOTAL; };
-    SkSmallArgs sa{nullptr, 0u, b.C, I, b.comp, b.pmask, b.zmask, b.elist, /* dcursor holds positions in the one list: */ b.elist, b.hist, b.cursor, b.dhist, b.dcursor, b.tau, b.runlabel,
-                   b.lists[0], b.lists[1], b.st};
-    static const char *tenv = getenv("IVX_SK_TILE_LEVEL"); // voxels from which a basin-free level is relaxed tile-wise (A/B; 0 = never)
-    const uint64_t tile_min = tenv ? (uint64_t)atoll(tenv) : ((uint64_t)1 << 16);
-    auto is_tile_level = [&](uint32_t c) { return dhist[c] == 0 && tile_min && lhist[c] >= tile_min; };
-    // ---- the second stream (the early parts' sorts) and the events that order it against the chain
-    struct SkSide {
-        hipStream_t stream = nullptr;
-        hipEvent_t done[4] = {nullptr, nullptr, nullptr, nullptr}, early[2] = {nullptr, nullptr};
-    };
-    static thread_local SkSide side;
-    if (split_on && !side.stream) {
-        IVX_HIP(hipStreamCreateWithFlags(&side.stream, hipStreamNonBlocking));
-        for (auto &e : side.done) IVX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (auto &e : side.early) IVX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    static thread_local bool attr_set[2] = {false, false};
-    if (split_on && !attr_set[sizeof(MT) == 2]) { // (one instantiation per marker type)
-        IVX_HIP(hipFuncSetAttribute((const void *)k_sk_split_assign<MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LATE_MAX * 12)));
-        attr_set[sizeof(MT) == 2] = true;
-    }
-    uint32_t ndone = 0;           // events recorded on the chain's stream so far (a ring of four)
-    uint32_t early_of = 0xFFFFFFFFu, early_cnt = 0; // the level whose early part is (being) sorted on the side stream, in set early_set
-    int early_set = 0, next_set = 0;
-    int64_t nsplit = 0;
-    // key records of a level's late part, two sets like the early parts' (6 neighbours; at the end of kind[]'s bytes, which nobody
-    // reads after the buckets; IVX_SK_LATE_RECS=0: the late keys chase the neighbours themselves)
-    static const bool late_recs_on = []() { const char *e = getenv("IVX_SK_LATE_RECS"); return !(e && e[0] == '0'); }();
-    const size_t late_rec_bytes = ((size_t)late_max * 32 + 255) & ~(size_t)255;
-    uint32_t *late_recs[2] = {nullptr, nullptr};
-    if (late_recs_on && split_on && conn == 6 && (size_t)g.n >= (size_t)g.n / 8 + 1024 + 2 * late_rec_bytes + ((size_t)1 << 22))
-        for (int q = 0; q < 2; q++) late_recs[q] = (uint32_t *)(b.kind + (((size_t)g.n - (size_t)(2 - q) * late_rec_bytes) & ~(size_t)255));
-    // the early part of the level that follows c, if that level is a candidate: called before c's own work is queued
-    auto queue_early_after = [&](uint32_t c) -> int {
-        if (!split_on) return IVX_OK;
-        uint32_t cn = c + 1;
-        while (cn < 65535 && !hist[cn]) cn++;
-        if (cn >= 65535) return IVX_OK;
-        const uint32_t ce = hist[cn] - hist_l[cn];
-        if (is_small(cn) || is_tile_level(cn) || ce == 0 || hist_l[cn] > hist[cn] / 2) return IVX_OK; // (mostly late: nothing to gain)
-        uint32_t sn = start + hist[c]; // where level cn's stretch of the list begins (levels between c and cn are empty)
-        // levels below c are final -- and c's own generation 0 (the chain's critical stretch) has the chip to itself: the side
-        // stream starts when c's flood does
-        IVX_HIP(hipEventRecord(side.done[ndone % 4], st));
-        ndone++;
-        IVX_HIP(hipStreamWaitEvent(side.stream, side.done[(ndone - 1) % 4], 0));
-        SortOut so;
-        const int rc = sort_list(side.stream, b.sort[1], b.elist + sn, ce, c, &so); // (neighbours below c count: c itself is being flooded)
-        if (rc != IVX_OK) return rc;
-        hipLaunchKernelGGL(k_sk_scatter_sorted, dim3((unsigned)cdiv(ce, 256)), dim3(256), 0, side.stream, so.key, so.val, so.part, so.shares, so.ch,
-                           b.ekey[next_set], b.eval[next_set], ce);
-        IVX_LAUNCH_CHECK();
-        if (late_recs[next_set] && hist_l[cn] && hist_l[cn] <= late_max) { // the late part's key records (k_sk_small_recs), for the chain's k_sk_keys_rec
-            hipLaunchKernelGGL(k_sk_small_recs<MT>, dim3((unsigned)cdiv(hist_l[cn], 256)), dim3(256), 0, side.stream, g, b.C, mk, I, b.comp,
-                               b.elist + sn + ce, hist_l[cn], late_recs[next_set]);
-            IVX_LAUNCH_CHECK();
-        }
-        IVX_HIP(hipEventRecord(side.early[next_set], side.stream));
-        early_of = cn;
-        early_cnt = ce;
-        early_set = next_set;
-        next_set ^= 1;
-        return IVX_OK;
-    };
-    for (uint32_t c = 0; c < 65535; c++) {
-        const uint32_t cnt = hist[c], ndl = dhist[c];
-        if (!cnt) { // (no voxel of the level at all: a level's drained voxels hang off its generation 0)
-            dstart += ndl;
-            continue;
-        }
-        if (is_small(c)) { // a run of consecutive small levels: one launch
-            {
-                const int rc = sync_gbase();
-                if (rc != IVX_OK) return rc;
-            }
-            uint32_t c_hi = c, esum = 0, dsum = 0, nlv = 0;
-            for (uint32_t q = c; q < 65535 && (hist[q] == 0 || is_small(q)); q++)
-                if (hist[q]) c_hi = q;
-            for (uint32_t q = c; q <= c_hi; q++) {
-                nlv += hist[q] != 0;
-                esum += hist[q];
-                dsum += dhist[q];
-            }
-            // key records of the run's entries (6 neighbours; in kind[]'s bytes behind the level plane's: nobody reads those any more)
-            static const bool recs_on = []() { const char *e = getenv("IVX_SK_SMALL_RECS"); return !(e && e[0] == '0'); }();
-            SkSmallArgs sr = sa;
-            const size_t rec_off = ((size_t)g.n / 8 + 511) & ~(size_t)255;
-            if (recs_on && conn == 6 && esum && rec_off + (size_t)esum * 32 + 2 * late_rec_bytes + 512 <= (size_t)g.n) {
-                uint32_t *rec = (uint32_t *)(b.kind + rec_off);
-                hipLaunchKernelGGL(k_sk_small_recs<MT>, dim3((unsigned)cdiv(esum, 256)), dim3(256), 0, st, g, b.C, mk, I, b.comp, b.elist + start, esum, rec);
-                IVX_LAUNCH_CHECK();
-                sr.rec = rec;
-                sr.run_start = start;
-            }
-            hipLaunchKernelGGL(k_sk_levels_small<MT>, dim3(1), dim3(1024), 0, st, g, sr, mk, c, c_hi, gbase, roff);
-            IVX_LAUNCH_CHECK();
-            uint32_t mseq = 0, msg[4] = {0, 0, 0, 0};
-            int rc = mailbox_publish(&b.st->done, 4, st, &mseq);
-            if (rc != IVX_OK) return rc;
-            rc = mailbox_wait(mseq, st, msg, 4);
-            if (rc != IVX_OK) return rc;
-            gbase = msg[1] + 1;
-            roff += esum;
-            start += esum;
-            dstart += dsum;
-            nlevels += nlv;
-            nsmall_runs++;
-            if (trace) fprintf(stderr, "sk levels %u..%u (%u levels) in one workgroup -> generation %u\n", c, c_hi, nlv, gbase - 1);
-            c = c_hi;
-            continue;
-        }
-        nlevels++;
-        const auto lvl_t0 = std::chrono::steady_clock::now();
-        uint32_t lvl_batches = 0;
-        const unsigned gb = (unsigned)cdiv(cnt, 256);
-        const bool tile_level = is_tile_level(c);
-        const bool split_here = early_of == c; // this level's early part is on its way (queued when the level below started)
-        const uint32_t my_early_cnt = early_cnt;
-        const int my_early_set = early_set;
-        if (tile_level || !persist || trace) {
-            const int rc = sync_gbase();
-            if (rc != IVX_OK) return rc;
-        }
-        const uint32_t g0_gbase = gknown ? gbase : 0u, g0_seq = persist && !tile_level ? 0u : seq;
-        if (const uint32_t chl = g0_chunk(cnt)) { // keys -> sorted -> stamps, run labels, first frontier: one launch
-            const unsigned nch = (unsigned)cdiv((int64_t)cnt, chl);
-            if (chl <= 2048) {
-                WS_CONN_SWITCH(conn, hipLaunchKernelGGL((k_sk_gen0<CC, MT, 2>), dim3(nch), dim3(G0_T), 0, st, g, b.C, mk, I, b.comp, b.tau,
-                                                          b.elist + start, b.sort[0].key_a, b.runlabel, b.lists[0], cnt, chl, c, roff, g0_gbase, g0_seq,
-                                                          b.st, b.g0ctl));
-            } else {
-                WS_CONN_SWITCH(conn, hipLaunchKernelGGL((k_sk_gen0<CC, MT, 4>), dim3(nch), dim3(G0_T), 0, st, g, b.C, mk, I, b.comp, b.tau,
-                                                          b.elist + start, b.sort[0].key_a, b.runlabel, b.lists[0], cnt, chl, c, roff, g0_gbase, g0_seq,
-                                                          b.st, b.g0ctl));
-            }
-            IVX_LAUNCH_CHECK();
-        } else if (split_here) { // the early part is sorted already: late keys, then every stamp in one launch
-            const uint32_t ce = my_early_cnt, cl = cnt - ce;
-            nsplit++;
-            if (cl <= late_max) { // late keys, then every stamp in one launch (the late pairs ranked by brute force in LDS)
-                IVX_HIP(hipStreamWaitEvent(st, side.early[my_early_set], 0)); // (long since: the side stream worked beside the level below)
-                if (cl && late_recs[my_early_set]) {
-                    hipLaunchKernelGGL(k_sk_keys_rec, dim3((unsigned)cdiv(cl, 256)), dim3(256), 0, st, late_recs[my_early_set], b.tau, b.sort[0].key_a,
-                                       b.sort[0].val_a, cl);
-                    IVX_LAUNCH_CHECK();
-                } else if (cl) {
-                    WS_CONN_SWITCH(conn, hipLaunchKernelGGL((k_sk_keys<CC, MT>), dim3((unsigned)cdiv(cl, 256)), dim3(256), 0, st, g, b.C, mk, I, b.comp,
-                                                              b.tau, b.elist + start + ce, b.sort[0].key_a, b.sort[0].val_a, cl, c));
-                    IVX_LAUNCH_CHECK();
-                }
-                const unsigned nwg = (unsigned)(cdiv(ce, 256) + cdiv(cl, LATE_PER_WG));
-                hipLaunchKernelGGL(k_sk_split_assign<MT>, dim3(nwg), dim3(256), (size_t)cl * 12, st, b.ekey[my_early_set], b.eval[my_early_set], ce,
-                                   b.sort[0].key_a, b.sort[0].val_a, cl, mk, b.tau, b.runlabel, b.lists[0], roff, g0_gbase, g0_seq, b.st);
-                IVX_LAUNCH_CHECK();
-            } else { // a late part too long for that (1024^3: 16 000 of a level's 360 000): sorted like any list, placed behind the early part
-                SortOut so;
-                const int rc = sort_list(st, b.sort[0], b.elist + start + ce, cl, c, &so);
-                if (rc != IVX_OK) return rc;
-                IVX_HIP(hipStreamWaitEvent(st, side.early[my_early_set], 0));
-                hipLaunchKernelGGL(k_sk_assign_ranked<MT>, dim3((unsigned)cdiv(ce, 256)), dim3(256), 0, st, b.ekey[my_early_set], b.eval[my_early_set],
-                                   (const uint32_t *)nullptr, 0u, 0x80000000u, mk, b.tau, b.runlabel, b.lists[0], ce, 0u, cnt, roff, g0_gbase, g0_seq, b.st);
-                IVX_LAUNCH_CHECK();
-                hipLaunchKernelGGL(k_sk_assign_ranked<MT>, dim3((unsigned)cdiv(cl, 256)), dim3(256), 0, st, so.key, so.val, so.part, so.shares, so.ch, mk,
-                                   b.tau, b.runlabel, b.lists[0], cl, ce, cnt, roff, g0_gbase, g0_seq, b.st);
-                IVX_LAUNCH_CHECK();
-            }
-            if ((mbits[c >> 5] >> (c & 31u)) & 1u) {
-                hipLaunchKernelGGL(k_sk_mixed<MT>, dim3(gb), dim3(256), 0, st, b.lists[0], mk, cnt, b.st);
-                IVX_LAUNCH_CHECK();
-            }
-        } else {
-            SortOut so;
-            const int rc = sort_list(st, b.sort[0], b.elist + start, cnt, c, &so);
-            if (rc != IVX_OK) return rc;
-            hipLaunchKernelGGL(k_sk_assign_ranked<MT>, dim3(gb), dim3(256), 0, st, so.key, so.val, so.part, so.shares, so.ch, mk, b.tau, b.runlabel,
-                               b.lists[0], cnt, 0u, cnt, roff, g0_gbase, g0_seq, b.st);
-            IVX_LAUNCH_CHECK();
-            if ((mbits[c >> 5] >> (c & 31u)) & 1u) {
-                hipLaunchKernelGGL(k_sk_mixed<MT>, dim3(gb), dim3(256), 0, st, b.lists[0], mk, cnt, b.st);
-                IVX_LAUNCH_CHECK();
-            }
-        }
-        {
-            const int rc = queue_early_after(c); // (this level's stamps are queued: the next level's early part may start beside its flood)
-            if (rc != IVX_OK) return rc;
-        }
-        if (tile_level) {
-            hipLaunchKernelGGL(k_sk_mark_tiles, dim3(gb), dim3(256), 0, st, g, b.lists[0], cnt, b.dirty);
-            IVX_LAUNCH_CHECK();
-            // the level's voxels as a bit plane (in kind[]'s bytes: nobody reads those after the buckets); IVX_SK_PLANE=0: C and I per cell
-            static const bool plane_on = []() { const char *e = getenv("IVX_SK_PLANE"); return !(e && e[0] == '0'); }();
-            const unsigned long long *P = nullptr;
-            if (plane_on && (((uintptr_t)I | (uintptr_t)b.C) & 15) == 0) {
-                hipLaunchKernelGGL(k_sk_level_plane, dim3((unsigned)cdiv(cdiv(g.n, 64) * 8, 256)), dim3(256), 0, st, b.C, I, g.n, c, (unsigned long long *)b.kind);
-                IVX_LAUNCH_CHECK();
-                P = (const unsigned long long *)b.kind;
-            }
-            // Rounds of dirty tiles.  The host never stands between two rounds' kernels: a round's relaxation is launched with a grid
-            // guessed from the previous round's list (1.5 x + 64: the wave front grows slowly) BEFORE the host has read how long this
-            // round's list is -- the read then overlaps the kernel (110 us), and a list longer than the guess gets a second launch
-            // behind it.  (Rounds 1 - 5: list length read first, 20 us of host round trip per round, 61 / 125 rounds per flood.)
-            uint32_t guess = 0;
-            int parity = 0; // (both list counters are zero between two loops: a loop ends on an empty list, which cleared the other one)
-            for (;;) {
-                uint32_t mseq = 0, nl = 0, *cur = nullptr;
-                int rc = ws_build_list_publish(g.ntiles, b.dirty, b.tlist, b.wst, parity, st, &mseq, &cur); // (list, count and mailbox in one launch)
-                if (rc != IVX_OK) return rc;
-                parity ^= 1;
-                if (guess) {
-                    WS_CONN_SWITCH(conn, hipLaunchKernelGGL(k_sk_plateau_relax<CC>, dim3(guess), dim3(256), 0, st, g, I, b.C, b.tau, b.tlist, b.dirty, c, b.st,
-                                                              cur, 0u, P));
-                    IVX_LAUNCH_CHECK();
-                }
-                rc = mailbox_wait(mseq, st, &nl, 1);
-                if (rc != IVX_OK) return rc;
-                if (!nl) break; // (a guessed launch of this round found an empty list and returned)
-                ntile_rounds++;
-                if (nl > guess) {
-                    WS_CONN_SWITCH(conn, hipLaunchKernelGGL(k_sk_plateau_relax<CC>, dim3(nl - guess), dim3(256), 0, st, g, I, b.C, b.tau, b.tlist, b.dirty, c,
-                                                              b.st, cur, guess, P));
-                    IVX_LAUNCH_CHECK();
-                }
-                guess = (uint32_t)std::min<int64_t>(g.ntiles, (int64_t)nl + nl / 2 + 64);
-            }
-            uint32_t mseq = 0, msg[4] = {0, 0, 0, 0};
-            int rc = mailbox_publish(&b.st->done, 4, st, &mseq);
-            if (rc != IVX_OK) return rc;
-            rc = mailbox_wait(mseq, st, msg, 4);
-            if (rc != IVX_OK) return rc;
-            gbase = msg[1] + 1;
-            roff += cnt;
-            start += cnt;
-            dstart += ndl;
-            if (trace)
-                fprintf(stderr, "sk level %u gen0 %u tile-wise -> generation %u, %.0f us\n", c, cnt, gbase - 1,
-                        std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - lvl_t0).count());
-            continue;
-        }
-        if (persist) { // one resident launch; the host moves on without reading anything
-            // (as many workgroups as twice the first frontier asks for, at most res_per_cu per compute unit: all of them must be
-            // resident -- 256 threads, 30 registers and 16 KB of LDS each leave room for eight)
-            // (a large first frontier -- the levels of a 1024^3 volume hold 4 - 5 x 10^5 generation-0 voxels -- is served better by
-            // twice the workgroups with half the entries each: 235 -> 224 ms at 1024^3; at 512^3, 5 x 10^4 voxels, it measured worse)
-            const bool wide = !epb && !erc && cnt >= (1u << 17);
-            const uint32_t lvl_per_wg = per_wg; // (round 6: one pass per workgroup here too -- 512 entries measured 136.7 ms of level chain at 1024^3, 256: 131.6)
-            const int64_t lvl_res = wide ? 2 : res_per_cu;
-            const unsigned nres = (unsigned)std::min<int64_t>(std::max<int64_t>(cdiv(2 * (int64_t)std::max(cnt, ndl), lvl_per_wg), 8), lvl_res * std::max(ncu, 8));
-            if (level_local) { // the rounds on one XCD: an eighth of an eight times wider launch
-                const unsigned want_wgs = (unsigned)std::min<int64_t>(std::max<int64_t>(cdiv(2 * (int64_t)std::max(cnt, ndl), lvl_per_wg), 1), local_wgs);
-                WS_CONN_SWITCH(conn, hipLaunchKernelGGL((k_sk_level<CC, true>), dim3(8 * want_wgs), dim3(256), 0, st, g, b.pmask, b.zmask, b.comp, b.tau,
-                                                          lists, b.dlist + dstart, droot_d + dstart, ndl, lvl_per_wg, solo_max, b.st));
-            } else {
-                WS_CONN_SWITCH(conn, hipLaunchKernelGGL((k_sk_level<CC, false>), dim3(nres), dim3(256), 0, st, g, b.pmask, b.zmask, b.comp, b.tau, lists,
-                                                          b.dlist + dstart, droot_d + dstart, ndl, lvl_per_wg, solo_max, b.st));
-            }
-            IVX_LAUNCH_CHECK();
-            gknown = false;
-            if (trace) {
-                const int rc = sync_gbase();
-                if (rc != IVX_OK) return rc;
-                fprintf(stderr, "sk level %u gen0 %u drained %u -> generation %u, resident, %.0f us\n", c, cnt, ndl, gbase - 1,
-                        std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - lvl_t0).count());
-            }
-            roff += cnt;
-            start += cnt;
-            dstart += ndl;
-            continue;
-        }
-        // rounds are queued in growing batches; one host read per batch (a round after the level's last returns at once)
-        // (a host read costs about as much as eight idle launches: the first batch is sized for a typical level)
-        uint32_t batch = 16, width = cnt;
-        for (;;) {
-            // the frontier can grow a lot inside one batch: the grid is sized for a large one (idle workgroups leave at once)
-            const unsigned nb = (unsigned)std::min<int64_t>(std::max<int64_t>(4 * cdiv(std::max(width, ndl), 256), 1024), 4096);
-            for (uint32_t r = 0; r < batch; r++) {
-                hipLaunchKernelGGL(k_sk_round, dim3(nb), dim3(256), 0, st, g, b.pmask, b.zmask, b.comp, b.tau, lists, b.dlist + dstart, ndl, seq++, per_wg, b.st);
-                IVX_LAUNCH_CHECK();
-            }
-            uint32_t mseq = 0, msg[4] = {0, 0, 0, 0};
-            int rc = mailbox_publish(&b.st->done, 4, st, &mseq);
-            if (rc != IVX_OK) return rc;
-            rc = mailbox_wait(mseq, st, msg, 4);
-            if (rc != IVX_OK) return rc;
-            gbase = msg[1];
-            lvl_batches++;
-            if (msg[0]) break;
-            width = std::max(msg[3], 1u);
-            batch = std::min(batch * 2, 64u);
-        }
-        if (trace)
-            fprintf(stderr, "sk level %u gen0 %u drained %u -> generation %u, %u batches, %.0f us\n", c, cnt, ndl, gbase, lvl_batches,
-                    std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - lvl_t0).count());
-        gbase++;
-        IVX_REQUIRE(gbase < 0x7FFFFFF0u, IVX_EINVAL, "watershed: more than 2^31 generations");
-        roff += cnt;
-        start += cnt;
-        dstart += ndl;
-    }
+    // (as many workgroups as twice the first frontier asks for, at most res_per_cu per compute unit: all of them must be
+    // resident -- 256 threads, 30 registers and 16 KB of LDS each leave room for eight)
+    // (a large first frontier -- the levels of a 1024^3 volume hold 4 - 5 x 10^5 generation-0 voxels -- is served better by
+    // twice the workgroups with half the entries each: 235 -> 224 ms at 1024^3; at 512^3, 5 x 10^4 voxels, it measured worse)
+    const bool wide = !x.k.res_tuned && cnt >= (1u << 17);
+    const uint32_t per_wg = x.k.per_wg; // (round 6: one pass per workgroup here too -- 512 entries measured 136.7 ms of level chain at 1024^3, 256: 131.6)
+    const int64_t lvl_res = wide ? 2 : x.k.res_per_cu;
+    const unsigned nres = (unsigned)std::min<int64_t>(std::max<int64_t>(cdiv(2 * (int64_t)std::max(cnt, ndl), per_wg), 8), lvl_res * std::max(x.ncu, 8));
+    WS_CONN_SWITCH(x.conn, hipLaunchKernelGGL(k_sk_level<CC>, dim3(nres), dim3(256), 0, x.st, x.g, b.pmask, b.zmask, b.comp, b.tau, lists,
+                                                b.dlist + cur.dstart, x.droot_d + cur.dstart, ndl, per_wg, x.k.solo_max, b.st));
+    IVX_LAUNCH_CHECK();
+    cur.gknown = false;
+    return IVX_OK;
+}
 
-    {
-        const int rc = sync_gbase();
-        if (rc != IVX_OK) return rc;
-        IVX_REQUIRE(gbase < 0x7FFFFFF0u, IVX_EINVAL, "watershed: more than 2^31 generations");
+// ---- 3. the level chain: per non-empty level, ascending -- pick the kind of level, stamp, queue the next early part, run, advance
+template <typename MT>
+static int sk_level_chain(SkCtx<MT> &x, SkCursor &cur) {
+    const SkState *dst = x.b.st;
+    for (uint32_t c = 0; c < 65535; c++) {
+        const uint32_t cnt = x.hist[c], ndl = x.dhist[c];
+        if (!cnt) { // (no voxel of the level at all: a level's drained voxels hang off its generation 0)
+            cur.dstart += ndl;
+            continue;
+        }
+        int rc;
+        if (x.is_small(c)) { // a run of consecutive small levels: one launch
+            if ((rc = sk_run_small_levels(x, cur, c, &c)) != IVX_OK) return rc;
+            continue;
+        }
+        x.nlevels++;
+        const auto lvl_t0 = std::chrono::steady_clock::now();
+        const bool tile_level = x.is_tile_level(c);
+        if ((tile_level || x.k.trace) && (rc = cur.sync_gbase(dst, x.st)) != IVX_OK) return rc;
+        if ((rc = sk_stamp_gen0(x, cur, c)) != IVX_OK) return rc;
+        // (this level's stamps are queued: the next level's early part may start beside its flood)
+        if ((rc = sk_queue_early_after(x, cur, c)) != IVX_OK) return rc;
+        if ((rc = tile_level ? sk_run_tile_level(x, cur, c) : sk_run_resident_level(x, cur, c)) != IVX_OK) return rc;
+        if (x.k.trace) {
+            if ((rc = cur.sync_gbase(dst, x.st)) != IVX_OK) return rc;
+            const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - lvl_t0).count();
+            if (tile_level) fprintf(stderr, "sk level %u gen0 %u tile-wise -> generation %u, %.0f us\n", c, cnt, cur.gbase - 1, us);
+            else fprintf(stderr, "sk level %u gen0 %u drained %u -> generation %u, resident, %.0f us\n", c, cnt, ndl, cur.gbase - 1, us);
+        }
+        cur.advance(cnt, ndl);
     }
+    const int rc = cur.sync_gbase(dst, x.st);
+    if (rc != IVX_OK) return rc;
+    IVX_REQUIRE(cur.gbase < 0x7FFFFFF0u, IVX_EINVAL, "watershed: more than 2^31 generations");
+    return IVX_OK;
+}
+
+template <typename MT>
+static int sk_run(const WsGeom &g, const uint16_t *I, const MT *mk, MT *out, int32_t *out32, uint8_t *out8, uint16_t *cost_out,
+                  int64_t *stats, hipStream_t st) {
+    SkCtx<MT> x;
+    x.g = g;
+    x.conn = conn_of(g.smask);
+    x.I = I;
+    x.mk = mk;
+    x.st = st;
+    x.k = sk_read_knobs();
+    SkBufs &b = x.b;
+    sk_layout(g, nullptr, &b);
+    void *mem = nullptr;
+    IVX_REQUIRE(ws_get_s(WS_WSIFT, st, b.bytes, &mem) == IVX_OK, IVX_ENOMEM, "watershed: %zu bytes of scratch", b.bytes);
+    sk_layout(g, (char *)mem, &b);
+
+    WsTimer tm;
+    tm.on = stats != nullptr;
+    tm.mark(st);
+    int rc = sk_cost_map(x);
+    if (rc != IVX_OK) return rc;
+    if (x.M == 0) { // no marker: nothing is ever queued, every label stays 0
+        if (out) IVX_HIP(hipMemsetAsync(out, 0, (size_t)g.n * sizeof(MT), st));
+        if (out32) IVX_HIP(hipMemsetAsync(out32, 0, (size_t)g.n * 4, st));
+        if (out8) IVX_HIP(hipMemsetAsync(out8, 0, (size_t)g.n, st));
+        if (cost_out) IVX_HIP(hipMemsetAsync(cost_out, 0xFF, (size_t)g.n * 2, st));
+        if (stats) memset(stats, 0, 16 * sizeof(int64_t));
+        return IVX_OK;
+    }
+    if (cost_out) IVX_HIP(hipMemcpyAsync(cost_out, b.C, (size_t)g.n * 2, hipMemcpyDeviceToDevice, st));
+    tm.mark(st);
+    if ((rc = sk_bucket_levels(x)) != IVX_OK) return rc;
+    tm.mark(st);
+    SkCursor cur;
+    if ((rc = sk_level_chain(x, cur)) != IVX_OK) return rc;
     tm.mark(st);
     // ---- 4. labels -------------------------------------------------------------------------------------------
-    hipLaunchKernelGGL(k_sk_labels<MT>, dim3(gl), dim3(256), 0, st, g.n, b.comp, b.tau, b.runlabel, out, out32, out8);
+    hipLaunchKernelGGL(k_sk_labels<MT>, dim3((unsigned)cdiv(g.n, 256)), dim3(256), 0, st, g.n, b.comp, b.tau, b.runlabel, out, out32, out8);
     IVX_LAUNCH_CHECK();
     tm.mark(st);
     SkState hs;
-    SkG0Ctl hg;
     IVX_HIP(hipMemcpyAsync(&hs, b.st, sizeof(hs), hipMemcpyDeviceToHost, st));
-    IVX_HIP(hipMemcpyAsync(&hg, b.g0ctl, sizeof(hg), hipMemcpyDeviceToHost, st));
     IVX_HIP(hipStreamSynchronize(st));
-    IVX_REQUIRE(!hg.fail, IVX_EHIP, "watershed: a generation-0 launch lost its device-wide barrier (workgroups not resident)");
-    if (trace) fprintf(stderr, "sk levels whose early part was sorted beside the level below: %lld of %lld\n", (long long)nsplit, (long long)nlevels);
-    if (trace && SK_TICKS)
+    if (x.k.trace) fprintf(stderr, "sk levels whose early part was sorted beside the level below: %lld of %lld\n", (long long)x.nsplit, (long long)x.nlevels);
+    if (x.k.trace && SK_TICKS)
         fprintf(stderr, "sk rounds, workgroup 0 (%u rounds): A: loads %.0f us, plateau offers %.0f, basin offers %.0f, flush %.0f, drain %.0f | B: loads %.0f, offers %.0f, flush %.0f, drain %.0f | word wait %.0f, ticket %.0f\n",
                 hs.ticks[14], hs.ticks[0] * 0.01, hs.ticks[1] * 0.01, hs.ticks[2] * 0.01, hs.ticks[3] * 0.01, hs.ticks[4] * 0.01, hs.ticks[6] * 0.01,
                 hs.ticks[7] * 0.01, hs.ticks[9] * 0.01, hs.ticks[10] * 0.01, hs.ticks[12] * 0.01, hs.ticks[13] * 0.01);
-    if (trace)
-        fprintf(stderr, "sk generation-0 launches, workgroup 0: keys %.0f us, chunk sort %.0f, barrier %.0f, ranks %.0f, stamps %.0f (sums over the flood)\n",
-                hg.ticks[0] * 0.01, hg.ticks[1] * 0.01, hg.ticks[2] * 0.01, hg.ticks[3] * 0.01, hg.ticks[4] * 0.01);
     if (stats) {
-        stats[0] = rounds; stats[1] = visits; stats[2] = nlevels; stats[3] = gbase; stats[4] = M; stats[5] = (int64_t)ngen0;
+        stats[0] = x.rounds; stats[1] = x.visits; stats[2] = x.nlevels; stats[3] = cur.gbase; stats[4] = x.M; stats[5] = (int64_t)x.ngen0;
         stats[6] = hs.mixed; stats[7] = hs.rounds;
         for (int i = 8; i < 16; i++) stats[i] = 0;
         tm.read(stats + 8); // [8] costs, [9] generation 0, [10] level chain, [11] labels (microseconds)
-        stats[12] = hs.brounds; stats[13] = hs.gens; stats[14] = nsmall_runs; stats[15] = ntile_rounds;
+        stats[12] = hs.brounds; stats[13] = hs.gens; stats[14] = x.nsmall_runs; stats[15] = x.ntile_rounds;
     }
     return IVX_OK;
 }
