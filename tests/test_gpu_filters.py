@@ -9,12 +9,12 @@ import numpy as np
 import pytest
 import scipy.ndimage as ndi
 
+from _filters_ref import AXIS, _fn, _ref, _ref_2d
 from conftest import synth_volume
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_filters.npz")
-AXIS = {"Axial": 0, "Coronal": 1, "Sagittal": 2}
 
 
 @pytest.fixture(scope="module")
@@ -25,12 +25,6 @@ def golden():
         vn, ft, v, dim, ori = str(name).split("|")
         cases.append((i, vn, int(ft), float(v), dim, ori))
     return g, cases
-
-
-def _fn(ft):
-    from invesalius3_amd import filters as F
-    return {0: F.gaussian_blur_filter, 1: F.median_blur_filter, 2: F.mean_blur_filter, 3: F.sharpening_filter,
-            4: F.despeckle_filter, 5: F.border_detection_filter}[ft]
 
 
 @pytest.mark.parametrize("ft", range(6))
@@ -86,28 +80,7 @@ def test_golden_border_no_normalize_and_2d_image(ivxlib, golden):
             assert np.array_equal(_fn(int(ft))(g["img2d"], float(v)), g[key]), key
 
 
-# -- live scipy, the reference's formulas restated on scipy (filters.py:5-66) -------------------------------------------
-def _ref(ft, m, v, normalize=True):
-    if ft in (0, 4):
-        return ndi.gaussian_filter(m, sigma=v)
-    if ft == 1:
-        return ndi.median_filter(m, size=max(3, min(int(2 * v + 1), 5)))
-    if ft == 2:
-        return ndi.uniform_filter(m, size=int(2 * v + 1)).astype(m.dtype)
-    if ft == 3:
-        f = m.astype(float)
-        return np.clip(f + v * 0.5 * (f - ndi.gaussian_filter(f, sigma=1.0)), m.min(), m.max()).astype(m.dtype)
-    f = ndi.gaussian_filter(m.astype(float), sigma=v)
-    mag = np.sqrt(sum(ndi.sobel(f, axis=a) ** 2 for a in range(m.ndim)))
-    if not normalize:
-        return mag.astype(m.dtype)
-    lo, hi = float(m.min()), float(m.max())
-    mr = mag.max() - mag.min()
-    if mr > 0:
-        mag = (mag - mag.min()) / mr * (hi - lo) + lo
-    return mag.astype(m.dtype)
-
-
+# -- live scipy, the reference's formulas restated on scipy (filters.py:5-66; _ref and _ref_2d of _filters_ref.py) ------
 LIVE = [(0, 1.0), (0, 2.5), (1, 1.0), (1, 1.6), (1, 3.0), (2, 0.5), (2, 3.0), (3, 1.0), (4, 0.7), (5, 1.0), (5, 2.0)]
 
 
@@ -133,12 +106,7 @@ def test_live_scipy_2d_mode(ivxlib, ft, v, ori):
     """apply_image_filter's 2-D mode == the reference's slice loop with live scipy on each slice."""
     from invesalius3_amd import slice_
     img = synth_volume((12, 17, 22), seed=3)
-    ax = AXIS[ori]
-    want = np.zeros_like(img)
-    for k in range(img.shape[ax]):
-        sl = (slice(None),) * ax + (k,)
-        want[sl] = _ref(ft, img[sl], v)
-    assert np.array_equal(slice_.apply_image_filter(img, ft, v, "2D", ori), want)
+    assert np.array_equal(slice_.apply_image_filter(img, ft, v, "2D", ori), _ref_2d(ft, img, v, ori))
 
 
 def test_border_magnitude_over_int16_no_normalize(ivxlib):
