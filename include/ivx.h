@@ -561,6 +561,12 @@ int ivx_dev_flood_run(const ivx_flood_plan *p, const uint64_t *cand, uint64_t *r
 int ivx_dev_flood_grow(const ivx_flood_plan *p, int dtype, const void *data, double t0, double t1,
                        const int64_t *seeds_xyz, int64_t nseeds, uint64_t *cand, uint64_t *reached, void *scratch,
                        int *rounds, void *stream);
+/* What the rounds of the last flood on `scratch` cost: out[0] = tile visits (the sum of the rounds' list lengths), out[1] =
+ * the length of the first round's list.  Queue-ordered on `stream` (it waits for what the stream holds), one small read.
+ * Only the rounds of tile visits count: when a long thin region went to the union-find engine after 48 rounds the figure
+ * covers the rounds before that, and after a flood that ran no round at all (IVX_FLOOD_MODE=ccl) the two words are not
+ * defined (that path does not touch the counters). */
+int ivx_dev_flood_visits(const ivx_flood_plan *p, const void *scratch, uint32_t out[2], void *stream);
 /* host only, for tests: the path ivx_dev_flood_grow takes for this plan and `nseeds` seeds, from the functions that size its
  * launches (no device call).  out[0] coarse pass on (0/1), out[1] block width in voxels along x (16 / 32 / 64), out[2] blocks
  * per tile along x, out[3] lanes of the coarse workgroup, out[4] rows of tiles per lane = ceil(rows / lanes) (out[1..4] are 0

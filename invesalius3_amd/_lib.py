@@ -171,3 +171,11 @@ def set_device(i: int):
 
 def synchronize():
     check(lib().ivx_device_synchronize())
+
+
+def flood_visits(plan: FloodPlan, scratch, stream=None):
+    """(tile visits, length of the first round's list) of the last region-growing flood that ran on `scratch` (a device
+    pointer): ivx_dev_flood_visits, queue-ordered on `stream`, one small read."""
+    out = (ctypes.c_uint32 * 2)()
+    check(lib().ivx_dev_flood_visits(ctypes.byref(plan), scratch, out, stream), "flood_visits")
+    return int(out[0]), int(out[1])

@@ -53,6 +53,8 @@ static int make_tiles(const ivx_flood_plan *p, Tiles *t) {
 
 // scratch: dirty[2][ntiles] u8 | counter ring | seed staging | status words | round lists | coarse-pass row words
 constexpr size_t SEED_CHUNK = 4096;
+// the counter block: counter ring, the resident launch's control words, the rounds' list lengths (k_flood.hip)
+constexpr int FLOOD_CNT_DWORDS = 128;
 static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 struct FScratch {
     size_t off_dirty0, off_dirty1, off_cnt, off_seeds, off_status, off_list0, off_list1;
@@ -63,7 +65,7 @@ static FScratch make_fscratch(const Tiles &t) {
     s.off_dirty0 = 0;
     s.off_dirty1 = al256((size_t)t.ntiles);
     s.off_cnt = al256(s.off_dirty1 + (size_t)t.ntiles);
-    s.off_seeds = al256(s.off_cnt + 64 * 4); // everything before off_seeds is zeroed by flood_clear
+    s.off_seeds = al256(s.off_cnt + FLOOD_CNT_DWORDS * 4); // everything before off_seeds is zeroed by flood_clear
     s.off_status = al256(s.off_seeds + SEED_CHUNK * 3 * 8);
     s.off_list0 = al256(s.off_status + 64);
     s.off_list1 = al256(s.off_list0 + (size_t)t.ntiles * 4);

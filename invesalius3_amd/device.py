@@ -409,6 +409,10 @@ class DeviceVolume:
                 self._apply_reached(fill, select_value, shared)
         return rounds.value
 
+    def flood_visits(self):
+        """(tile visits, length of the first round's list) of the last flood of this volume (L.flood_visits)"""
+        return L.flood_visits(self.plan, self.flood_scratch.ptr, self.stream)
+
     def _before_flood(self):
         """the reached plane is about to be cleared: a deferred out_mask write that is still wanted must land first, and a
         note that describes the mask's bytes through that plane dies with it"""

@@ -1,11 +1,15 @@
 """CPU model of the region-growing engine's ROUND STRUCTURE (k_flood.hip): coarse pass on all-candidate blocks, then rounds of
 dirty-tile visits -- a visit = at most `itcap` local iterations of "OR of the 3 x 3 neighbour rows, each dilated by one voxel
 in x, AND candidates, then close the x-runs" on a tile staged with a one-voxel halo, the halo constant during the visit --
-with the wake-up rule of the kernel (a changed face wakes the neighbours that can see it, an exhausted tile wakes itself).
+with the wake-up rule of the kernel (--wake open-yz: a neighbour tile is woken when the staged halo holds a voxel of it that
+was unreached, lies in the 3 x 3 x 3 neighbourhood of one of the visit's new bits and, in the y / z halo rows, is a candidate
+-- the voxels beside the tile's words are tested by "unreached" alone; open: candidates there too; faces: the rule before
+these, a changed face wakes every neighbour that can see it; an exhausted tile wakes itself and a tile without an unreached
+candidate is closed for good under all three).
 It counts what the GPU timeline is made of: productive rounds, tile visits, local iterations; the result is checked against
 scipy.ndimage.label.  Use: explore tile shapes / iteration caps / coarse-block sizes offline before spending GPU time.
 
-    python tools/sim_flood.py [n=512] [--ty 16 --tz 16 --itcap 16 --block 16]      (~1-3 min per configuration at 512^3)"""
+    python tools/sim_flood.py [n=512] [--ty 16 --tz 16 --itcap 24 --block 16 --wake open-yz]   (~1-3 min per configuration at 512^3)"""
 import argparse
 import sys
 import time
@@ -63,12 +67,34 @@ def visit(Rw, Cw, itcap):
     return R[:, 1:-1, 1:-1, 1:-1], its, exhausted
 
 
+def wake_dirs(rule, chg, Rw, Cw):
+    """the set of (dz, dy, dx) tile offsets one visit wakes: chg = its new bits (tile interior), Rw / Cw = the reached and
+    candidate windows as staged (one-voxel halo)"""
+    if rule == "faces":
+        zl, zh = chg[0].any(), chg[-1].any()
+        yl, yh = chg[:, 0].any(), chg[:, -1].any()
+        xl, xh = chg[:, :, 0].any(), chg[:, :, -1].any()
+        return {(dz, dy, dx) for dz in (-1, 0, 1) for dy in (-1, 0, 1) for dx in (-1, 0, 1)
+                if (dz or dy or dx) and (dz == 0 or (zl if dz < 0 else zh)) and (dy == 0 or (yl if dy < 0 else yh))
+                and (dx == 0 or (xl if dx < 0 else xh))}
+    near = ndimage.binary_dilation(np.pad(chg, 1), structure=np.ones((3, 3, 3), bool))
+    front = near & Cw & ~Rw
+    if rule == "open-yz":  # no candidate bit of the x-neighbour words is looked at
+        front[:, :, 0] = near[:, :, 0] & ~Rw[:, :, 0]
+        front[:, :, -1] = near[:, :, -1] & ~Rw[:, :, -1]
+    front[1:-1, 1:-1, 1:-1] = False
+    sl = {-1: slice(0, 1), 0: slice(1, -1), 1: slice(-1, None)}
+    return {(dz, dy, dx) for dz in (-1, 0, 1) for dy in (-1, 0, 1) for dx in (-1, 0, 1)
+            if (dz or dy or dx) and front[sl[dz], sl[dy], sl[dx]].any()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("n", nargs="?", type=int, default=512)
     ap.add_argument("--ty", type=int, default=16)
     ap.add_argument("--tz", type=int, default=16)
-    ap.add_argument("--itcap", type=int, default=16)
+    ap.add_argument("--itcap", type=int, default=24)
+    ap.add_argument("--wake", choices=("faces", "open", "open-yz"), default="open-yz", help="the wake-up rule (open-yz: the kernel's)")
     ap.add_argument("--block", type=int, default=16, help="coarse blocks of block^3 voxels (0: no coarse pass)")
     ap.add_argument("--recoarse", type=int, default=0, help="after every round from this one on, every all-candidate block that "
                     "holds a reached voxel floods its component of the block graph again (0: the coarse pass runs once)")
@@ -109,7 +135,8 @@ def main():
         return set(map(tuple, np.argwhere(front.reshape(ntz, tz, nty, ty, ntx, TX).any(axis=(1, 3, 5)))))
 
     dirty = tiles_near(R)
-    rounds = visits = iters = 0
+    closed = set()  # tiles whose last visit left no candidate unreached: the kernel never enlists them again (CLOSED)
+    rounds = visits = iters = wasted = shut = 0
     hist = []
     while dirty:
         tl = sorted(dirty)
@@ -121,33 +148,35 @@ def main():
             Cw[i] = Cp[a_ * tz:a_ * tz + tz + 2, b_ * ty:b_ * ty + ty + 2, c_ * TX:c_ * TX + TX + 2]
         newR, its, exhausted = visit(Rw, Cw, a.itcap)
         nxt = set()
-        gained = 0
+        gained = idle = 0
+        asked = []
         for i, (a_, b_, c_) in enumerate(tl):
             old = Rw[i, 1:-1, 1:-1, 1:-1]
             chg = newR[i] & ~old
+            if not (Cw[i, 1:-1, 1:-1, 1:-1] & ~newR[i]).any():
+                closed.add((a_, b_, c_))
             if not chg.any():
+                idle += 1
                 continue
             gained += int(chg.sum())
             Rp[a_ * tz + 1:a_ * tz + tz + 1, b_ * ty + 1:b_ * ty + ty + 1, c_ * TX + 1:c_ * TX + TX + 1] = newR[i]
-            zl, zh = chg[0].any(), chg[-1].any()
-            yl, yh = chg[:, 0].any(), chg[:, -1].any()
-            xl, xh = chg[:, :, 0].any(), chg[:, :, -1].any()
-            for dz in (-1, 0, 1):
-                for dy in (-1, 0, 1):
-                    for dx in (-1, 0, 1):
-                        if not (dz or dy or dx):
-                            continue
-                        if (dz == 0 or (zl if dz < 0 else zh)) and (dy == 0 or (yl if dy < 0 else yh)) and (dx == 0 or (xl if dx < 0 else xh)):
-                            t = (a_ + dz, b_ + dy, c_ + dx)
-                            if 0 <= t[0] < ntz and 0 <= t[1] < nty and 0 <= t[2] < ntx:
-                                nxt.add(t)
+            for dz, dy, dx in wake_dirs(a.wake, chg, Rw[i], Cw[i]):
+                t = (a_ + dz, b_ + dy, c_ + dx)
+                if 0 <= t[0] < ntz and 0 <= t[1] < nty and 0 <= t[2] < ntx:
+                    asked.append(t)
             if exhausted[i]:
                 nxt.add((a_, b_, c_))
+        asked = set(asked)
+        shut += len(asked & closed)
+        nxt |= asked - closed
         rounds += 1
         visits += T
+        wasted += idle
         iters += int(its.sum())
         hist.append((T, int(its.max()), gained))
-        print("round %2d: %5d tiles, max %2d / mean %.1f iterations, %8d voxels gained" % (rounds, T, its.max(), its.mean(), gained), flush=True)
+        print("round %2d: %5d tiles (%5d gained nothing), max %2d / mean %.1f iterations, %8d voxels gained"
+              % (rounds, T, idle, its.max(), its.mean(), gained), flush=True)
+        print("          wakes %d tiles, %d of them closed" % (len(asked), len(asked & closed)), flush=True)
         if not gained:
             rounds -= 1  # (the round that finds nothing is the GPU's first empty round only if its list is empty: here it is a visit round)
         dirty = nxt
@@ -167,8 +196,9 @@ def main():
                 print("          coarse pass again: %d more blocks wholly reached, %d voxels, %d tiles enlisted" % (whole.sum(), add.sum(), len(near)), flush=True)
     got = Rp[1:-1, 1:-1, 1:-1]
     ok = bool(np.array_equal(got, want))
-    print("tile %dx%dx%d itcap %d block %d: %d productive rounds, %d visits, %d tile-iterations, == scipy component: %s (%.0f s)"
-          % (TX, ty, tz, a.itcap, a.block, rounds, visits, iters, ok, time.time() - t0))
+    print("tile %dx%dx%d itcap %d block %d wake %s: %d productive rounds, %d visits (%d gained nothing), %d wake-ups dropped at "
+          "closed tiles, %d tile-iterations, == scipy component: %s (%.0f s)"
+          % (TX, ty, tz, a.itcap, a.block, a.wake, rounds, visits, wasted, shut, iters, ok, time.time() - t0))
     return 0 if ok else 1
 
 
