@@ -421,6 +421,52 @@ int ivx_mesh_remove_nonvisible(const float *verts, int64_t nverts, const int32_t
                                const ivx_mesh_view *views, int nviews, int remove_visible, float *out_verts,
                                int32_t *out_faces, int64_t *out_nverts, int64_t *out_ntris);
 
+/* Surface connectivity tools beyond keep-largest (Surface.OnSplitSurface / OnSeedSurface, invesalius/data/surface.py:319-411;
+ * pu.SplitDisconectedParts / pu.JoinSeedsParts, invesalius/data/polydata_utils.py:206-278: vtkPolyDataConnectivityFilter in its
+ * SpecifiedRegions and PointSeededRegions modes), DESIGN 7h.  Regions are keep-largest's: triangles joined through shared point
+ * ids.  Region r is the r-th region in ascending order of its first (smallest-index) triangle -- the `r` of AddSpecifiedRegion.
+ *   ivx_*_mesh_region_labels  tri_labels[t] = region of triangle t; vert_labels[v] = region of point v, -1 when no triangle uses
+ *                             it (either array may be NULL).
+ *   ivx_*_mesh_split          every part at once: out_faces holds all ntris triangles grouped by region (original order inside
+ *                             a region) with PART-LOCAL point ids, out_verts the used points grouped the same way (original
+ *                             order inside a region), table[r] = {triangle offset, triangles, point offset, points} of part r.
+ *                             Output arrays NULL -> sizes only (*out_nverts, *nparts); the host form takes the capacities of
+ *                             out_verts / table in through *out_nverts / *nparts on the filling call (out_faces: ntris rows).
+ *   ivx_*_mesh_parts_mass     out[8 r ..] = ivx_*_mesh_mass_properties' out8 of part r (its own cell count in the weights).
+ *                             The number of launches does not depend on the number of parts.  small_max: parts of up to that
+ *                             many triangles are reduced by one wave each, larger ones by the two-kernel path of
+ *                             ivx_dev_mesh_mass_properties on their slice (<= 0: the default, 1024); `ntris` = all triangles.
+ *   ivx_*_mesh_select_seeded  the union of the regions that hold a seed point, as triangles in order on their points compacted
+ *                             in order.  Duplicate seeds are harmless, a seed no triangle uses selects nothing, no seeds give an
+ *                             empty mesh.  Host form: a seed outside [0, nverts) is IVX_EDOM (DEVIATION: VTK skips negative ids
+ *                             and reads past its array for large ones); the device form ignores such seeds.
+ *   ivx_*_mesh_nearest_point  id of the point with the smallest squared distance to xyz (host doubles), computed in double as
+ *                             (dx dx + dy dy) + dz dz; the smallest id on a tie; -1 for no points.
+ *   ivx_dev_partition_u32     the stable many-way partition behind the split: order[] = item indices grouped by key (keys < nkeys,
+ *                             original order inside a key), offsets[k] = items with a key below k (nkeys + 1 entries).
+ * Device forms take device pointers (seeds, table, out_id included); sizes come back on the host.  PARITY UNPINNED vs VTK. */
+int ivx_dev_mesh_region_labels(int64_t nverts, const int32_t *faces, int64_t ntris, int32_t *tri_labels, int32_t *vert_labels,
+                               int64_t *nregions, int64_t *nused_verts /* may be NULL */, void *stream);
+int ivx_dev_mesh_split(const float *verts, int64_t nverts, const int32_t *faces, int64_t ntris, float *out_verts,
+                       int64_t max_verts, int32_t *out_faces, int64_t max_tris, int64_t *table, int64_t max_parts,
+                       int64_t *out_nverts, int64_t *nparts, void *stream);
+int ivx_dev_mesh_parts_mass(const float *verts, const int32_t *faces, const int64_t *table, int64_t nparts, int64_t ntris,
+                            int64_t small_max, double *out, void *stream);
+int ivx_dev_mesh_select_seeded(const float *verts, int64_t nverts, const int32_t *faces, int64_t ntris, const int32_t *seeds,
+                               int64_t nseeds, float *out_verts, int64_t max_verts, int32_t *out_faces, int64_t max_tris,
+                               int64_t *out_nverts, int64_t *out_ntris, void *stream);
+int ivx_dev_mesh_nearest_point(const float *verts, int64_t nverts, const double *xyz /* host */, int32_t *out_id, void *stream);
+int ivx_dev_partition_u32(const uint32_t *keys, int64_t n, uint32_t nkeys, uint32_t *order, uint32_t *offsets, void *stream);
+int ivx_mesh_region_labels(int64_t nverts, const int32_t *faces, int64_t ntris, int32_t *tri_labels, int32_t *vert_labels,
+                           int64_t *nregions);
+int ivx_mesh_split(const float *verts, int64_t nverts, const int32_t *faces, int64_t ntris, float *out_verts, int32_t *out_faces,
+                   int64_t *table, int64_t *out_nverts, int64_t *nparts);
+int ivx_mesh_parts_mass(const float *verts, int64_t nverts, const int32_t *faces, int64_t ntris, const int64_t *table,
+                        int64_t nparts, double *out);
+int ivx_mesh_select_seeded(const float *verts, int64_t nverts, const int32_t *faces, int64_t ntris, const int64_t *seeds,
+                           int64_t nseeds, float *out_verts, int32_t *out_faces, int64_t *out_nverts, int64_t *out_ntris);
+int ivx_mesh_nearest_point(const float *verts, int64_t nverts, const double *xyz, int64_t *id);
+
 /* ------------------------------------------------------------------------------------------------
  * context-aware smoothing of the indexed surface
  *   replaces context_aware_smoothing           invesalius_rs/src/mesh_py.rs:7-330 -> mesh.rs:27-86

@@ -3,6 +3,8 @@
     python -m invesalius3_amd.headless CASE.inv3 --threshold 226 3071 --seed 250 260 100 --largest --smooth \\
         --stl bone.stl --save CASE_out.inv3
     python -m invesalius3_amd.headless CASE.inv3 --threshold 226 3071 --largest --remove-nonvisible --stl shell.stl
+    python -m invesalius3_amd.headless CASE.inv3 --threshold 226 3071 --surface-seed 120.5 98.0 40.0 --stl part.stl
+    python -m invesalius3_amd.headless CASE.inv3 --threshold 226 3071 --split parts/ --split-min-triangles 100
     python -m invesalius3_amd.headless CASE.inv3 --filter median 3 --threshold 226 3071 --stl bone.stl
     python -m invesalius3_amd.headless CASE.inv3 --segment brain --weights brain_mri_t1.pt --stl brain.stl
     python -m invesalius3_amd.headless CASE.inv3 --render "Bone + Skin" --presets-dir DIR --view iso --png out.png
@@ -11,7 +13,7 @@
 What the reference does through its GUI for the same result: Slice.SetMaskThreshold / do_threshold_to_all_slices
 (invesalius/data/slice_.py:1240-1247, 1739-1769), the Image Filters dialog (slice_.py:2330-2539), the deep-learning segmentation (segmentation/deep_learning/segment.py), the 3-D view's volume rendering (data/volume.py:575-707), the region-growing tool (styles.py:3151-3216),
 SurfaceManager.AddNewActor -> create_surface_piece / join_process_surface (surface.py:1362-1380,
-surface_process.py:71-472), Remove non-visible faces (polydata_utils.py:363-455) and vtkSTLWriter (surface.py:1827-1829).  No wx, no VTK here; one JSON line on stdout."""
+surface_process.py:71-472), Remove non-visible faces (polydata_utils.py:363-455), the surface connectivity tools (Surface.OnSplitSurface / OnSeedSurface, surface.py:319-411) and vtkSTLWriter (surface.py:1827-1829).  No wx, no VTK here; one JSON line on stdout."""
 from __future__ import annotations
 
 import argparse
@@ -145,6 +147,18 @@ def run(args) -> dict:
                                                       ctypes.byref(nr), vol.stream), "keep_largest")
             verts_buf, faces_buf, nv, nt = keep_v, keep_f, n1.value, n2.value
             out["largest"] = {"regions": nr.value, "vertices": nv, "triangles": nt}
+        seeded = None
+        if args.surface_seed and nt:
+            # Surface.OnSeedSurface -> pu.JoinSeedsParts (surface.py:363-411): the GUI's point pick is the nearest point here
+            from . import polydata_utils as pu
+            whole = pu.DeviceMesh(verts_buf, nv, faces_buf, nt, vol.stream)
+            picks = [tuple(args.surface_seed[i:i + 3]) for i in range(0, len(args.surface_seed), 3)]
+            with vol.timer.span("surface_seed"):
+                ids = [whole.nearest_point(xyz) for xyz in picks]
+                seeded = whole.select_seeded(ids)
+            out["surface_seed"] = {"points": [list(xyz) for xyz in picks], "point_ids": ids, "vertices": seeded.nverts,
+                                   "triangles": seeded.ntris}
+            verts_buf, faces_buf, nv, nt = seeded.verts, seeded.faces, seeded.nverts, seeded.ntris
         shell = None
         if args.remove_nonvisible and nt:
             # Surface.OnRemoveNonVisibleFaces -> pu.RemoveNonVisibleFaces (surface.py:413-435) on the resident mesh
@@ -178,6 +192,26 @@ def run(args) -> dict:
             faces = faces_buf.download((nt, 3), np.int32)
             sp.write_stl_binary(args.stl, verts[faces])
             out["stl"] = args.stl
+        if args.split is not None:
+            # Surface.OnSplitSurface -> pu.SplitDisconectedParts (surface.py:319-361) on the final surface: one STL per part, in
+            # region order, and every part's measures (CreateSurfaceFromPolydata takes them per part, surface.py:953-960)
+            from . import polydata_utils as pu
+            os.makedirs(args.split, exist_ok=True)
+            with vol.timer.span("split"):
+                parts = pu.DeviceMesh(verts_buf, nv, faces_buf, nt, vol.stream).split()
+                measures = parts.mass_properties()
+            table = parts.table
+            rows = []
+            for r in range(parts.n):
+                if int(table[r, 1]) < args.split_min_triangles:
+                    continue
+                pv, pf = parts.download(r)
+                name = os.path.join(args.split, "part_%05d.stl" % r)
+                sp.write_stl_binary(name, pv[pf])
+                rows.append({"part": r, "triangles": int(table[r, 1]), "vertices": int(table[r, 3]), "volume": float(measures[r, 0]),
+                             "area": float(measures[r, 1]), "stl": name})
+            parts.close()
+            out["split"] = {"regions": parts.n, "min_triangles": args.split_min_triangles, "parts": rows}
         if args.save:
             rec = prj.new_mask(proj, args.mask_name, (lo, hi))
             rec.matrix[1:, 1:, 1:] = mask
@@ -200,6 +234,8 @@ def run(args) -> dict:
                 b.close()
         if shell is not None:
             shell.close()
+        if seeded is not None:
+            seeded.close()
     finally:
         vol.close()
         for b in bound:
@@ -212,7 +248,8 @@ def run(args) -> dict:
 def _render_only(args) -> bool:
     """--render without anything that asks for a mask or a surface: the image is all there is to make"""
     return (args.threshold is None and args.segment is None and not args.seed and not args.stl and not args.save
-            and not args.largest and not args.smooth and not args.remove_nonvisible and "--mask" not in (args.argv or []))
+            and not args.largest and not args.smooth and not args.remove_nonvisible and not args.surface_seed
+            and args.split is None and "--mask" not in (args.argv or []))
 
 
 def _strct(conn: int) -> np.ndarray:
@@ -253,7 +290,16 @@ def main(argv=None) -> int:
     ap.add_argument("--size", nargs=2, type=int, metavar=("W", "H"), default=(512, 512), help="image size (default 512 512)")
     ap.add_argument("--png", metavar="OUT", default=None, help="write the rendered image as an RGBA PNG")
     ap.add_argument("--connectivity", type=int, choices=(6, 18, 26), default=26)
-    ap.add_argument("--largest", action="store_true", help="keep the largest connected surface")
+    gs = ap.add_mutually_exclusive_group()
+    gs.add_argument("--largest", action="store_true", help="keep the largest connected surface")
+    gs.add_argument("--surface-seed", nargs="+", type=float, default=None, metavar="X Y Z",
+                    help="keep the connected parts of the surface that hold the points nearest to these coordinates (the "
+                         "reference's Select regions of interest); not with --largest")
+    ap.add_argument("--split", metavar="DIR", default=None,
+                    help="split the final surface into its connected parts: DIR/part_%%05d.stl per part, in region order, and "
+                         "a table of triangles, volume and area in the JSON line")
+    ap.add_argument("--split-min-triangles", type=int, default=1, metavar="N",
+                    help="leave parts with fewer than N triangles out of --split's files and table (default 1)")
     ap.add_argument("--remove-nonvisible", action="store_true",
                     help="remove the faces that cannot be seen from outside (the six axis views at 800 x 800 of the reference's "
                          "Remove non-visible faces), after --largest and before --smooth / --stl")
@@ -276,6 +322,10 @@ def main(argv=None) -> int:
         ap.error("--weights / --apply-wwwl need --segment")
     if args.seed and len(args.seed) % 3:
         ap.error("--seed takes triples of x y z")
+    if args.surface_seed and len(args.surface_seed) % 3:
+        ap.error("--surface-seed takes triples of x y z")
+    if args.split_min_triangles != 1 and args.split is None:
+        ap.error("--split-min-triangles needs --split DIR")
     if args.filter is not None:
         if args.filter[0] not in FILTER_TYPES:
             ap.error("--filter NAME must be one of %s" % ", ".join(FILTER_TYPES))

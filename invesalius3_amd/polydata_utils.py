@@ -7,8 +7,13 @@ The cameras are built here, on the host, in float64 and handed to the kernels as
 same mesh resident in HBM (what ``DeviceVolume.marching_cubes_indexed(download=False)`` leaves behind): with it
 threshold -> mesh -> keep largest -> remove non-visible never leaves the device.
 
-PARITY UNPINNED: VTK and its OpenGL rasteriser are not installed; the rules of DESIGN 7f are pinned bit for bit against
-their numpy restatement (tests/_meshvis_ref.py).  vtkCleanPolyData's merge of coincident points is not done."""
+The surface connectivity tools (polydata_utils.py:206-278; csrc/k_meshparts.hip) are here as well:
+``SplitDisconectedParts``, ``JoinSeedsParts`` and ``SelectLargestPart``, on arrays or on a `DeviceMesh`; `MeshParts` is the
+split resident in HBM, every part a view into two grouped buffers.
+
+PARITY UNPINNED: VTK and its OpenGL rasteriser are not installed; the rules of DESIGN 7f / 7h are pinned bit for bit against
+their numpy restatements (tests/_meshvis_ref.py, tests/_mesh_regions_ref.py).  vtkCleanPolyData's merge of coincident points
+is not done."""
 from __future__ import annotations
 
 import ctypes
@@ -159,11 +164,169 @@ class DeviceMesh:
                 "mesh_select_points")
         return DeviceMesh(ov, nv.value, of, nt.value, self.stream, owns=True)
 
+    # ---- surface connectivity ----
+    def region_labels(self):
+        """``(tri_labels int32 (T,), n_regions)``: region r is the r-th region in the order of its first triangle"""
+        from .device import DeviceBuffer
+        lab = DeviceBuffer(self.ntris * 4 + 16)
+        nr = ctypes.c_int64(0)
+        try:
+            L.check(L.lib().ivx_dev_mesh_region_labels(ctypes.c_int64(self.nverts), self.faces.ptr, ctypes.c_int64(self.ntris), lab.ptr,
+                                                       None, ctypes.byref(nr), None, self.stream), "mesh_region_labels")
+            self.sync()
+            return lab.download((self.ntris,), np.int32), nr.value
+        finally:
+            lab.close()
+
+    def keep_largest(self) -> "DeviceMesh":
+        from .device import DeviceBuffer
+        ov, of = DeviceBuffer(self.nverts * 12 + 16), DeviceBuffer(self.ntris * 12 + 16)
+        nv, nt = ctypes.c_int64(0), ctypes.c_int64(0)
+        L.check(L.lib().ivx_dev_mesh_keep_largest(self.verts.ptr, ctypes.c_int64(self.nverts), self.faces.ptr, ctypes.c_int64(self.ntris),
+                                                  ov.ptr, ctypes.c_int64(self.nverts), of.ptr, ctypes.c_int64(self.ntris),
+                                                  ctypes.byref(nv), ctypes.byref(nt), None, self.stream), "mesh_keep_largest")
+        return DeviceMesh(ov, nv.value, of, nt.value, self.stream, owns=True)
+
+    def select_seeded(self, ids) -> "DeviceMesh":
+        """the regions that hold any of the point ids `ids` (a host sequence, or a `DeviceBuffer` of int32 with `count`)"""
+        from .device import DeviceBuffer
+        seeds = _seed_ids(ids, self.nverts)  # (raises before anything is launched)
+        sbuf = DeviceBuffer(seeds.nbytes + 16)
+        ov, of = DeviceBuffer(self.nverts * 12 + 16), DeviceBuffer(self.ntris * 12 + 16)
+        nv, nt = ctypes.c_int64(0), ctypes.c_int64(0)
+        try:
+            if len(seeds):
+                sbuf.upload(seeds)
+            L.check(L.lib().ivx_dev_mesh_select_seeded(self.verts.ptr, ctypes.c_int64(self.nverts), self.faces.ptr,
+                                                       ctypes.c_int64(self.ntris), sbuf.ptr, ctypes.c_int64(len(seeds)), ov.ptr,
+                                                       ctypes.c_int64(self.nverts), of.ptr, ctypes.c_int64(self.ntris), ctypes.byref(nv),
+                                                       ctypes.byref(nt), self.stream), "mesh_select_seeded")
+        finally:
+            sbuf.close()  # (the call waited for its counts: the seeds have been read)
+        return DeviceMesh(ov, nv.value, of, nt.value, self.stream, owns=True)
+
+    def nearest_point(self, xyz) -> int:
+        """id of the point nearest to `xyz` (float64 distances, the smallest id on a tie); -1 for a mesh without points"""
+        from .device import DeviceBuffer
+        q = (ctypes.c_double * 3)(*[float(x) for x in xyz])
+        out = DeviceBuffer(16)
+        try:
+            L.check(L.lib().ivx_dev_mesh_nearest_point(self.verts.ptr, ctypes.c_int64(self.nverts), q, out.ptr, self.stream),
+                    "mesh_nearest_point")
+            self.sync()
+            return int(out.download((1,), np.int32)[0])
+        finally:
+            out.close()
+
+    def split(self) -> "MeshParts":
+        from .device import DeviceBuffer
+        lib = L.lib()
+        nv, nr = ctypes.c_int64(0), ctypes.c_int64(0)
+        args = (self.verts.ptr, ctypes.c_int64(self.nverts), self.faces.ptr, ctypes.c_int64(self.ntris))
+        L.check(lib.ivx_dev_mesh_split(*args, None, ctypes.c_int64(0), None, ctypes.c_int64(0), None, ctypes.c_int64(0),
+                                       ctypes.byref(nv), ctypes.byref(nr), self.stream), "mesh_split")
+        ov, of, tb = DeviceBuffer(nv.value * 12 + 16), DeviceBuffer(self.ntris * 12 + 16), DeviceBuffer(nr.value * 32 + 16)
+        if nr.value:
+            L.check(lib.ivx_dev_mesh_split(*args, ov.ptr, nv, of.ptr, ctypes.c_int64(self.ntris), tb.ptr, nr, ctypes.byref(nv),
+                                           ctypes.byref(nr), self.stream), "mesh_split")
+        return MeshParts(ov, nv.value, of, self.ntris if nr.value else 0, tb, nr.value, self.stream)
+
     def close(self):
         if self._owns:
             self.verts.close()
             self.faces.close()
         self._owns = False
+
+
+def _seed_ids(ids, nverts) -> np.ndarray:
+    """the seed list as int32, checked on the host: an id outside [0, nverts) is a ValueError (VTK skips negative ids
+    and reads past its array for large ones)"""
+    a = np.asarray(list(ids) if not isinstance(ids, np.ndarray) else ids)
+    if a.size == 0:
+        return np.zeros(0, np.int32)
+    if a.dtype.kind not in "iu":
+        raise ValueError("seed point ids must be integers")
+    a = a.reshape(-1).astype(np.int64)
+    if a.min() < 0 or a.max() >= int(nverts):
+        bad = a[(a < 0) | (a >= int(nverts))][0]
+        raise ValueError("seed point id %d outside [0, %d)" % (int(bad), int(nverts)))
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+class _BufferView:
+    """A window into a `DeviceBuffer` that somebody else owns: same calls, `close` does nothing.  Only 4-byte aligned."""
+
+    def __init__(self, base, offset_bytes: int, nbytes: int):
+        self._base, self.nbytes = base, int(nbytes)
+        self.ptr = ctypes.c_void_p(base.ptr.value + int(offset_bytes))
+
+    def download(self, shape, dtype, out=None):
+        if out is None:
+            out = np.empty(shape, dtype)
+        assert out.flags["C_CONTIGUOUS"] and out.nbytes <= self.nbytes
+        if out.nbytes:
+            L.check(L.lib().ivx_memcpy_d2h(L.ptr(out), self.ptr, ctypes.c_size_t(out.nbytes)))
+        return out
+
+    def at(self, offset_bytes: int):
+        return ctypes.c_void_p(self.ptr.value + int(offset_bytes))
+
+    def close(self):
+        pass
+
+
+class MeshParts:
+    """Every connected part of a mesh, resident (``DeviceMesh.split``): all triangles grouped by region with part-local point
+    ids, the used points grouped the same way, and the part table -- `table` on the host, ``int64 (R, 4)`` = (triangle offset,
+    triangles, point offset, points)."""
+
+    def __init__(self, verts_buf, nverts, faces_buf, ntris, table_buf, n, stream=None):
+        self.verts, self.nverts, self.faces, self.ntris, self.table_buf, self.n, self.stream = (
+            verts_buf, int(nverts), faces_buf, int(ntris), table_buf, int(n), stream)
+        self._table = None
+
+    def sync(self):
+        L.check(L.lib().ivx_stream_synchronize(self.stream) if self.stream else L.lib().ivx_device_synchronize())
+
+    @property
+    def table(self) -> np.ndarray:
+        if self._table is None:
+            self.sync()
+            self._table = self.table_buf.download((self.n, 4), np.int64) if self.n else np.zeros((0, 4), np.int64)
+        return self._table
+
+    def part(self, i: int) -> DeviceMesh:
+        """part `i` as a `DeviceMesh` that looks into the grouped buffers (valid until `close`; 4-byte aligned: every mesh
+        kernel loads single floats / ints)"""
+        to, tn, vo, vn = (int(x) for x in self.table[int(i)])
+        return DeviceMesh(_BufferView(self.verts, vo * 12, vn * 12), vn, _BufferView(self.faces, to * 12, tn * 12), tn, self.stream)
+
+    def download(self, i: int):
+        return self.part(i).download()
+
+    def mass_properties(self, small_max: int = 0) -> np.ndarray:
+        """``float64 (R, 2)``: volume and area of every part (`surface_process.mass_properties` of each)"""
+        return self.mass_properties_full(small_max)[:, :2].copy()
+
+    def mass_properties_full(self, small_max: int = 0) -> np.ndarray:
+        from .device import DeviceBuffer
+        if not self.n:
+            return np.zeros((0, 8), np.float64)
+        out = DeviceBuffer(self.n * 64 + 16)
+        try:
+            L.check(L.lib().ivx_dev_mesh_parts_mass(self.verts.ptr, self.faces.ptr, self.table_buf.ptr, ctypes.c_int64(self.n),
+                                                    ctypes.c_int64(self.ntris), ctypes.c_int64(int(small_max)), out.ptr, self.stream),
+                    "mesh_parts_mass")
+            self.sync()
+            return out.download((self.n, 8), np.float64)
+        finally:
+            out.close()
+
+    def close(self):
+        for b in (self.verts, self.faces, self.table_buf):
+            if b is not None:
+                b.close()
+        self.verts = self.faces = self.table_buf = None
 
 
 def bounds(verts) -> tuple:
@@ -256,3 +419,74 @@ def HasNonVisibleFaces(verts, faces=None, threshold=0.7, positions=POSITIONS, si
     if n == 0:
         return False
     return int(np.count_nonzero(visible_points(verts, faces, positions, size))) / n < threshold
+
+
+# ---- surface connectivity (polydata_utils.py:206-278) ----
+def split_arrays(verts, faces):
+    """The split on host arrays in one piece: ``(grouped verts, grouped faces with part-local ids, table int64 (R, 4))``."""
+    v, f = _mesh(verts, faces)
+    lib = L.lib()
+    nv, nr = ctypes.c_int64(0), ctypes.c_int64(0)
+    args = (L.ptr(v), ctypes.c_int64(len(v)), L.ptr(f), ctypes.c_int64(len(f)))
+    L.check(lib.ivx_mesh_split(*args, None, None, None, ctypes.byref(nv), ctypes.byref(nr)), "mesh_split")
+    ov, of, tb = np.empty((nv.value, 3), np.float32), np.empty((len(f), 3), np.int32), np.empty((nr.value, 4), np.int64)
+    if nr.value:
+        L.check(lib.ivx_mesh_split(*args, L.ptr(ov), L.ptr(of), L.ptr(tb), ctypes.byref(nv), ctypes.byref(nr)), "mesh_split")
+    return ov, of, tb
+
+
+def parts_mass_properties(verts, faces, table) -> np.ndarray:
+    """``float64 (R, 2)`` volume and area of every part of a grouped mesh (what `split_arrays` returns)"""
+    v, f = _mesh(verts, faces)
+    tb = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, 4)
+    out = np.zeros((len(tb), 8), np.float64)
+    L.check(L.lib().ivx_mesh_parts_mass(L.ptr(v), ctypes.c_int64(len(v)), L.ptr(f), ctypes.c_int64(len(f)), L.ptr(tb),
+                                        ctypes.c_int64(len(tb)), L.ptr(out)), "mesh_parts_mass")
+    return out[:, :2].copy()
+
+
+def nearest_point(verts, xyz) -> int:
+    """id of the point nearest to `xyz` (float64 distances, the smallest id on a tie); -1 without points"""
+    if isinstance(verts, DeviceMesh):
+        return verts.nearest_point(xyz)
+    v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    q = (ctypes.c_double * 3)(*[float(x) for x in xyz])
+    out = ctypes.c_int64(-1)
+    L.check(L.lib().ivx_mesh_nearest_point(L.ptr(v), ctypes.c_int64(len(v)), q, ctypes.byref(out)), "mesh_nearest_point")
+    return int(out.value)
+
+
+def SplitDisconectedParts(verts, faces=None):
+    """``pu.SplitDisconectedParts`` (:241-278): every connected part, in region order (region r = the r-th region in the order of
+    its first triangle, the `r` of AddSpecifiedRegion).  A part keeps its triangles in their original order, on the points they
+    use in original order.  Arrays in -> a list of ``(verts, faces)``; a `DeviceMesh` in -> `MeshParts`, nothing downloaded."""
+    if isinstance(verts, DeviceMesh):
+        return verts.split()
+    ov, of, tb = split_arrays(verts, faces)
+    return [(ov[vo:vo + vn].copy(), of[to:to + tn].copy()) for to, tn, vo, vn in tb.tolist()]
+
+
+def JoinSeedsParts(verts, faces=None, point_id_list=()):
+    """``pu.JoinSeedsParts`` (:206-238): the union of the regions that hold any of the seed point ids.  Duplicate seeds are
+    harmless, a seed no triangle uses selects nothing, no seeds give an empty mesh; a seed outside ``[0, len(verts))`` is a
+    ValueError, raised before anything runs on the GPU (DEVIATION: VTK skips negative ids and reads past its array for large
+    ones).  Arrays in -> ``(verts', faces')``; a `DeviceMesh` in (``faces=None``) -> a `DeviceMesh` out."""
+    if isinstance(verts, DeviceMesh):
+        return verts.select_seeded(point_id_list)
+    v, f = _mesh(verts, faces)
+    seeds = _seed_ids(point_id_list, len(v)).astype(np.int64)
+    ov, of = np.empty_like(v), np.empty_like(f)
+    nv, nt = ctypes.c_int64(0), ctypes.c_int64(0)
+    L.check(L.lib().ivx_mesh_select_seeded(L.ptr(v), ctypes.c_int64(len(v)), L.ptr(f), ctypes.c_int64(len(f)), L.ptr(seeds),
+                                           ctypes.c_int64(len(seeds)), L.ptr(ov), L.ptr(of), ctypes.byref(nv), ctypes.byref(nt)),
+            "mesh_select_seeded")
+    return ov[: nv.value].copy(), of[: nt.value].copy()
+
+
+def SelectLargestPart(verts, faces=None):
+    """``pu.SelectLargestPart`` (:188-203): the part with the most triangles, the earliest on a tie
+    (`surface_process.keep_largest`)."""
+    if isinstance(verts, DeviceMesh):
+        return verts.keep_largest()
+    from . import surface_process as sp
+    return sp.keep_largest(verts, faces)[:2]

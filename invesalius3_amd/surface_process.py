@@ -139,6 +139,30 @@ def keep_largest(verts, faces):
     return ov[: nv.value].copy(), of[: nt.value].copy(), nr.value
 
 
+def region_labels(verts, faces):
+    """``(tri_labels int32 (T,), n_regions)`` of an indexed mesh: regions are `keep_largest`'s (triangles joined through shared
+    point ids); region r is the r-th region in ascending order of its first triangle, which is how
+    vtkPolyDataConnectivityFilter numbers them (csrc/k_meshparts.hip).  `verts` gives the number of points only."""
+    nv = len(np.asarray(verts).reshape(-1, 3))
+    f = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+    lab = np.empty(len(f), np.int32)
+    nr = ctypes.c_int64(0)
+    L.check(L.lib().ivx_mesh_region_labels(ctypes.c_int64(nv), L.ptr(f), ctypes.c_int64(len(f)), L.ptr(lab), None, ctypes.byref(nr)),
+            "mesh_region_labels")
+    return lab, nr.value
+
+
+def vertex_region_labels(verts, faces):
+    """int32 (V,): the region of every point, -1 for a point no triangle uses (see `region_labels`)"""
+    nv = len(np.asarray(verts).reshape(-1, 3))
+    f = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+    lab = np.empty(nv, np.int32)
+    nr = ctypes.c_int64(0)
+    L.check(L.lib().ivx_mesh_region_labels(ctypes.c_int64(nv), L.ptr(f), ctypes.c_int64(len(f)), None, L.ptr(lab), ctypes.byref(nr)),
+            "mesh_region_labels")
+    return lab
+
+
 def surface_piece(image, mask_matrix, roi, spacing, min_value, max_value, from_binary,
                   fill_border_holes=True) -> np.ndarray:
     """The geometry of one piece of surface_process.py:71-201 on arrays already in memory (the arguments that reach it).
