@@ -269,6 +269,15 @@ int ivx_dev_mc_count(const ivx_mc_params *p, const void *a, void *scratch, int64
 int ivx_dev_mc_count_async(const ivx_mc_params *p, const void *a, void *scratch, void *stream);
 int ivx_dev_mc_count_bits_async(const ivx_mc_params *p, const uint64_t *inside_bits, void *scratch, void *stream);
 int ivx_dev_mc_total(const ivx_mc_params *p, void *scratch, int64_t *ntris, void *stream);
+/* ivx_dev_mc_total is ordered behind everything queued on `stream`: when it returns, so have a list and an emit queued in
+ * front of it.  ivx_dev_mc_total_early gives the same number (and, for two iso-values, sets the same split) as soon as the
+ * count's own scan has run: the scan of a one-iso count publishes the total to the host itself, so this form launches nothing
+ * and does NOT wait for a list or an emit queued behind the count -- they may still be running when it returns.  The soup is
+ * then complete in stream order only: synchronise the stream (or order the reader behind it) before reading `tris` from
+ * elsewhere or freeing `tris`, `scratch` or the inside plane.  It may be called before or after the emit, and more than once.
+ * Where the scan's word cannot be used (two iso-values, or 64 other messages have gone through the library's host mailbox
+ * since the count was queued) it does what ivx_dev_mc_total does. */
+int ivx_dev_mc_total_early(const ivx_mc_params *p, void *scratch, int64_t *ntris, void *stream);
 /* same, from an inside plane (value >= iso[0]) the caller already holds; niso must be 1.  The plane is read IN PLACE by
  * this call and by the ivx_dev_mc_emit / ivx_dev_mc_indexed_* calls that follow on the same scratch: keep it unchanged
  * until they have run. */
@@ -667,6 +676,13 @@ int ivx_dev_flood_or_planes_acc(const ivx_flood_plan *p, const uint64_t *cand, u
 /* out[v] = fill where reached (uint8 out), or data[v] = fill (in-place form, dtype of data) */
 int ivx_dev_flood_apply(const ivx_flood_plan *p, const uint64_t *reached, int dtype, void *target,
                         double fill, void *stream);
+/* mask[v] = v_sel where reached, for a uint8 mask whose bytes are KNOWN to be v_in where `inside_bits` (layout of `reached`)
+ * has a bit and 0 elsewhere -- the mask and plane ivx_dev_threshold_i16_bits leaves, v_in = 255.  Same bytes afterwards as
+ * ivx_dev_flood_apply(p, reached, IVX_U8, mask, v_sel, stream), reached bits outside the inside plane included, but the mask
+ * is not read: a 16-voxel chunk with a reached bit is written from the two bit fields (v_sel where reached, else v_in where
+ * inside, else 0), a chunk without one is left alone.  dx % 64 == 0 and a 16-byte aligned mask only (IVX_EINVAL). */
+int ivx_dev_flood_apply_levels(const ivx_flood_plan *p, const uint64_t *reached, const uint64_t *inside_bits, uint8_t *mask,
+                               int v_in, int v_sel, void *stream);
 /* both writes of a GUI region-grow in one pass: out[v] = fill and mask[v] = select where reached
  * (floodfill_threshold's out + `mask[out_mask.astype(bool)] = 254`, styles.py:3200-3214) */
 int ivx_dev_flood_apply2(const ivx_flood_plan *p, const uint64_t *reached, uint8_t *out, int fill, uint8_t *mask,

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "ivx_internal.h"
+#include "mailbox_slot.h"
 #include "resident_ranges.h"
 
 namespace ivx {
@@ -861,7 +862,19 @@ int download_strided2(void *dst, const int64_t shape[2], const int64_t st[2], co
 
 // ---- mailbox ------------------------------------------------------------------------------------------------
 static uint32_t *g_mb = nullptr; // pinned host memory, 64 dwords per slot x 64 slots (ring)
-static uint32_t g_mb_seq = 0;
+static uint32_t g_mb_seq = 0;     // the newest sequence number handed out (mailbox_slot.h has the ring's arithmetic)
+
+// the next sequence number (g_mu held); the first call makes the ring
+static int mailbox_hand_out(uint32_t *seq_out) {
+    if (!g_mb) {
+        void *p = nullptr;
+        IVX_HIP(hipHostMalloc(&p, MAILBOX_SLOTS * 64 * 4, hipHostMallocMapped | hipHostMallocCoherent));
+        memset(p, 0, MAILBOX_SLOTS * 64 * 4);
+        g_mb = (uint32_t *)p;
+    }
+    *seq_out = g_mb_seq = mailbox_next_seq(g_mb_seq);
+    return IVX_OK;
+}
 
 __global__ void k_mailbox_publish(const uint32_t *__restrict__ src, int n, uint32_t *mb, uint32_t seq) {
     if (threadIdx.x || blockIdx.x) return;
@@ -873,17 +886,10 @@ __global__ void k_mailbox_publish(const uint32_t *__restrict__ src, int n, uint3
 int mailbox_publish(const void *dsrc, int ndwords, hipStream_t st, uint32_t *seq_out) {
     {
         std::lock_guard<std::mutex> lk(g_mu);
-        if (!g_mb) {
-            void *p = nullptr;
-            IVX_HIP(hipHostMalloc(&p, 64 * 64 * 4, hipHostMallocMapped | hipHostMallocCoherent));
-            memset(p, 0, 64 * 64 * 4);
-            g_mb = (uint32_t *)p;
-        }
-        *seq_out = ++g_mb_seq;
-        if (*seq_out == 0) *seq_out = ++g_mb_seq;
+        if (int rc = mailbox_hand_out(seq_out)) return rc;
     }
     IVX_REQUIRE(ndwords >= 0 && ndwords <= 32, IVX_EINVAL, "mailbox: too many words");
-    uint32_t *slot = g_mb + (size_t)(*seq_out & 63u) * 64;
+    uint32_t *slot = g_mb + (size_t)mailbox_slot_of(*seq_out) * 64;
     hipLaunchKernelGGL(k_mailbox_publish, dim3(1), dim3(64), 0, st, (const uint32_t *)dsrc, ndwords, slot, *seq_out);
     IVX_LAUNCH_CHECK();
     return IVX_OK;
@@ -893,15 +899,8 @@ int mailbox_publish(const void *dsrc, int ndwords, hipStream_t st, uint32_t *seq
 // number into dword 63 with release semantics at system scope -- what k_mailbox_publish does): saves the publishing launch
 int mailbox_reserve(uint32_t **slot_out, uint32_t *seq_out) {
     std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_mb) {
-        void *p = nullptr;
-        IVX_HIP(hipHostMalloc(&p, 64 * 64 * 4, hipHostMallocMapped | hipHostMallocCoherent));
-        memset(p, 0, 64 * 64 * 4);
-        g_mb = (uint32_t *)p;
-    }
-    *seq_out = ++g_mb_seq;
-    if (*seq_out == 0) *seq_out = ++g_mb_seq;
-    *slot_out = g_mb + (size_t)(*seq_out & 63u) * 64;
+    if (int rc = mailbox_hand_out(seq_out)) return rc;
+    *slot_out = g_mb + (size_t)mailbox_slot_of(*seq_out) * 64;
     return IVX_OK;
 }
 
@@ -927,23 +926,16 @@ __global__ void k_vote_publish(int32_t *v, uint32_t *mb, uint32_t seq) {
 int vote_publish(int32_t *votes, hipStream_t st, uint32_t *seq_out) {
     {
         std::lock_guard<std::mutex> lk(g_mu);
-        if (!g_mb) {
-            void *p = nullptr;
-            IVX_HIP(hipHostMalloc(&p, 64 * 64 * 4, hipHostMallocMapped | hipHostMallocCoherent));
-            memset(p, 0, 64 * 64 * 4);
-            g_mb = (uint32_t *)p;
-        }
-        *seq_out = ++g_mb_seq;
-        if (*seq_out == 0) *seq_out = ++g_mb_seq;
+        if (int rc = mailbox_hand_out(seq_out)) return rc;
     }
-    uint32_t *slot = g_mb + (size_t)(*seq_out & 63u) * 64;
+    uint32_t *slot = g_mb + (size_t)mailbox_slot_of(*seq_out) * 64;
     hipLaunchKernelGGL(k_vote_publish, dim3(1), dim3(64), 0, st, votes, slot, *seq_out);
     IVX_LAUNCH_CHECK();
     return IVX_OK;
 }
 
 int mailbox_wait(uint32_t seq, hipStream_t st, uint32_t *out, int ndwords) {
-    volatile uint32_t *slot = g_mb + (size_t)(seq & 63u) * 64;
+    volatile uint32_t *slot = g_mb + (size_t)mailbox_slot_of(seq) * 64;
     bool ok = false;
     for (long spins = 0; spins < 20000000L; spins++) { // ~ a few hundred ms worst case, then the safe path
         if (__atomic_load_n(&slot[63], __ATOMIC_ACQUIRE) == seq) { ok = true; break; }
@@ -956,6 +948,41 @@ int mailbox_wait(uint32_t seq, hipStream_t st, uint32_t *out, int ndwords) {
         IVX_REQUIRE(__atomic_load_n(&slot[63], __ATOMIC_ACQUIRE) == seq, IVX_EHIP, "mailbox: GPU never published sequence %u", seq);
     }
     for (int i = 0; i < ndwords; i++) out[i] = slot[i];
+    return IVX_OK;
+}
+
+// mailbox_wait for a number handed out by mailbox_reserve a while ago, whose slot may have gone to a later number since
+// (64 slots): `*got` = 0, with nothing read, when it has -- before the wait, during it, or under the read.  Launches nothing.
+int mailbox_wait_reserved(uint32_t seq, hipStream_t st, uint32_t *out, int ndwords, int *got) {
+    *got = 0;
+    auto in_slot = [seq]() {
+        std::lock_guard<std::mutex> lk(g_mu);
+        return g_mb != nullptr && mailbox_seq_in_slot(seq, g_mb_seq);
+    };
+    if (!in_slot()) return IVX_OK;
+    volatile uint32_t *slot = g_mb + (size_t)mailbox_slot_of(seq) * 64;
+    bool ok = false;
+    for (long spins = 0; spins < 20000000L; spins++) {
+        if (__atomic_load_n(&slot[63], __ATOMIC_ACQUIRE) == seq) { ok = true; break; }
+        if ((spins & 4095) == 4095 && !in_slot()) return IVX_OK; // (another thread's messages went round the ring meanwhile)
+#if defined(__x86_64__)
+        __builtin_ia32_pause();
+#endif
+    }
+    if (!ok) {
+        IVX_HIP(hipStreamSynchronize(st));
+        if (__atomic_load_n(&slot[63], __ATOMIC_ACQUIRE) != seq) {
+            IVX_REQUIRE(!in_slot(), IVX_EHIP, "mailbox: GPU never published sequence %u", seq);
+            return IVX_OK;
+        }
+    }
+    uint32_t w[32];
+    for (int i = 0; i < ndwords; i++) w[i] = slot[i];
+    // the words are `seq`'s only if the slot's next owner was not even handed out when they had been read
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    if (slot[63] != seq || !in_slot()) return IVX_OK;
+    for (int i = 0; i < ndwords; i++) out[i] = w[i];
+    *got = 1;
     return IVX_OK;
 }
 

@@ -1259,6 +1259,37 @@ __global__ __launch_bounds__(256) void k_flood_apply16(const uint16_t *__restric
     }
 }
 
+// k_flood_apply16 for a mask whose bytes are KNOWN: v_in where `inside` (same layout as `reached`) has a bit, 0 elsewhere.  Every
+// byte of a chunk with a reached bit is then a function of the two bit fields -- v_sel where reached, else v_in where inside,
+// else 0 -- so the lane loads both fields together and stores; no byte of `out` is read (k_flood_apply16 loads a partial
+// chunk's 16 bytes after its bits have arrived: a second, dependent round trip).  Chunks without a reached bit are not written.
+__global__ __launch_bounds__(256) void k_flood_apply_levels16(const uint16_t *__restrict__ reached, const uint16_t *__restrict__ inside,
+                                                              int64_t nchunks, uint4 *__restrict__ out, uint8_t v_in, uint8_t v_sel) {
+    const int64_t stride = (int64_t)gridDim.x * 1024;
+    const unsigned int in4 = 0x01010101u * v_in, sel4 = 0x01010101u * v_sel;
+    for (int64_t i0 = (int64_t)blockIdx.x * 1024 + threadIdx.x; i0 < nchunks; i0 += stride) {
+        unsigned int m[4], b[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int64_t i = i0 + u * 256;
+            m[u] = i < nchunks ? reached[i] : 0u;
+            b[u] = i < nchunks ? inside[i] : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            if (!m[u]) continue;
+            // bit e of four -> 0xff in byte e (the products' bits e + 7 k are all different: no carries)
+            auto bytes = [](unsigned int bits4) { return ((bits4 * 0x00204081u) & 0x01010101u) * 0xffu; };
+            auto word = [&](unsigned int r4, unsigned int i4) {
+                const unsigned int rs = bytes(r4);
+                return (sel4 & rs) | (in4 & bytes(i4) & ~rs);
+            };
+            out[i0 + u * 256] = make_uint4(word(m[u] & 15u, b[u] & 15u), word(m[u] >> 4 & 15u, b[u] >> 4 & 15u),
+                                           word(m[u] >> 8 & 15u, b[u] >> 8 & 15u), word(m[u] >> 12 & 15u, b[u] >> 12 & 15u));
+        }
+    }
+}
+
 // out[v] = fill AND mask[v] = select where reached: floodfill_threshold's `out` plus the caller's
 // `mask[out_mask.astype(bool)] = 254` (styles.py:3214) in one pass over the reached bits
 __global__ __launch_bounds__(256) void k_flood_apply2(Tiles t, const uint8_t *__restrict__ reached, uint8_t *__restrict__ out,
@@ -2054,6 +2085,26 @@ extern "C" int ivx_dev_flood_apply(const ivx_flood_plan *p, const uint64_t *reac
     case IVX_F64: hipLaunchKernelGGL(k_flood_apply<double>, dim3(g), dim3(256), 0, st, t, r, (double *)target, fill); break;
     default: ivx::set_error("flood: unsupported dtype %d", dtype); return IVX_EINVAL;
     }
+    IVX_LAUNCH_CHECK();
+    return IVX_OK;
+}
+
+// mask[reached] = v_sel for a uint8 mask that is known to be v_in inside the plane `inside_bits` and 0 outside it (a fused
+// threshold's mask and plane): the same bytes as ivx_dev_flood_apply(..., IVX_U8, mask, v_sel, ...) without reading the mask
+extern "C" int ivx_dev_flood_apply_levels(const ivx_flood_plan *p, const uint64_t *reached, const uint64_t *inside_bits, uint8_t *mask,
+                                          int v_in, int v_sel, void *stream) {
+    Tiles t;
+    int rc = make_tiles(p, &t);
+    if (rc) return rc;
+    IVX_REQUIRE(reached && inside_bits && mask, IVX_EINVAL, "flood_apply_levels: null plane or mask");
+    IVX_REQUIRE(t.dx % 64 == 0 && ((uintptr_t)mask & 15) == 0, IVX_EINVAL,
+                "flood_apply_levels: rows of whole 64-voxel words and a 16-byte aligned mask only");
+    IVX_REQUIRE(v_in >= 0 && v_in <= 255 && v_sel >= 0 && v_sel <= 255, IVX_EINVAL, "flood_apply_levels: levels are bytes");
+    const int64_t nchunks = t.dz * t.dy * t.dx / 16;
+    if (!nchunks) return IVX_OK;
+    const int64_t blocks = ivx::cdiv(nchunks, 1024);
+    hipLaunchKernelGGL(k_flood_apply_levels16, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, ivx::S(stream),
+                       (const uint16_t *)reached, (const uint16_t *)inside_bits, nchunks, (uint4 *)mask, (uint8_t)v_in, (uint8_t)v_sel);
     IVX_LAUNCH_CHECK();
     return IVX_OK;
 }

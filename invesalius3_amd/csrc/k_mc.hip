@@ -328,8 +328,10 @@ __global__ __launch_bounds__(256) void k_mc_count(const uint64_t *__restrict__ b
 // ---- 3. scan of workgroup sums (single workgroup of 1024) ---------------------------------------------
 // (Tried in round 3: the scan in k_mc_count's tail, done by the last workgroup to sign a ticket -- one launch less, but the
 // 9 259 same-address agent-scope atomics of the ticket serialise at ~8 ns each: mc_count 44 -> 124 us.  Dropped.)
+// `mb` (or nullptr): a mailbox slot of the host's; the lane that stores the total also publishes it there under `seq`, the way
+// k_mailbox_publish would in a launch of its own behind everything queued since (ivx_runtime.hip).
 __global__ __launch_bounds__(1024) void k_mc_scan(const uint32_t *__restrict__ bsum, size_t n,
-                                                  uint64_t *__restrict__ boff) {
+                                                  uint64_t *__restrict__ boff, uint32_t *mb, uint32_t seq) {
     // One workgroup per 16 384 sums (one at 512^3, five at 1024^3 -- where the single workgroup of rounds 1 - 5 took 68 us, 5 % of
     // the stage).  No hand-over between workgroups: each first adds up everything in front of its chunk itself (a coalesced
     // read of at most a few hundred KB out of the L2) and then scans its own chunk.
@@ -402,7 +404,16 @@ __global__ __launch_bounds__(1024) void k_mc_scan(const uint32_t *__restrict__ b
         uint64_t c = 0;
         for (int q = 0; q < 16; q++) c += s_wave[q];
         if (lane == 0) s_carry = c;
-        if (lane == 63 && base + 1024 * 4 * RND >= n) boff[n] = c + e; // the last chunk leaves the total behind the offsets
+        if (lane == 63 && base + 1024 * 4 * RND >= n) { // the last chunk leaves the total behind the offsets
+            const uint64_t total = c + e;
+            boff[n] = total;
+            if (mb) {
+                mb[0] = (uint32_t)total;
+                mb[1] = (uint32_t)(total >> 32);
+                __threadfence_system();
+                __hip_atomic_store(&mb[63], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
     }
     __syncthreads();
     const uint64_t carry = s_carry;
@@ -811,6 +822,24 @@ static int mc_read_total(const ivx_mc_params *p, const Scratch &s, void *scratch
     return IVX_OK;
 }
 
+// The total as soon as the scan has published it: no launch, and no waiting for what was queued behind the scan.  Falls back
+// to mc_read_total when the scan does not publish (two iso-values: the split is wanted as well), when no slot was reserved,
+// and when the slot has meanwhile gone to a later message.
+static int mc_read_total_early(const ivx_mc_params *p, const Scratch &s, void *scratch_, int64_t *ntris, hipStream_t st) {
+    const uint32_t seq = p->niso == 1 ? mc_pieces().total_seq(scratch_) : 0u;
+    if (seq) {
+        uint32_t tw[2];
+        int got = 0;
+        const int rc = ivx::mailbox_wait_reserved(seq, st, tw, 2, &got);
+        if (rc) return rc;
+        if (got) {
+            *ntris = (int64_t)(((uint64_t)tw[1] << 32) | tw[0]);
+            return IVX_OK;
+        }
+    }
+    return mc_read_total(p, s, scratch_, ntris, st);
+}
+
 // A count: [the inside planes of the voxels `a` into the scratch, unless the caller hands in the plane of its one iso-value,]
 // classify + count + scan (queued, nothing comes back to the host), and -- when `ntris` is wanted -- the total
 static int mc_count_impl(const ivx_mc_params *p, const void *a, const uint64_t *inside_bits, void *scratch_, int64_t *ntris,
@@ -838,9 +867,15 @@ static int mc_count_impl(const ivx_mc_params *p, const void *a, const uint64_t *
         IVX_LAUNCH_CHECK();
     }
     const size_t nb = s.nblocks * (size_t)p->niso;
-    hipLaunchKernelGGL(k_mc_scan, dim3((unsigned)std::max<size_t>(1, (nb + 16383) / 16384)), dim3(1024), 0, st, bsum, nb, boff);
+    uint32_t *mb = nullptr, seq = 0;
+    if (p->niso == 1) { // the scan publishes the total itself (ivx_dev_mc_total_early; two iso-values need the split too)
+        if ((rc = ivx::mailbox_reserve(&mb, &seq))) return rc;
+        mc_pieces().set_total_seq(scratch_, seq);
+    }
+    hipLaunchKernelGGL(k_mc_scan, dim3((unsigned)std::max<size_t>(1, (nb + 16383) / 16384)), dim3(1024), 0, st, bsum, nb, boff, mb,
+                       seq);
     IVX_LAUNCH_CHECK();
-    return ntris ? mc_read_total(p, s, scratch_, ntris, st) : IVX_OK;
+    return ntris ? mc_read_total_early(p, s, scratch_, ntris, st) : IVX_OK;
 }
 
 extern "C" int ivx_dev_mc_count(const ivx_mc_params *p, const void *a, void *scratch_, int64_t *ntris, void *stream) {
@@ -859,6 +894,17 @@ extern "C" int ivx_dev_mc_total(const ivx_mc_params *p, void *scratch_, int64_t 
     if (rc) return rc;
     *ntris = 0;
     return empty ? IVX_OK : mc_read_total(p, s, scratch_, ntris, S(stream));
+}
+// The total of the piece last counted into the scratch, as soon as its scan has run: nothing is launched, and list or emit
+// passes queued behind the count may still be running when this returns (include/ivx.h).
+extern "C" int ivx_dev_mc_total_early(const ivx_mc_params *p, void *scratch_, int64_t *ntris, void *stream) {
+    Geom g;
+    Scratch s;
+    bool empty;
+    int rc = mc_piece_layout(p, &g, &s, &empty);
+    if (rc) return rc;
+    *ntris = 0;
+    return empty ? IVX_OK : mc_read_total_early(p, s, scratch_, ntris, S(stream));
 }
 
 // Same, with the inside plane (value >= iso[0], source coordinates, the layout of the region-growing planes) handed in

@@ -14,6 +14,9 @@
 //   * the split (number of iso-0 triangles of a two-iso piece) is set when the total is read: ivx_dev_mc_total, and the
 //     counts that return the total themselves.
 //   * the vertex split (number of iso-0 vertices) is set by ivx_dev_mc_indexed_count*.
+//   * the pending total: the scan of a one-iso count publishes the total through a mailbox slot reserved for it; the record
+//     keeps the slot's sequence number (0: none) for ivx_dev_mc_total_early and the counts that return the total.  The next
+//     count on the scratch clears it with the rest; the slot itself is recycled by the ring, which the reader checks.
 //   * the triangle list: ivx_dev_mc_list fills a list buffer -- a per-stream workspace that every piece on that stream shares
 //     -- ahead of the emit.  The list is "ready" for a later pass when it is the same buffer that was filled for this scratch,
 //     with room for at least what is asked now, and the buffer still belongs to this scratch.  A negative answer means the
@@ -34,6 +37,7 @@ struct McPiece {
     uint32_t vsplit = 0;                // number of iso-0 vertices
     const void *list = nullptr;         // list buffer filled ahead of the emit, with room for list_cap triangles
     int64_t list_cap = 0;
+    uint32_t total_seq = 0;             // mailbox number under which this count's scan publishes the total itself, or 0
 };
 
 class McPieces {
@@ -43,6 +47,16 @@ class McPieces {
         McPiece &r = by_scratch_[scratch];
         r = McPiece();
         r.ext_bits = ext_bits;
+    }
+    void set_total_seq(const void *scratch, uint32_t seq) {
+        std::lock_guard<std::mutex> lk(mu_);
+        by_scratch_[scratch].total_seq = seq;
+    }
+    // the pending mailbox number of the piece counted into `scratch`, or 0
+    uint32_t total_seq(const void *scratch) {
+        std::lock_guard<std::mutex> lk(mu_);
+        auto it = by_scratch_.find(scratch);
+        return it == by_scratch_.end() ? 0u : it->second.total_seq;
     }
     void set_split(const void *scratch, uint64_t split) {
         std::lock_guard<std::mutex> lk(mu_);

@@ -232,6 +232,7 @@ class DeviceVolume:
         self._mbits_version = 0   # bumped whenever the inside plane is rewritten
         self._out_pending = None      # fill value of a deferred `out_mask[reached] = fill` (self.reached still holds it)
         self._fuse = os.environ.get("IVX_NO_FUSE", "") == ""
+        self._apply_levels = os.environ.get("IVX_APPLY_LEVELS", "1") != "0"  # (A/B: mask[reached] = v from the bit planes alone)
         self.image = TrackedBuffer(self.n * 2, self._image_touched)
         self.mask = TrackedBuffer(self.n, self._mask_touched)       # dense interior of mask.matrix[1:,1:,1:]
         self.out_mask = TrackedBuffer(self.n, self._out_touched)    # region-growing `out` (styles.py:3190)
@@ -442,7 +443,11 @@ class DeviceVolume:
         defer = self._out_logically_zero() and int(fill) != 0
         if defer:
             self._out_pending = int(fill)  # bytes stay zero; self.reached carries the result until it is needed
-            if select_value is not None:
+            if select_value is not None and self._mask_levels == (255, None) and self._mbits_valid and self._apply_levels:
+                # mask == 255 * plane, byte for byte: a touched chunk's bytes follow from the two bit planes, no byte is read
+                L.check(lib.ivx_dev_flood_apply_levels(p, self.reached.ptr, self._mbits.ptr, self.mask.raw, 255, int(select_value), st),
+                        "flood_apply_levels")
+            elif select_value is not None:
                 L.check(lib.ivx_dev_flood_apply(p, self.reached.ptr, L.U8, self.mask.raw, ctypes.c_double(int(select_value)), st))
         elif select_value is not None:
             L.check(lib.ivx_dev_flood_apply2(p, self.reached.ptr, self.out_mask.raw, int(fill), self.mask.raw,
@@ -544,6 +549,7 @@ class DeviceVolume:
         if self._mc_scratch is None or self._mc_scratch.nbytes < nb.value:
             self._join_prefetch()
             if self._mc_scratch is not None:
+                self.sync()  # (marching_cubes returns with the emit still queued: it reads the block about to be freed)
                 self._mc_scratch.close()
             self._mc_scratch = DeviceBuffer(nb.value)
         isz = 1 if p.dtype == L.U8 else 2
@@ -644,7 +650,10 @@ class DeviceVolume:
                        params: L.McParams | None = None, z0: int = 0, out: np.ndarray | None = None):
         """count + emit on the resident mask (from_binary, iso 127) or image (two iso-values).  Returns the triangle
         count, or the (T,3,3) float32 soup when download=True (written into `out` -- e.g. a `_lib.pinned_empty` array with
-        room for it -- when given)."""
+        room for it -- when given).
+        With download=False the count may come back while the triangle list and the emit are still queued or running: the
+        soup in `self._tris` is complete in stream order.  Whatever is queued on `self.stream` afterwards (the next threshold,
+        another surface) is ordered behind it by the stream; call sync() before reading the buffer from anywhere else."""
         lib = L.lib()
         if params is not None:
             p = params
@@ -688,9 +697,12 @@ class DeviceVolume:
                     L.check(lib.ivx_dev_mc_count_async(ctypes.byref(p), src, self._mc_scratch.ptr, self.stream), "mc_count")
             with self.timer.span("mc_emit"):
                 self._emit(p, src, plane, z0, cap, self.stream)
-            L.check(lib.ivx_dev_mc_total(ctypes.byref(p), self._mc_scratch.ptr, ctypes.byref(n), self.stream), "mc_total")
+            # the scan published the count itself: it is here long before the emit ends, and the next call's kernels can be
+            # queued behind an emit that is still running
+            L.check(lib.ivx_dev_mc_total_early(ctypes.byref(p), self._mc_scratch.ptr, ctypes.byref(n), self.stream), "mc_total")
             nt = n.value
             if nt > cap:  # the surface outgrew the buffer: emit again into a larger one
+                self.sync()  # (the first emit may still be writing the buffer that is about to be freed)
                 self._tris.close()
                 self._tris = DeviceBuffer(int(nt * 36 * 1.25) + 4096)
                 self._emit(p, src, plane, z0, nt, self.stream)
