@@ -865,6 +865,8 @@ int ivx_dev_flood_apply_where(uint8_t *dst, const uint8_t *src, int64_t n, int v
  *            nearest / trilinear / tricubic / Lanczos-4 with single wrap-around  invesalius_rs/src/interpolation.rs
  * m is row-major; orientation 0/1/2 = AXIAL/CORONAL/SAGITAL adds n to z/y/x of the output index; minterpol
  * 0 nearest, 1 trilinear, 2 tricubic, else Lanczos; out has the volume's dtype.  A NumCast failure -> IVX_EDOM.
+ * Lanczos on a volume with an axis of length 2: every voxel that falls inside is set to cval without a read and
+ * raises IVX_EDOM on the same status word (the reference's tap -3 wraps to -1 and panics on the index).
  * ---------------------------------------------------------------------------------------------- */
 int ivx_dev_apply_view_matrix_transform(int dtype, const void *vol, int64_t dz, int64_t dy, int64_t dx,
                                         const double spacing[3], const double m[16], int64_t n, int orientation,

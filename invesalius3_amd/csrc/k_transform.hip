@@ -124,7 +124,10 @@ __device__ double lanczos(const T *__restrict__ v, const TGeom &g, double x, dou
     return lz;
 }
 
-template <typename T>
+// PANIC: Lanczos on a volume with an axis of length 2.  Lanczos-4 taps floor(x)-3 .. floor(x)+3 and get_value wraps once, so
+// on such an axis the tap -3 lands on -1, which the reference indexes as usize (interpolation.rs:34): every voxel that falls
+// inside is the reference's panic.  That instance reads nothing: cval and IVX_EDOM for the inside voxels, cval for the rest.
+template <typename T, bool PANIC>
 __global__ __launch_bounds__(256) void k_view_transform(const T *__restrict__ vol, TGeom g, T *__restrict__ out,
                                                         int *__restrict__ status) {
     const int64_t total = g.oz * g.oy * g.ox;
@@ -143,7 +146,8 @@ __global__ __launch_bounds__(256) void k_view_transform(const T *__restrict__ vo
         const double nz = (nc[0] / nc[3]) / g.sz, ny = (nc[1] / nc[3]) / g.sy, nx = (nc[2] / nc[3]) / g.sx;
         double v = g.cval;
         if (nz >= 0.0 && nz < dz - 1.0 && ny >= 0.0 && ny < dy - 1.0 && nx >= 0.0 && nx < dx - 1.0) {
-            if (g.minterpol == 0) v = (double)vol[((int64_t)nz * g.dy + (int64_t)ny) * g.dx + (int64_t)nx];
+            if (PANIC) atomicMin(status, IVX_EDOM); // v stays cval
+            else if (g.minterpol == 0) v = (double)vol[((int64_t)nz * g.dy + (int64_t)ny) * g.dx + (int64_t)nx];
             else {
                 const double f = g.minterpol == 1 ? trilinear(vol, g, nx, ny, nz)
                                  : g.minterpol == 2 ? tricubic(vol, g, nx, ny, nz) : lanczos(vol, g, nx, ny, nz);
@@ -162,7 +166,10 @@ static int launch(const void *vol, const TGeom &g, void *out, int *status, hipSt
     const int64_t total = g.oz * g.oy * g.ox;
     if (!total) return IVX_OK;
     const int64_t b = ivx::cdiv(total, 256);
-    hipLaunchKernelGGL(k_view_transform<T>, dim3((unsigned)(b < 65536 ? b : 65536)), dim3(256), 0, st, (const T *)vol, g, (T *)out, status);
+    const dim3 grid((unsigned)(b < 65536 ? b : 65536));
+    const bool lanczos_mode = g.minterpol < 0 || g.minterpol > 2, short_axis = g.dz == 2 || g.dy == 2 || g.dx == 2;
+    if (lanczos_mode && short_axis) hipLaunchKernelGGL((k_view_transform<T, true>), grid, dim3(256), 0, st, (const T *)vol, g, (T *)out, status);
+    else hipLaunchKernelGGL((k_view_transform<T, false>), grid, dim3(256), 0, st, (const T *)vol, g, (T *)out, status);
     IVX_LAUNCH_CHECK();
     return IVX_OK;
 }
@@ -214,6 +221,7 @@ extern "C" int ivx_apply_view_matrix_transform(int dtype, const void *vol, const
     if ((rc = download_strided(out, oshape, ostrides, d_o, isz, WS_OUT))) return rc;
     int stt = 0;
     IVX_HIP(hipMemcpy(&stt, d_s, 4, hipMemcpyDeviceToHost));
-    IVX_REQUIRE(stt == 0, IVX_EDOM, "NumCast failure: an interpolated value does not fit the volume dtype (the reference panics)");
+    IVX_REQUIRE(stt == 0, IVX_EDOM, "NumCast failure: an interpolated value does not fit the volume dtype, or a Lanczos tap left an axis of "
+                                    "length 2 (the reference panics)");
     return IVX_OK;
 }

@@ -212,7 +212,9 @@ _ORIENTATION = {"AXIAL": 0, "CORONAL": 1, "SAGITAL": 2}
 def apply_view_matrix_transform(volume, spacing, m, n, orientation, minterpol, cval, out):
     """apply_view_matrix_transform (invesalius_rs/src/transforms_py.rs:95-147 -> transforms.rs:9-55): resample `volume`
     through the 4x4 matrix `m` into `out` (same dtype: int16 / uint8 / float64).  `m` must be a C-contiguous float64
-    4x4 (the reference calls ``m.as_slice().unwrap()``); `cval` must fit the dtype (``cval.extract::<T>()``)."""
+    4x4 (the reference calls ``m.as_slice().unwrap()``); `cval` must fit the dtype (``cval.extract::<T>()``) and `n` a usize.
+    Where the reference panics -- a NumCast failure, or a Lanczos sample inside a volume with an axis of length 2, whose tap -3
+    wraps once to the index -1 -- the voxel is set to `cval` and the call raises ValueError after `out` is written."""
     if volume.ndim != 3 or out.ndim != 3 or volume.dtype != out.dtype:
         raise TypeError("Invalid volume or output type")
     code = L.dtype_code(volume, (L.U8, L.I16, L.F64))
@@ -223,6 +225,8 @@ def apply_view_matrix_transform(volume, spacing, m, n, orientation, minterpol, c
     if sp.shape != (3,):
         raise TypeError("spacing must have 3 entries")
     cval = _fits(cval, volume.dtype, "cval")
+    if int(n) < 0:
+        raise OverflowError("n=%r must fit a usize" % (n,))  # transforms_py.rs:100 `n: usize`
     L.check(L.lib().ivx_apply_view_matrix_transform(
         code, L.ptr(volume), L.i64(volume.shape), L.i64(volume.strides), L.ptr(sp), L.ptr(mm), ctypes.c_int64(int(n)),
         _ORIENTATION.get(orientation, -1), int(minterpol), ctypes.c_double(cval), L.ptr(out), L.i64(out.shape),

@@ -522,7 +522,8 @@ int64_t orc_marching_cubes(int dt, const void *a, const int64_t shape[3], const 
  * column by column, i.e. ((m0*c0 + m1*c1) + m2*c2) + m3*c3 per component.
  * orientation: 0 AXIAL (z = n + cz), 1 CORONAL (y = n + cy), 2 SAGITAL (x = n + cx),
  * anything else: no offset.  A NumCast failure (tricubic / Lanczos overshoot
- * outside T) returns ORC_EDOM (the reference panics).
+ * outside T) returns ORC_EDOM (the reference panics).  So does a Lanczos
+ * sample inside a volume with an axis of length 2 (index panic), unread.
  * ---------------------------------------------------------------------- */
 typedef struct { int dt; const char *v; int64_t dz, dy, dx; const int64_t *s; } tvol_t;
 static inline double tv_get(const tvol_t *t, int64_t x, int64_t y, int64_t z) { /* interpolation.rs:6-35 */
@@ -609,6 +610,8 @@ int orc_apply_view_matrix_transform(int dt, const void *vol, const int64_t shape
         double v = cval;
         if (nz >= 0.0 && nz < dz - 1.0 && ny >= 0.0 && ny < dy - 1.0 && nx >= 0.0 && nx < dx - 1.0) {
             if (minterpol == 0) v = ld(dt, AT(t.v, s, (int64_t)nz, (int64_t)ny, (int64_t)nx));
+            else if ((minterpol < 0 || minterpol > 2) && (shape[0] == 2 || shape[1] == 2 || shape[2] == 2))
+                rc = ORC_EDOM; /* Lanczos tap floor-3 = -3 wraps once to -1: `-1 as usize` index panic (interpolation.rs:34); v stays cval */
             else {
                 const double f = minterpol == 1 ? tv_trilinear(&t, nx, ny, nz) : minterpol == 2 ? tv_tricubic(&t, nx, ny, nz) : tv_lanczos(&t, nx, ny, nz);
                 if (numcast_f64(dt, f, &v)) { rc = ORC_EDOM; v = cval; }
