@@ -160,6 +160,23 @@ int ivx_dev_threshold_i16(const int16_t *img, int64_t dz, int64_t dy, int64_t dx
  * aligned buffers (IVX_EINVAL otherwise: use ivx_dev_threshold_i16).  bits: dz*dy*(dx/64) words. */
 int ivx_dev_threshold_i16_bits(const int16_t *img, int64_t dz, int64_t dy, int64_t dx, int lo, int hi, uint8_t *mask,
                                uint64_t *bits, void *stream);
+/* Per-word (min, max) records of an int16 image: one uint32 per plane word (64 x-voxels, index (z*dy + y)*(dx/64) + x/64 like
+ * the bit planes), min as int16 in the low half, max as int16 in the high half.  A word wholly inside or wholly outside
+ * [lo, hi] is thresholded from its record alone.  Only for dx % 64 == 0 (IVX_EINVAL otherwise).
+ *   ivx_image_ranges_bytes: size of the record buffer.
+ *   ivx_dev_image_ranges_i16: build the records in one pass over the image.
+ *   ivx_dev_threshold_i16_bits_ranges: ivx_dev_threshold_i16_bits with the records;
+ *     mode IVX_RANGES_BUILD writes them as a by-product of the pass (the first threshold after the image's bytes changed),
+ *     mode IVX_RANGES_USE reads them and loads voxels of mixed words only (every later threshold of the same image).
+ *   Mask and plane are byte for byte those of ivx_dev_threshold_i16_bits in both modes, for every lo / hi -- PROVIDED the
+ *   records describe the image: use mode trusts them and does not look at a word they decide.  Whoever writes the image
+ *   must rebuild (or build-mode again) before the next use-mode call. */
+#define IVX_RANGES_BUILD 0
+#define IVX_RANGES_USE 1
+int ivx_image_ranges_bytes(int64_t dz, int64_t dy, int64_t dx, size_t *nbytes);
+int ivx_dev_image_ranges_i16(const int16_t *img, int64_t dz, int64_t dy, int64_t dx, uint32_t *ranges, void *stream);
+int ivx_dev_threshold_i16_bits_ranges(const int16_t *img, int64_t dz, int64_t dy, int64_t dx, int lo, int hi,
+                                      uint8_t *mask, uint64_t *bits, uint32_t *ranges, int mode, void *stream);
 /* Host form.  `mask` points at the FULL (dz+1,dy+1,dx+1) matrix of invesalius/data/mask.py:422-431
  * (flag cells in the index-0 planes); strides in bytes.  With honour_flags the per-slice flag
  * mask[n,0,0] is tested and then set to 1 (slice_.py:1761-1767); without it every slice is
@@ -601,6 +618,12 @@ int ivx_dev_flood_clear(const ivx_flood_plan *p, uint64_t *reached, void *scratc
  * blocks (out-of-place form, floodfill.rs:154), 2: data[v] == fill blocks (in-place form, floodfill.rs:225) */
 int ivx_dev_flood_candidates(const ivx_flood_plan *p, int dtype, const void *data, double t0, double t1,
                              const uint8_t *barrier, int barrier_mode, double fill, uint64_t *cand, void *stream);
+/* The same plane for int16 data whose (min, max) records are valid (ivx_dev_image_ranges_i16; dx % 64 == 0 and 16-byte
+ * aligned buffers, IVX_EINVAL otherwise): a word wholly outside [t0, t1] is written as 0 without a load, a word wholly
+ * inside skips the image (and with barrier_mode 0 the barrier too).  barrier_mode 0 or 1.  The records are trusted. */
+int ivx_dev_flood_candidates_ranges(const ivx_flood_plan *p, const int16_t *data, double t0, double t1,
+                                    const uint8_t *barrier, int barrier_mode, double fill, const uint32_t *ranges,
+                                    uint64_t *cand, void *stream);
 /* reached := seeds (x,y,z triples on the HOST) that are in [t0,t1]; such seeds are also forced into cand
  * (a pre-filled seed still expands, floodfill.rs:121-128).  Out-of-bounds seed -> IVX_ERANGE. */
 int ivx_dev_flood_seed(const ivx_flood_plan *p, int dtype, const void *data, double t0, double t1,

@@ -63,7 +63,14 @@ def _declare(lib):
     for name, args in (("ivx_host_register", [c_vp, sz, u64p]), ("ivx_host_touch", [u64]), ("ivx_host_touch_range", [u64, sz, sz]),
                        ("ivx_host_release", [u64]), ("ivx_host_stats", [u64, u64p]), ("ivx_host_count", [u64p]),
                        ("ivx_host_set_check", [ctypes.c_int]), ("ivx_transfer_stats", [u64p]),
-                       ("ivx_upload_strided", [c_vp, c_vp, i64p, i64p, sz]), ("ivx_download_strided", [c_vp, i64p, i64p, c_vp, sz])):
+                       ("ivx_upload_strided", [c_vp, c_vp, i64p, i64p, sz]), ("ivx_download_strided", [c_vp, i64p, i64p, c_vp, sz]),
+                       # the per-word (min, max) records of an int16 image and the kernels that read them
+                       ("ivx_image_ranges_bytes", [c_i64, c_i64, c_i64, ctypes.POINTER(sz)]),
+                       ("ivx_dev_image_ranges_i16", [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
+                       ("ivx_dev_threshold_i16_bits_ranges", [c_vp, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp,
+                                                              ctypes.c_int, c_vp]),
+                       ("ivx_dev_flood_candidates_ranges", [ctypes.POINTER(FloodPlan), c_vp, ctypes.c_double, ctypes.c_double, c_vp,
+                                                            ctypes.c_int, ctypes.c_double, c_vp, c_vp, c_vp])):
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = args, ctypes.c_int
 

@@ -89,6 +89,55 @@ __global__ __launch_bounds__(256) void k_flood_candidates16(const short8_t *__re
     }
 }
 
+// int16 data with valid per-word (min, max) records (k_threshold.hip): lane = 16 voxels as above, every lane reads its word's
+// record first.  Wholly outside [lo, hi]: 0, nothing loaded.  Wholly inside: the image is skipped (BAR 0: 0xffff, BAR 1:
+// the barrier alone decides).  Mixed: the arithmetic above.  The next trip's record is requested before this trip's store.
+template <int BAR>
+__global__ __launch_bounds__(256) void k_flood_candidates16_ranges(const short8_t *__restrict__ data,
+                                                                   const uint4 *__restrict__ bar,
+                                                                   const unsigned *__restrict__ ranges, int64_t nchunks,
+                                                                   double t0, double t1, double fill,
+                                                                   uint16_t *__restrict__ cand) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int lo = (int)ceil(t0 < -70000.0 ? -70000.0 : t0), hi = (int)floor(t1 > 70000.0 ? 70000.0 : t1); // integer data
+    const unsigned fb = (unsigned)(uint8_t)fill;
+    int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= nchunks) return;
+    unsigned rec = ranges[c >> 2];
+    for (;;) {
+        const int64_t cn = c + stride;
+        unsigned rec_next = 0;
+        if (cn < nchunks) rec_next = ranges[cn >> 2];
+        const int mn = (int)(short)(rec & 0xffffu), mx = (int)(short)(rec >> 16);
+        unsigned m = 0;
+        if (!(mx < lo || mn > hi)) {
+            const bool inside = mn >= lo && mx <= hi;
+            if (inside) {
+                m = 0xffffu;
+            } else {
+                const short8_t a = __builtin_nontemporal_load(&data[2 * c]);
+                const short8_t b = __builtin_nontemporal_load(&data[2 * c + 1]);
+#pragma unroll
+                for (int e = 0; e < 16; e++) {
+                    const int v = (int)(e < 8 ? a[e & 7] : b[e & 7]);
+                    m |= (v >= lo && v <= hi) ? (1u << e) : 0u;
+                }
+            }
+            if (BAR == 1 && m) {
+                const uint4 q = bar[c];
+                const unsigned bw[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+                for (int e = 0; e < 16; e++)
+                    if (((bw[e >> 2] >> (8 * (e & 3))) & 0xffu) == fb) m &= ~(1u << e);
+            }
+        }
+        cand[c] = (uint16_t)m;
+        if (cn >= nchunks) break;
+        c = cn;
+        rec = rec_next;
+    }
+}
+
 template <typename T, int BAR>
 __global__ __launch_bounds__(256) void k_flood_candidates(const T *__restrict__ data, const uint8_t *__restrict__ bar,
                                                           Tiles t, double t0, double t1, double fill,
@@ -1416,6 +1465,33 @@ extern "C" int ivx_dev_flood_candidates(const ivx_flood_plan *p, int dtype, cons
     }
     ivx::set_error("flood: unsupported dtype %d", dtype);
     return IVX_EINVAL;
+}
+
+extern "C" int ivx_dev_flood_candidates_ranges(const ivx_flood_plan *p, const int16_t *data, double t0, double t1,
+                                               const uint8_t *barrier, int barrier_mode, double fill,
+                                               const uint32_t *ranges, uint64_t *cand, void *stream) {
+    Tiles t;
+    int rc = make_tiles(p, &t);
+    if (rc) return rc;
+    IVX_REQUIRE(barrier_mode == 0 || barrier_mode == 1, IVX_EINVAL, "flood: candidates_ranges: barrier_mode 0 or 1");
+    IVX_REQUIRE(barrier_mode != 1 || barrier, IVX_EINVAL, "flood: barrier array missing");
+    IVX_REQUIRE(t.dx % 64 == 0 && (((uintptr_t)data | (uintptr_t)barrier | (uintptr_t)cand) & 15) == 0 && ((uintptr_t)ranges & 3) == 0,
+                IVX_EINVAL, "flood: candidates_ranges needs dx %% 64 == 0, 16-byte aligned buffers and 4-byte aligned records "
+                            "(use ivx_dev_flood_candidates)");
+    const int64_t nchunks = t.dz * t.dy * t.dx / 16;
+    if (!nchunks) return IVX_OK;
+    IVX_REQUIRE(data && ranges && cand, IVX_EINVAL, "flood: candidates_ranges: null argument");
+    const int64_t blocks = ivx::cdiv(nchunks, 256);
+    const int gg = (int)(blocks < 16384 ? blocks : 16384);
+    hipStream_t st = ivx::S(stream);
+    if (barrier_mode == 0)
+        hipLaunchKernelGGL((k_flood_candidates16_ranges<0>), dim3(gg), dim3(256), 0, st, (const short8_t *)data, (const uint4 *)barrier,
+                           (const unsigned *)ranges, nchunks, t0, t1, fill, (uint16_t *)cand);
+    else
+        hipLaunchKernelGGL((k_flood_candidates16_ranges<1>), dim3(gg), dim3(256), 0, st, (const short8_t *)data, (const uint4 *)barrier,
+                           (const unsigned *)ranges, nchunks, t0, t1, fill, (uint16_t *)cand);
+    IVX_LAUNCH_CHECK();
+    return IVX_OK;
 }
 
 extern "C" int ivx_dev_flood_seed(const ivx_flood_plan *p, int dtype, const void *data, double t0, double t1,

@@ -70,6 +70,114 @@ __global__ __launch_bounds__(256) void k_threshold16_bits(const short8_t *__rest
     }
 }
 
+// ---- per-word (min, max) records ---------------------------------------------------------------------------------
+// One record per plane word (64 x-voxels = one 128-byte line of int16): min in the low half, max in the high half of a
+// uint32.  A word that lies wholly inside or wholly outside [lo, hi] needs no voxel: on a CT volume that is most of them,
+// so a threshold of an unchanged image reads 4 B per word and then only the mixed lines (2 B/voxel -> ~0.3 B/voxel).
+// The four lanes of a word are the four lanes of a DPP quad: c = 256 * k + threadIdx.x, so c & 3 == lane & 3, and
+// nchunks % 4 == 0 (dx % 64 == 0) keeps a quad together at the loop's end.
+__device__ __forceinline__ int quad_xor1(int v) { return __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xf, 0xf, true); } // quad_perm [1,0,3,2]
+__device__ __forceinline__ int quad_xor2(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xf, 0xf, true); } // quad_perm [2,3,0,1]
+
+__device__ __forceinline__ unsigned word_record(const short8_t a, const short8_t b) {
+    int mn = a[0], mx = a[0];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        mn = min(mn, min((int)a[i], (int)b[i]));
+        mx = max(mx, max((int)a[i], (int)b[i]));
+    }
+    mn = min(mn, quad_xor1(mn));
+    mx = max(mx, quad_xor1(mx));
+    mn = min(mn, quad_xor2(mn));
+    mx = max(mx, quad_xor2(mx));
+    return ((unsigned)mn & 0xffffu) | ((unsigned)mx << 16);
+}
+
+__global__ __launch_bounds__(256) void k_image_ranges16(const short8_t *__restrict__ img, unsigned *__restrict__ ranges,
+                                                        int64_t nchunks) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < nchunks; c += stride) {
+        const short8_t a = __builtin_nontemporal_load(&img[2 * c]);
+        const short8_t b = __builtin_nontemporal_load(&img[2 * c + 1]);
+        const unsigned rec = word_record(a, b);
+        if ((c & 3) == 0) ranges[c >> 2] = rec;
+    }
+}
+
+// k_threshold16_bits with the records as a by-product: what the first threshold after an image change runs
+__global__ __launch_bounds__(256) void k_threshold16_bits_build(const short8_t *__restrict__ img, uchar16_t *__restrict__ mask,
+                                                                uint16_t *__restrict__ bits, unsigned *__restrict__ ranges,
+                                                                int64_t nchunks, int lo, int hi) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < nchunks; c += stride) {
+        const short8_t a = __builtin_nontemporal_load(&img[2 * c]);
+        const short8_t b = __builtin_nontemporal_load(&img[2 * c + 1]);
+        uchar16_t r;
+        unsigned m = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const bool in0 = (int)a[i] >= lo && (int)a[i] <= hi, in1 = (int)b[i] >= lo && (int)b[i] <= hi;
+            r[i] = in0 ? 255 : 0;
+            r[8 + i] = in1 ? 255 : 0;
+            m |= (in0 ? 1u : 0u) << i;
+            m |= (in1 ? 1u : 0u) << (8 + i);
+        }
+        const unsigned rec = word_record(a, b);
+        mask[c] = r;
+        bits[c] = (uint16_t)m;
+        if ((c & 3) == 0) ranges[c >> 2] = rec;
+    }
+}
+
+// The threshold of an image whose records are valid.  Every lane reads its word's record (the four lanes of a word share
+// the address; a wave reads 64 contiguous bytes) and only the lanes of a mixed word load voxels; the record of the next
+// trip is requested before this trip's stores.  The records are trusted: the image is not looked at where they decide.
+// Measured: 193 MB instead of 422 MB, but 54 us instead of 65 -- the stores alone take 21 us and the sparse
+// reads of the mixed lines add their own time to that whatever the kernel's shape (several chunks in flight per lane, the
+// mixed words compacted through LDS and non-temporal mask stores all measured the same or slower), so this is the plain form.
+__global__ __launch_bounds__(256) void k_threshold16_bits_use(const short8_t *__restrict__ img, uchar16_t *__restrict__ mask,
+                                                              uint16_t *__restrict__ bits, const unsigned *__restrict__ ranges,
+                                                              int64_t nchunks, int lo, int hi) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= nchunks) return;
+    unsigned rec = ranges[c >> 2];
+    for (;;) {
+        const int64_t cn = c + stride;
+        unsigned rec_next = 0;
+        if (cn < nchunks) rec_next = ranges[cn >> 2];
+        const int mn = (int)(short)(rec & 0xffffu), mx = (int)(short)(rec >> 16);
+        uchar16_t r;
+        unsigned m;
+        if (mn >= lo && mx <= hi) {
+#pragma unroll
+            for (int i = 0; i < 16; i++) r[i] = 255;
+            m = 0xffffu;
+        } else if (mx < lo || mn > hi) {
+#pragma unroll
+            for (int i = 0; i < 16; i++) r[i] = 0;
+            m = 0;
+        } else {
+            const short8_t a = __builtin_nontemporal_load(&img[2 * c]);
+            const short8_t b = __builtin_nontemporal_load(&img[2 * c + 1]);
+            m = 0;
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                const bool in0 = (int)a[i] >= lo && (int)a[i] <= hi, in1 = (int)b[i] >= lo && (int)b[i] <= hi;
+                r[i] = in0 ? 255 : 0;
+                r[8 + i] = in1 ? 255 : 0;
+                m |= (in0 ? 1u : 0u) << i;
+                m |= (in1 ? 1u : 0u) << (8 + i);
+            }
+        }
+        mask[c] = r;
+        bits[c] = (uint16_t)m;
+        if (cn >= nchunks) break;
+        c = cn;
+        rec = rec_next;
+    }
+}
+
 // scalar path: tails, unaligned pointers, slices whose size is not a multiple of 16
 template <bool PRESERVE>
 __global__ __launch_bounds__(256) void k_threshold1(const int16_t *__restrict__ img, uint8_t *__restrict__ mask,
@@ -135,6 +243,54 @@ extern "C" int ivx_dev_threshold_i16_bits(const int16_t *img, int64_t dz, int64_
     const int64_t blocks = ivx::cdiv(nchunks, 256);
     hipLaunchKernelGGL(k_threshold16_bits, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, ivx::S(stream),
                        (const short8_t *)img, (uchar16_t *)mask, (uint16_t *)bits, nchunks, lo, hi);
+    IVX_LAUNCH_CHECK();
+    return IVX_OK;
+}
+
+extern "C" int ivx_image_ranges_bytes(int64_t dz, int64_t dy, int64_t dx, size_t *nbytes) {
+    IVX_REQUIRE(nbytes, IVX_EINVAL, "image_ranges: nbytes is NULL");
+    IVX_REQUIRE(dz >= 0 && dy >= 0 && dx >= 0, IVX_EINVAL, "image_ranges: negative shape");
+    IVX_REQUIRE(dx % 64 == 0, IVX_EINVAL, "image_ranges: needs dx %% 64 == 0 (rows of whole 64-voxel words)");
+    *nbytes = (size_t)(dz * dy * (dx / 64)) * 4;
+    return IVX_OK;
+}
+
+static inline unsigned ranges_grid(int64_t nchunks) {
+    const int64_t blocks = ivx::cdiv(nchunks, 256);
+    return (unsigned)(blocks < 16384 ? blocks : 16384);
+}
+
+extern "C" int ivx_dev_image_ranges_i16(const int16_t *img, int64_t dz, int64_t dy, int64_t dx, uint32_t *ranges,
+                                        void *stream) {
+    IVX_REQUIRE(dz >= 0 && dy >= 0 && dx >= 0, IVX_EINVAL, "image_ranges: negative shape");
+    IVX_REQUIRE(dx % 64 == 0 && ((uintptr_t)img & 15) == 0 && ((uintptr_t)ranges & 3) == 0, IVX_EINVAL,
+                "image_ranges: needs dx %% 64 == 0, a 16-byte aligned image and 4-byte aligned records");
+    const int64_t n = dz * dy * dx;
+    if (n == 0) return IVX_OK;
+    IVX_REQUIRE(img && ranges, IVX_EINVAL, "image_ranges: null argument");
+    hipLaunchKernelGGL(k_image_ranges16, dim3(ranges_grid(n / 16)), dim3(256), 0, ivx::S(stream), (const short8_t *)img,
+                       (unsigned *)ranges, n / 16);
+    IVX_LAUNCH_CHECK();
+    return IVX_OK;
+}
+
+extern "C" int ivx_dev_threshold_i16_bits_ranges(const int16_t *img, int64_t dz, int64_t dy, int64_t dx, int lo, int hi,
+                                                 uint8_t *mask, uint64_t *bits, uint32_t *ranges, int mode, void *stream) {
+    IVX_REQUIRE(dz >= 0 && dy >= 0 && dx >= 0, IVX_EINVAL, "threshold: negative shape");
+    IVX_REQUIRE(dx % 64 == 0 && (((uintptr_t)img | (uintptr_t)mask | (uintptr_t)bits) & 15) == 0 && ((uintptr_t)ranges & 3) == 0,
+                IVX_EINVAL, "threshold_bits_ranges: needs dx %% 64 == 0, 16-byte aligned buffers and 4-byte aligned records "
+                            "(use ivx_dev_threshold_i16)");
+    IVX_REQUIRE(mode == IVX_RANGES_BUILD || mode == IVX_RANGES_USE, IVX_EINVAL, "threshold_bits_ranges: mode %d", mode);
+    const int64_t n = dz * dy * dx;
+    if (n == 0) return IVX_OK;
+    IVX_REQUIRE(img && mask && bits && ranges, IVX_EINVAL, "threshold_bits_ranges: null argument");
+    const int64_t nchunks = n / 16;
+    if (mode == IVX_RANGES_BUILD)
+        hipLaunchKernelGGL(k_threshold16_bits_build, dim3(ranges_grid(nchunks)), dim3(256), 0, ivx::S(stream),
+                           (const short8_t *)img, (uchar16_t *)mask, (uint16_t *)bits, (unsigned *)ranges, nchunks, lo, hi);
+    else
+        hipLaunchKernelGGL(k_threshold16_bits_use, dim3(ranges_grid(nchunks)), dim3(256), 0, ivx::S(stream),
+                           (const short8_t *)img, (uchar16_t *)mask, (uint16_t *)bits, (const unsigned *)ranges, nchunks, lo, hi);
     IVX_LAUNCH_CHECK();
     return IVX_OK;
 }

@@ -233,6 +233,11 @@ class DeviceVolume:
         self._out_pending = None      # fill value of a deferred `out_mask[reached] = fill` (self.reached still holds it)
         self._fuse = os.environ.get("IVX_NO_FUSE", "") == ""
         self._apply_levels = os.environ.get("IVX_APPLY_LEVELS", "1") != "0"  # (A/B: mask[reached] = v from the bit planes alone)
+        self._use_ranges = os.environ.get("IVX_RANGES", "1") != "0"  # (A/B: threshold / candidates from the per-word records)
+        # (min, max) of every 64-voxel x-word of the image (ivx_dev_image_ranges_i16): written by the first fused threshold
+        # after the image's bytes changed, read by every later one.  Dropped with the image (_image_touched), like _range_valid.
+        self._ranges = None
+        self._ranges_valid = False
         self.image = TrackedBuffer(self.n * 2, self._image_touched)
         self.mask = TrackedBuffer(self.n, self._mask_touched)       # dense interior of mask.matrix[1:,1:,1:]
         self.out_mask = TrackedBuffer(self.n, self._out_touched)    # region-growing `out` (styles.py:3190)
@@ -262,6 +267,7 @@ class DeviceVolume:
     def _image_touched(self):
         self._mbits_range = None
         self._range_valid = False
+        self._ranges_valid = False
         self._drop_volren()
 
     def _mask_touched(self):
@@ -319,6 +325,7 @@ class DeviceVolume:
         self._drop_maskren()
         for b in (self.image, self.mask, self.out_mask, self.cand, self.reached, self._mbits, self.flood_scratch,
                   self._mc_scratch, self._tris, self._verts, self._faces, self._gate, getattr(self, "_range_buf", None),
+                  getattr(self, "_ranges", None),
                   getattr(self, "prob", None)):
             if b is not None:
                 b.close()
@@ -358,14 +365,30 @@ class DeviceVolume:
         if self._fuse and not preserve and self.dx % 64 == 0:
             self._mbits_version += 1
             self._mp_cells_valid = False
-            L.check(lib.ivx_dev_threshold_i16_bits(self.image.raw, c64(self.dz), c64(self.dy), c64(self.dx), int(lo), int(hi),
-                                                   self.mask.raw, self._mbits.ptr, self.stream), "threshold")
+            if self._use_ranges:
+                # the first threshold of an image leaves the records behind, every later one reads them and the mixed words only
+                mode = 1 if self._ranges_valid else 0  # IVX_RANGES_USE / IVX_RANGES_BUILD
+                L.check(lib.ivx_dev_threshold_i16_bits_ranges(self.image.raw, c64(self.dz), c64(self.dy), c64(self.dx), int(lo), int(hi),
+                                                              self.mask.raw, self._mbits.ptr, self._ranges_buffer().ptr, mode,
+                                                              self.stream), "threshold")
+                self._ranges_valid = True
+            else:
+                L.check(lib.ivx_dev_threshold_i16_bits(self.image.raw, c64(self.dz), c64(self.dy), c64(self.dx), int(lo), int(hi),
+                                                       self.mask.raw, self._mbits.ptr, self.stream), "threshold")
             self._mbits_valid, self._mbits_range = True, (int(lo), int(hi))
             self._mask_levels = (255, None)  # mask == 255 * plane, byte for byte
             return
         L.check(lib.ivx_dev_threshold_i16(self.image.raw, c64(self.dz), c64(self.dy), c64(self.dx), int(lo), int(hi),
                                           int(bool(preserve)), None, self.mask.raw, self.stream), "threshold")
         self._mask_touched()
+
+    def _ranges_buffer(self) -> DeviceBuffer:
+        if self._ranges is None:
+            nb = ctypes.c_size_t(0)
+            L.check(L.lib().ivx_image_ranges_bytes(c64(self.dz), c64(self.dy), c64(self.dx), ctypes.byref(nb)), "image_ranges_bytes")
+            self._ranges = DeviceBuffer(max(nb.value, 4))
+            self._ranges_valid = False
+        return self._ranges
 
     # -- region growing (floodfill.rs:96-166 on the image; styles.py:3151-3216) ----------------------------
     def lut_image_255(self, ww, wl) -> DeviceBuffer:
@@ -429,9 +452,17 @@ class DeviceVolume:
                   and self._mbits_range == (int(t0), int(t1)))
         if shared:
             return self._mbits, True
+        # out_mask's bytes known to be zero (fill's byte is not): nothing is barred, and reading 1 B/voxel to learn that is a
+        # pass over memory for nothing
+        bar, bar_mode = (None, 0) if (self._out_logically_zero() and (int(fill) & 0xff) != 0) else (self.out_mask.raw, 1)
+        if image is None and self._use_ranges and self._ranges_valid:
+            L.check(L.lib().ivx_dev_flood_candidates_ranges(ctypes.byref(self.plan), self.image.raw, ctypes.c_double(t0),
+                                                            ctypes.c_double(t1), bar, bar_mode, ctypes.c_double(fill),
+                                                            self._ranges.ptr, self.cand.ptr, self.stream), "flood_candidates_ranges")
+            return self.cand, False
         img_ptr = image.ptr if image is not None else self.image.raw
         L.check(L.lib().ivx_dev_flood_candidates(ctypes.byref(self.plan), L.I16, img_ptr, ctypes.c_double(t0),
-                                                 ctypes.c_double(t1), self.out_mask.raw, 1, ctypes.c_double(fill),
+                                                 ctypes.c_double(t1), bar, bar_mode, ctypes.c_double(fill),
                                                  self.cand.ptr, self.stream))
         return self.cand, False
 
@@ -838,7 +869,8 @@ class DeviceVolume:
         bytes change (any access to `image` from outside the pipeline's kernels drops it, like the bit-plane notes), the way
         `Slice` keeps the image's histogram (slice_.py:192-194; SURVEY 8d counts the cached range as allowed).
         `forget_image_range()` drops it by hand -- and every writer inside this package that goes to `image.raw` /
-        `image.raw_at()` directly (past the tracked accessor) must call it."""
+        `image.raw_at()` directly (past the tracked accessor) must call it -- or `_image_touched()`, which also drops the
+        per-word records the threshold keeps (`_ranges`)."""
         if getattr(self, "_range_buf", None) is None:
             self._range_buf = DeviceBuffer(64)
             self._range_valid = False

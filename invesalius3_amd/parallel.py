@@ -189,6 +189,7 @@ def _make_slab_volume():
                                self.image.raw_at(lay.last_interior * sb), self.image.raw_at((lay.local_dz - 1) * sb), sb,
                                self.stream)
             self.sync()
+            self._image_touched()  # written past the tracked accessor: nothing derived from the image's bytes may survive
             self.plane_words = self.dy * self.plan.wx
             self._recv = [DeviceBuffer(self.plane_words * 8) for _ in range(2)]
             self._votes = DeviceBuffer(64)  # int32 [0] vote travelling with the planes, [1] words my last OR gained

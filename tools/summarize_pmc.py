@@ -52,8 +52,10 @@ def main():
         import json
         # steps of the kernel-trace run (warm-up + timed + the bench's instrumented extra steps); "auto" = the call count
         # of a kernel that runs exactly once per step
-        once = [k for k in stats if k.startswith("k_threshold16")]  # (k_flood_clear no longer runs in the fused start)
-        nsteps = stats[once[0]][0] if sys.argv[4] == "auto" else int(sys.argv[4])
+        # (k_flood_clear no longer runs in the fused start; the threshold is k_threshold16_bits_build once per upload and
+        # k_threshold16_bits_use in every other step: together once per step)
+        once = sum(stats[k][0] for k in stats if k.startswith("k_threshold16"))
+        nsteps = once if sys.argv[4] == "auto" else int(sys.argv[4])
         stage_of = lambda k: ("threshold" if k.startswith("k_threshold") else "marching_cubes" if k.startswith("k_mc_")
                               else "region_grow" if k.startswith(("k_flood_", "k_ccl_", "k_scan_")) and not k.startswith("k_flood_count")
                               else None)
