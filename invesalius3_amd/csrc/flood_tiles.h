@@ -36,7 +36,6 @@ static int make_tiles(const ivx_flood_plan *p, Tiles *t) {
         const uint32_t sb = p->strct_bits | (1u << 13);
         t->conn = sb == m26 ? 26 : sb == m18 ? 18 : sb == m6 ? 6 : 0;
     }
-    if (getenv("IVX_FLOOD_DBG")) t->strct |= 1u << 30;
     // One tile crossing (TY = TZ = 16 rows) per visit: a tile that is still changing after that re-enlists itself and
     // carries on in the next round, when its neighbours have already started on what it has published so far -- the
     // rounds pipeline instead of waiting for the slowest tile's local fix-point (measured 0.240 -> 0.232 ms on the bench
@@ -53,7 +52,7 @@ static int make_tiles(const ivx_flood_plan *p, Tiles *t) {
 
 // scratch: dirty[2][ntiles] u8 | counter ring | seed staging | status words | round lists | coarse-pass row words
 constexpr size_t SEED_CHUNK = 4096;
-// the counter block: counter ring, the resident launch's control words, the rounds' list lengths (k_flood.hip)
+// the counter block: counter ring, four reserved dwords, the rounds' list lengths (k_flood.hip)
 constexpr int FLOOD_CNT_DWORDS = 128;
 static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 struct FScratch {

@@ -228,16 +228,14 @@ __device__ __forceinline__ unsigned long long fill_runs(unsigned long long seed,
     return __brevll(fill_up(__brevll(f), __brevll(m)));
 }
 
-// Tile update shared by the per-round kernel and the resident launch.
+// Tile update of the per-round kernel.
 // LDS holds, for the 18x18 rows of the tile + halo: sN = the row's word, sD = the row's word dilated by one voxel
 // along x including the carry bits of the x-neighbour words (so a full 3-wide strct row costs ONE LDS read), and the
 // two carry bits themselves (generic structuring elements).  The local fix-point is a chaotic relaxation: reached
 // bits only ever get OR'ed in, so a lane may read a neighbour's word while it is being rewritten -- any mix of old
 // and new bits is a valid intermediate state -- and ONE barrier per iteration (the termination vote) is enough.
-// ATOMIC: stage / publish with agent-scope atomics (needed when other workgroups update neighbours concurrently
-// AND no kernel boundary orders them, i.e. between the rounds of the resident launch, k_flood_resident).
-__device__ unsigned long long g_dbg[16];
-#define DBG_T(i) if (DBG && threadIdx.x == 0) g_dbg[i] = __builtin_readcyclecounter();
+// Staging loads and the publish store are plain: a round's visits never share a tile, a neighbour's publish can only add
+// bits to a halo row, and the kernel boundary between two rounds orders one round's stores before the next one's loads.
 // workgroup barrier that only waits for this wave's LDS traffic (lgkmcnt), NOT for its global stores/atomics in flight:
 // __syncthreads() also drains vmcnt, which would park the whole tile behind the publish stores (~2.5 us).
 __device__ __forceinline__ void lds_barrier() {
@@ -265,7 +263,7 @@ __device__ __forceinline__ void post_dirs(TileLds &L, unsigned dirs) {
     if ((threadIdx.x & 63) == 0 && dirs) atomicOr(&L.dirs, dirs);
 }
 
-template <bool ATOMIC, int CONN, bool DBG = false>
+template <int CONN>
 __device__ __forceinline__ void tile_update(const Tiles &t, const unsigned long long *__restrict__ cand,
                                             unsigned long long *reached, int64_t tile, TileLds &L, TileOpen &O) {
     const int64_t txi = tile % t.wx, r1 = tile / t.wx;
@@ -289,8 +287,7 @@ __device__ __forceinline__ void tile_update(const Tiles &t, const unsigned long 
 #pragma unroll
                 for (int xx = 0; xx < 3; xx++) {
                     const int64_t w = txi + xx - 1;
-                    if (w >= 0 && w < t.wx)
-                        w3[pass][xx] = ATOMIC ? __hip_atomic_load(row + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : row[w];
+                    if (w >= 0 && w < t.wx) w3[pass][xx] = row[w];
                 }
                 if (zz == 0 || zz == HZ - 1 || yy == 0 || yy == HY - 1) hc[pass] = cand[(z * t.dy + y) * t.wx + txi];
                 hx[pass] = 1u;
@@ -319,7 +316,6 @@ __device__ __forceinline__ void tile_update(const Tiles &t, const unsigned long 
     const unsigned long long c = inside ? cand[(z * t.dy + y) * t.wx + txi] : 0ull;
     if (threadIdx.x == 0) L.vote[0] = 0u;
     __syncthreads();
-    DBG_T(1)
     const int me = (tz + 1) * HY + (ty + 1);
     const unsigned long long r_in = L.sN[me];
     const unsigned long long mycl = L.sCL[me] & 1u, mycr = L.sCR[me];
@@ -393,13 +389,10 @@ __device__ __forceinline__ void tile_update(const Tiles &t, const unsigned long 
             break;
         }
     }
-    DBG_T(2)
-    if (DBG && threadIdx.x == 0) g_dbg[8] = 0;
     const unsigned long long chg = r ^ r_in;
     unsigned dirs = 0;
     if (chg) {
-        if (ATOMIC) atomicOr(&reached[(z * t.dy + y) * t.wx + txi], r); // monotone publish: bits are never lost
-        else reached[(z * t.dy + y) * t.wx + txi] = r;
+        reached[(z * t.dy + y) * t.wx + txi] = r;
         if (exhausted) dirs |= 1u << 13; // iteration cap hit before the local fix-point: revisit this tile
     }
     // Wake a neighbour tile only for an OPEN candidate: a voxel of it that is a candidate, was unreached when this visit
@@ -449,37 +442,32 @@ __device__ __forceinline__ void tile_update(const Tiles &t, const unsigned long 
 }
 
 // the structuring element's gather is a compile-time pattern for the three standard structures (see tile_update)
-template <bool ATOMIC>
 __device__ __forceinline__ void tile_update_conn(const Tiles &t, const unsigned long long *__restrict__ cand,
                                                  unsigned long long *reached, int64_t tile, TileLds &L, TileOpen &O) {
-    if (t.conn == 26) tile_update<ATOMIC, 26>(t, cand, reached, tile, L, O);
-    else if (t.conn == 18) tile_update<ATOMIC, 18>(t, cand, reached, tile, L, O);
-    else if (t.conn == 6) tile_update<ATOMIC, 6>(t, cand, reached, tile, L, O);
-    else tile_update<ATOMIC, 0>(t, cand, reached, tile, L, O);
+    if (t.conn == 26) tile_update<26>(t, cand, reached, tile, L, O);
+    else if (t.conn == 18) tile_update<18>(t, cand, reached, tile, L, O);
+    else if (t.conn == 6) tile_update<6>(t, cand, reached, tile, L, O);
+    else tile_update<0>(t, cand, reached, tile, L, O);
 }
 
 // ---- tile hand-off: what a visit leaves for the next round ------------------------------------------------------------
-#define AT_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define AT_STORE(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 // Mark tile nt in the next round's byte flags (four tiles per word: the atomicOr goes to the byte's word); whoever marks
 // a byte first appends the tile to the next round's list.  MARK / SEEN: the bit set and the bits that mean "somebody was
-// here before" (the coarse pass enlists with a bit of its own, see ENLISTED).  ATOMIC: the list entry is an agent-scope
-// store (the resident launch reads it without a kernel boundary in between).
-template <bool ATOMIC, unsigned int MARK = 1u, unsigned int SEEN = 0xffu>
+// here before" (the coarse pass enlists with a bit of its own, see ENLISTED).  The list entry is a plain store: the next
+// round reads it behind a kernel boundary.
+template <unsigned int MARK = 1u, unsigned int SEEN = 0xffu>
 __device__ __forceinline__ void enlist_tile(uint8_t *dirty_next, unsigned int *list_next, unsigned int *n_next, int64_t nt) {
     unsigned int *wp = (unsigned int *)(dirty_next + (nt & ~(int64_t)3));
     const unsigned int sh = 8 * (unsigned int)(nt & 3);
     const unsigned int old = atomicOr(wp, MARK << sh);
     if (!((old >> sh) & SEEN)) {
         unsigned int *slot = &list_next[atomicAdd(n_next, 1u)];
-        if (ATOMIC) AT_STORE(slot, (unsigned int)nt);
-        else *slot = (unsigned int)nt;
+        *slot = (unsigned int)nt;
     }
 }
 // After the tile update (L.dirs and L.open complete): a tile with no candidate left is closed for good, so nobody needs to
 // enlist it again (see CLOSED), and lane d < 27 wakes the neighbour tile in direction d when the visit's new bits touch an
 // open candidate of that tile (bit 13 = the tile itself: the iteration cap ended the visit).
-template <bool ATOMIC>
 __device__ __forceinline__ void publish_tile(const Tiles &t, int64_t tile, const TileLds &L, uint8_t *dirty_cur,
                                              uint8_t *dirty_next, unsigned int *list_next, unsigned int *n_next) {
     const int64_t txi = tile % t.wx, r1 = tile / t.wx;
@@ -493,7 +481,7 @@ __device__ __forceinline__ void publish_tile(const Tiles &t, int64_t tile, const
         const int d = threadIdx.x;
         const int64_t nz = tzi + d / 9 - 1, ny = tyi + (d / 3) % 3 - 1, nx = txi + d % 3 - 1;
         if (nz >= 0 && nz < t.ntz && ny >= 0 && ny < t.nty && nx >= 0 && nx < t.wx)
-            enlist_tile<ATOMIC>(dirty_next, list_next, n_next, (nz * t.nty + ny) * t.wx + nx);
+            enlist_tile(dirty_next, list_next, n_next, (nz * t.nty + ny) * t.wx + nx);
     }
 }
 
@@ -604,7 +592,7 @@ __device__ __forceinline__ bool lin_enlist(const Tiles &t, int64_t word, int64_t
     const int64_t row = word / t.wx, txi = word - row * t.wx, z = row / t.dy, y = row - z * t.dy;
     const int64_t nt = ((z / TZ) * t.nty + (y >> TY_LOG)) * t.wx + txi;
     if (nt == self) return true;
-    enlist_tile<false>(dirty_next, list_next, n_next, nt);
+    enlist_tile(dirty_next, list_next, n_next, nt);
     return false;
 }
 
@@ -691,13 +679,6 @@ __device__ __forceinline__ void tile_update_lin(const Tiles &t, const unsigned l
     if (threadIdx.x == 0) L.open = 1u; // (arc planes change from level to level: a tile is never closed for good)
 }
 
-// diagnostic only (not part of include/ivx.h): cycle stamps written under IVX_FLOOD_DBG=1, see tools/dbg_tile.py
-extern "C" int ivx_debug_read(unsigned long long *out16) {
-    IVX_HIP(hipDeviceSynchronize());
-    IVX_HIP(hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_dbg), 16 * 8));
-    return IVX_OK;
-}
-
 // ---- list-driven round: only as many workgroups as there are dirty tiles do any work ------------------------------------
 // The dirty set of a round is a compact list (plus the byte flags, which de-duplicate marks).  A workgroup takes list
 // entries blockIdx.x, blockIdx.x + gridDim.x, ...; an idle round costs one small launch instead of ntiles empty workgroups,
@@ -712,6 +693,7 @@ __global__ void k_flood_build_list(Tiles t, const uint8_t *__restrict__ dirty, u
 // list in a word of its own -- one plain store beside the others thread 0 of workgroup 0 issues as the round starts, no load, so
 // no visit waits for it -- and the rounds past HIST (the union-find escape takes a plain flood over long before; the
 // directed and the linear floods can get there) add theirs to one more word; the stream orders the rounds.
+// (Dwords 32 .. 35, right below STATS_AT, are a reserved gap: cleared with the block, used by nothing.)
 constexpr int STATS_AT = 36, HIST_AT = 64, HIST = 64, CNT_CLEARED = HIST_AT + HIST;
 static_assert(CNT_CLEARED == FLOOD_CNT_DWORDS, "the counter block of flood_tiles.h");
 __device__ __forceinline__ void count_visits(unsigned int *cnt, unsigned int round, unsigned int n) {
@@ -753,120 +735,15 @@ __global__ __launch_bounds__(NT, 6) void k_flood_round_list(Tiles t, const unsig
             L.open = 0;
         }
         __syncthreads();
-        const bool dbg = (t.strct >> 30 & 1u) && li == 0; // IVX_FLOOD_DBG: cycle stamps of the first tile (tools/dbg_tile.py)
-        if (dbg && threadIdx.x == 0) g_dbg[0] = __builtin_readcyclecounter();
         if constexpr (MODE == 2) tile_update_lin(t, cand, reached, tile, L, dirty_next, list_next, n_next);
         else if constexpr (MODE == 1) tile_update_dir(t, cand, reached, tile, L);
         else {
             __shared__ TileOpen O; // (the candidate-plane flood only)
-            if (dbg) tile_update<false, 26, true>(t, cand, reached, tile, L, O);
-            else tile_update_conn<false>(t, cand, reached, tile, L, O);
+            tile_update_conn(t, cand, reached, tile, L, O);
         }
         lds_barrier(); // L.dirs complete; the publish stores keep flying (the kernel boundary orders them for the next round)
-        if (dbg && threadIdx.x == 0) g_dbg[3] = __builtin_readcyclecounter();
-        publish_tile<false>(t, tile, L, dirty_cur, dirty_next, list_next, n_next);
-        if (dbg && threadIdx.x == 0) g_dbg[4] = __builtin_readcyclecounter();
+        publish_tile(t, tile, L, dirty_cur, dirty_next, list_next, n_next);
         __syncthreads(); // L is reused by the next list entry of this workgroup
-    }
-}
-
-// ---- resident rounds: the same rounds, ONE launch ------------------------------------------------------------------
-// A launch per round costs ~5 us of dispatch whether the round has 1 500 tiles or none, the host has to see a round start
-// with an empty list before it stops queueing (three more empty launches are in the queue by then), and the stage that
-// follows waits behind all of them.  Here the grid stays resident (every workgroup is on a compute unit at once: the host
-// sizes the grid from the occupancy) and a round boundary is a device-wide barrier: a workgroup drains its own stores and
-// atomics (s_waitcnt), signs an arrival counter and polls it.  Everything that crosses workgroups inside the launch --
-// reached words, dirty bytes, list entries, counters -- is an agent-scope access (served where all XCDs meet), so the
-// boundary needs no L2 write-back.  Only workgroups that had a tile this round sign (the others just wait for them).
-// The kernel ends at the first empty list, or after `round_cap` rounds (the caller's escape to the union-find engine), or
-// -- every spin is bounded -- with status 3 when a barrier never completes (the caller finishes with launches per round:
-// `reached` is monotone, a partial result is valid).  The last word goes to the pinned progress line.
-// OPT-IN (IVX_FLOOD_RESIDENT=1), measured slower on the bench volume: region growing 0.27 ms with one workgroup per compute
-// unit, 0.31 / 0.42 / 0.49 ms with 2 / 4 / 6, against 0.19 ms for one launch per round -- a round inside the launch is a chain
-// of ~6 agent-scope round trips of ~1.2 us (poll, list entry, staged rows, publish, drain, arrival) and up to 10^3 pollers
-// share one address, while a kernel boundary costs ~5 us flat and its loads hit the L2.  What the launch per round cannot
-// do -- have the next stage queued before the flood ends -- ivx_dev_flood_grow_async / ivx_dev_flood_wait offer with it.
-struct ResCtl {
-    unsigned int arrive; // barrier arrivals since the launch (monotone)
-    unsigned int status; // 0 running, 1 converged, 2 round cap reached, 3 a barrier timed out
-    unsigned int rounds; // rounds that had work
-    unsigned int visits; // (statistics) tile visits
-};
-constexpr int RES_CTL_AT = 32; // dword index of ResCtl inside the counter block (cleared together with the counter ring)
-static_assert(STATS_AT == RES_CTL_AT + 4, "the statistics word sits right behind ResCtl");
-__global__ __launch_bounds__(NT, 6) void k_flood_resident(Tiles t, const unsigned long long *__restrict__ cand,
-                                                           unsigned long long *reached, unsigned int *list0,
-                                                           unsigned int *list1, unsigned int *cnt, uint8_t *dirty0,
-                                                           uint8_t *dirty1, ResCtl *ctl, unsigned long long *line,
-                                                           unsigned int tag, unsigned int ring, unsigned int round_cap,
-                                                           unsigned int max_spins, unsigned int *gate, unsigned int gate_val,
-                                                           unsigned int gate_below) {
-    __shared__ TileLds L;
-    __shared__ TileOpen O;
-    __shared__ unsigned int s_n, s_abort;
-    unsigned int target = 0, round = 0, status = 1;
-    for (;; round++) {
-        const unsigned int r = round % ring, cur = round & 1u;
-        if (threadIdx.x == 0) {
-            s_n = AT_LOAD(&cnt[r]);
-            s_abort = 0u;
-        }
-        __syncthreads();
-        const unsigned int n = s_n;
-        if (n == 0u) break;
-        if (round >= round_cap) {
-            status = 2;
-            break;
-        }
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            AT_STORE(&cnt[(r + 2u) % ring], 0u); // the counter the round AFTER the next one appends to
-            count_visits(cnt, round + 1u, n);
-            if (gate && n < gate_below) AT_STORE(gate, gate_val);
-        }
-        unsigned int *list_cur = cur ? list1 : list0, *list_next = cur ? list0 : list1;
-        uint8_t *dirty_cur = cur ? dirty1 : dirty0, *dirty_next = cur ? dirty0 : dirty1;
-        unsigned int *n_next = cnt + (r + 1u) % ring;
-        for (unsigned int li = blockIdx.x; li < n; li += gridDim.x) {
-            const int64_t tile = AT_LOAD(&list_cur[li]);
-            if (threadIdx.x == 0) {
-                __hip_atomic_store(&dirty_cur[tile], (uint8_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                L.dirs = 0;
-                L.open = 0;
-            }
-            __syncthreads();
-            tile_update_conn<true>(t, cand, reached, tile, L, O);
-            lds_barrier(); // L.dirs complete; the publishing atomics keep flying until the round's barrier
-            publish_tile<true>(t, tile, L, dirty_cur, dirty_next, list_next, n_next);
-            __syncthreads(); // L is reused by the next list entry of this workgroup
-        }
-        // the round's barrier: min(n, grid) workgroups had work and sign; everybody waits for all of them
-        target += n < gridDim.x ? n : gridDim.x;
-        __builtin_amdgcn_s_waitcnt(0); // this wave's stores and atomics have been acknowledged
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            if (blockIdx.x < n) atomicAdd(&ctl->arrive, 1u);
-            for (unsigned int spins = 0; (int)(AT_LOAD(&ctl->arrive) - target) < 0; spins++) {
-                if (spins > max_spins || AT_LOAD(&ctl->status) == 3u) {
-                    AT_STORE(&ctl->status, 3u);
-                    s_abort = 1u;
-                    break;
-                }
-                if (blockIdx.x < n) __builtin_amdgcn_s_sleep(2);
-                else __builtin_amdgcn_s_sleep(24); // (a workgroup without work this round: poll gently)
-            }
-        }
-        __syncthreads();
-        if (s_abort) {
-            status = 3;
-            break;
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        if (status != 3u) AT_STORE(&ctl->status, status);
-        AT_STORE(&ctl->rounds, round);
-        if (gate) AT_STORE(gate, gate_val); // whatever happened, the gate is open when the flood is over
-        __hip_atomic_store(&line[0], ((unsigned long long)tag << 56) | ((unsigned long long)status << 48) | round, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 
@@ -1122,7 +999,7 @@ __global__ __launch_bounds__(256) void k_flood_block_apply(Tiles t, Blocks bk, c
             // OR-ed into a halo slice): even when those bits already fill the tile, nobody has told its neighbours yet
             s_chg[threadIdx.x] = s_all[threadIdx.x] = 1u;
         } else {
-            enlist_tile<false, ENLISTED, ENLISTED | CLOSED>(dirty, list, count, tile0 + threadIdx.x);
+            enlist_tile<ENLISTED, ENLISTED | CLOSED>(dirty, list, count, tile0 + threadIdx.x);
         }
     }
     if (!FRESH && !whole) return; // uniform
@@ -1182,7 +1059,7 @@ __global__ __launch_bounds__(256) void k_flood_block_apply(Tiles t, Blocks bk, c
             const unsigned long long wt = (unsigned long long)((unsigned int)(whole >> (bk.q * txi)) & qm) << (bk.q * txi);
             if (!((unsigned int)((wt | (wt << 1) | (wt >> 1)) >> (bk.q * nx)) & ex & ~wn)) continue;
         }
-        enlist_tile<false, ENLISTED, ENLISTED | CLOSED>(dirty, list, count, (nz * t.nty + ny) * t.wx + nx);
+        enlist_tile<ENLISTED, ENLISTED | CLOSED>(dirty, list, count, (nz * t.nty + ny) * t.wx + nx);
     }
 }
 
@@ -1699,69 +1576,8 @@ static int poll_line(volatile unsigned long long *line, long spins, hipStream_t 
     IVX_REQUIRE(done(*word), IVX_EHIP, "%s", never);
     return IVX_OK;
 }
-// a resident launch (k_flood_resident) whose last word has not been read yet, keyed by the scratch it runs on
-struct ResPending {
-    volatile unsigned long long *line;
-    uint32_t tag;
-    bool ccl_at_cap;
-};
-static std::map<const void *, ResPending> g_res_pending;
-static std::mutex g_res_mu;
 static int flood_run_impl(const ivx_flood_plan *p, const uint64_t *cand, ivx::FloodMode mode, uint64_t *reached, void *scratch_,
-                          int *rounds, void *stream, const Fresh *fresh = nullptr, int resident = -1);
-// Wait for the resident launch on `scratch_` (if any) and finish what it left: *late = 1 when `reached` was completed after
-// the launch had ended (round cap -> union-find engine; timed-out barrier -> launches per round), i.e. when work the caller
-// queued behind the launch has seen an incomplete plane and must be queued again.
-static int flood_wait_impl(const ivx_flood_plan *p, const uint64_t *cand, uint64_t *reached, void *scratch_, int *rounds,
-                           int *late, void *stream) {
-    if (late) *late = 0;
-    ResPending rp;
-    {
-        std::lock_guard<std::mutex> lk(g_res_mu);
-        auto it = g_res_pending.find(scratch_);
-        if (it == g_res_pending.end()) return IVX_OK; // nothing pending: the flood completed inside its call
-        rp = it->second;
-        g_res_pending.erase(it);
-    }
-    hipStream_t st = ivx::S(stream);
-    unsigned long long v = 0;
-    const uint32_t tag = rp.tag;
-    int rc = poll_line(rp.line, 40000000L, st,
-                       [tag](unsigned long long w) { return (uint32_t)(w >> 56) == tag && ((w >> 48) & 0xffull) != 0; },
-                       "flood: the resident launch never reported", &v);
-    if (rc) return rc;
-    const unsigned int status = (unsigned int)((v >> 48) & 0xffull);
-    int done_rounds = (int)(v & 0xffffffffull);
-    static const bool trace = getenv("IVX_FLOOD_TRACE") != nullptr;
-    if (trace) fprintf(stderr, "ivx flood: resident launch ended with status %u after %d rounds\n", status, done_rounds);
-    if (status != 1u) {
-        // round cap on a long, thin region: the union-find engine completes the components reached so far; a barrier that
-        // timed out (or a cap without that escape): every tile is marked and launches per round finish the flood
-        const bool to_ccl = status == 2u && rp.ccl_at_cap;
-        if (!to_ccl)
-            fprintf(stderr, "ivx: resident flood launch ended with status %u after %d rounds; finishing with launches per round\n", status,
-                    done_rounds);
-        Tiles t;
-        if ((rc = make_tiles(p, &t))) return rc;
-        const FScratch s = make_fscratch(t);
-        char *scr = (char *)scratch_;
-        IVX_HIP(hipMemsetAsync(scr + s.off_dirty0, to_ccl ? 0 : 1, (size_t)t.ntiles, st));
-        IVX_HIP(hipMemsetAsync(scr + s.off_dirty1, 0, (size_t)t.ntiles, st));
-        int more = 1;
-        if (to_ccl) rc = ivx::ccl_run(p, cand, reached, scratch_, st);
-        else rc = flood_run_impl(p, cand, ivx::FLOOD_SYMMETRIC, reached, scratch_, &more, stream, nullptr, 0);
-        if (rc) return rc;
-        done_rounds += more;
-        if (late) *late = 1;
-    }
-    if (rounds) *rounds = done_rounds;
-    return IVX_OK;
-}
-// resident: -1 = as IVX_FLOOD_RESIDENT says, returns when the flood is complete; 0 = launches per round; 1 = resident launch
-// allowed AND the call may return right behind it (ivx_dev_flood_grow_async: the caller picks the result up with
-// ivx_dev_flood_wait)
-static int flood_run_impl(const ivx_flood_plan *p, const uint64_t *cand, ivx::FloodMode mode, uint64_t *reached, void *scratch_,
-                          int *rounds, void *stream, const Fresh *fresh, int resident) {
+                          int *rounds, void *stream, const Fresh *fresh = nullptr) {
     const bool sym = mode == ivx::FLOOD_SYMMETRIC;
     Tiles t;
     int rc = make_tiles(p, &t);
@@ -1825,47 +1641,6 @@ static int flood_run_impl(const ivx_flood_plan *p, const uint64_t *cand, ivx::Fl
     volatile unsigned long long *line = nullptr;
     uint32_t tag = 0;
     if ((rc = ivx::progress_line(st, &line, &tag))) return rc;
-    // IVX_FLOOD_RESIDENT=1: the rounds in one resident launch (opt-in: measured slower, see k_flood_resident)
-    static const bool resident_env = [] {
-        const char *e = getenv("IVX_FLOOD_RESIDENT");
-        return e && e[0] == '1';
-    }();
-    if (sym && resident != 0 && resident_env) {
-        static const unsigned int max_spins = [] {
-            const char *e = getenv("IVX_FLOOD_MAX_SPINS");
-            return e ? (unsigned int)strtoul(e, nullptr, 10) : (1u << 20);
-        }();
-        static int res_per_cu = 0, ncu = 0;
-        if (!ncu) {
-            int dev = 0, occ = 0, n = 0;
-            IVX_HIP(hipGetDevice(&dev));
-            IVX_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
-            IVX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_flood_resident, NT, 0));
-            const char *e = getenv("IVX_FLOOD_RES_PER_CU"); // workgroups per compute unit (A/B; never more than fit)
-            int want = e ? atoi(e) : 4;
-            if (want < 1) want = 1;
-            res_per_cu = occ < 1 ? 0 : (want < occ ? want : occ);
-            ncu = n > 0 ? n : 1;
-        }
-        if (res_per_cu > 0) {
-            const int64_t cap = (int64_t)res_per_cu * ncu;
-            const unsigned rgrid = (unsigned)(t.ntiles < cap ? t.ntiles : cap);
-            const bool ccl_cap = ivx::ccl_supported(p->strct_bits);
-            ResCtl *ctl = (ResCtl *)(cnt + RES_CTL_AT);
-            hipLaunchKernelGGL(k_flood_resident, dim3(rgrid), dim3(NT), 0, st, t, (const unsigned long long *)cand,
-                               (unsigned long long *)reached, list[0], list[1], cnt, dirty[0], dirty[1], ctl,
-                               (unsigned long long *)line, (unsigned int)tag, (unsigned int)RING,
-                               ccl_cap ? (unsigned int)CCL_ESCAPE_ROUNDS : 0x00ffffffu, max_spins, arm.word, arm.value, arm.below);
-            IVX_LAUNCH_CHECK();
-            arm.word = nullptr; // the launch opens the gate itself
-            {
-                std::lock_guard<std::mutex> lk(g_res_mu);
-                g_res_pending[scratch_] = ResPending{line, tag, ccl_cap};
-            }
-            if (resident == 1) return IVX_OK; // the caller collects the result (ivx_dev_flood_wait)
-            return flood_wait_impl(p, cand, reached, scratch_, rounds, nullptr, stream);
-        }
-    }
     const unsigned grid_max = round_grid_cap(t);
     // The rounds queued ahead are sized by the newest list length the host has seen: the lists shrink towards the end, and
     // dispatching 1536 workgroups that find nothing costs ~3 us more per round than dispatching 128 (a list that turns out
@@ -1945,9 +1720,9 @@ static bool fused_start(const Tiles &t, int64_t nseeds) {
 // clear + seed + run in one call: the flood of `seeds` over `cand` into a plane whose old contents are dead.  With at most
 // 16 seeds and a standard structuring element the clearing and the seeding ride on the coarse pass (three launches before
 // the rounds instead of five, no separate pass over the plane); otherwise the three calls run one after the other.
-static int flood_grow_impl(const ivx_flood_plan *p, int dtype, const void *data, double t0, double t1,
-                           const int64_t *seeds_xyz, int64_t nseeds, uint64_t *cand, uint64_t *reached, void *scratch_,
-                           int *rounds, void *stream, int resident) {
+extern "C" int ivx_dev_flood_grow(const ivx_flood_plan *p, int dtype, const void *data, double t0, double t1,
+                                  const int64_t *seeds_xyz, int64_t nseeds, uint64_t *cand, uint64_t *reached, void *scratch_,
+                                  int *rounds, void *stream) {
     Tiles t;
     int rc = make_tiles(p, &t);
     if (rc) return rc;
@@ -1961,7 +1736,7 @@ static int flood_grow_impl(const ivx_flood_plan *p, int dtype, const void *data,
     if (!fused_start(t, nseeds)) {
         if ((rc = ivx_dev_flood_clear(p, reached, scratch_, stream))) return rc;
         if ((rc = ivx_dev_flood_seed(p, dtype, data, t0, t1, seeds_xyz, nseeds, cand, reached, scratch_, stream))) return rc;
-        return flood_run_impl(p, cand, ivx::FLOOD_SYMMETRIC, reached, scratch_, rounds, stream, nullptr, resident);
+        return flood_run_impl(p, cand, ivx::FLOOD_SYMMETRIC, reached, scratch_, rounds, stream);
     }
     ivx::ccl_invalidate(scratch_);
     Fresh f;
@@ -1972,7 +1747,7 @@ static int flood_grow_impl(const ivx_flood_plan *p, int dtype, const void *data,
     f.sp.n = (int)nseeds;
     for (int64_t n = 0; n < nseeds; n++)
         for (int q = 0; q < 3; q++) f.sp.xyz[n][q] = seeds_xyz[3 * n + q];
-    return flood_run_impl(p, cand, ivx::FLOOD_SYMMETRIC, reached, scratch_, rounds, stream, &f, resident);
+    return flood_run_impl(p, cand, ivx::FLOOD_SYMMETRIC, reached, scratch_, rounds, stream, &f);
 }
 extern "C" int ivx_dev_flood_visits(const ivx_flood_plan *p, const void *scratch_, uint32_t out[2], void *stream) {
     IVX_REQUIRE(scratch_ && out, IVX_EINVAL, "flood_visits: NULL argument");
@@ -2012,30 +1787,6 @@ extern "C" int ivx_flood_describe(const ivx_flood_plan *p, int64_t nseeds, int32
     out[6] = (int32_t)round_grid_cap(t);
     out[7] = (int32_t)t.ntiles;
     return IVX_OK;
-}
-extern "C" int ivx_dev_flood_grow(const ivx_flood_plan *p, int dtype, const void *data, double t0, double t1,
-                                  const int64_t *seeds_xyz, int64_t nseeds, uint64_t *cand, uint64_t *reached, void *scratch_,
-                                  int *rounds, void *stream) {
-    return flood_grow_impl(p, dtype, data, t0, t1, seeds_xyz, nseeds, cand, reached, scratch_, rounds, stream, -1);
-}
-// ivx_dev_flood_grow that may return right behind a resident launch (k_flood_resident): *pending = 1 then, and the flood is
-// complete for everything queued on `stream` after this call EXCEPT when the launch ends early (round cap, timed-out
-// barrier) -- ivx_dev_flood_wait tells, finishes the flood, and the caller queues its dependent work again.  The point: the
-// host is not in the loop while the flood runs, so the next stage is already in the queue when the last round ends.
-extern "C" int ivx_dev_flood_grow_async(const ivx_flood_plan *p, int dtype, const void *data, double t0, double t1,
-                                        const int64_t *seeds_xyz, int64_t nseeds, uint64_t *cand, uint64_t *reached,
-                                        void *scratch_, int *rounds, int *pending, void *stream) {
-    IVX_REQUIRE(pending, IVX_EINVAL, "flood_grow_async: NULL argument");
-    *pending = 0;
-    const int rc = flood_grow_impl(p, dtype, data, t0, t1, seeds_xyz, nseeds, cand, reached, scratch_, rounds, stream, 1);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(g_res_mu);
-    *pending = g_res_pending.count(scratch_) ? 1 : 0;
-    return IVX_OK;
-}
-extern "C" int ivx_dev_flood_wait(const ivx_flood_plan *p, const uint64_t *cand, uint64_t *reached, void *scratch_, int *rounds,
-                                  int *late, void *stream) {
-    return flood_wait_impl(p, cand, reached, scratch_, rounds, late, stream);
 }
 
 extern "C" int ivx_dev_flood_run_edges(const ivx_flood_plan *p, const uint64_t *edges, uint64_t *reached, void *scratch_,

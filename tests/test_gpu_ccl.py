@@ -1,6 +1,6 @@
 """The run-based union-find of csrc/k_ccl.hip past one tile (8 words x 8 rows x 4 slices), one word and one scan block
 (4096 words): Mask.fill_holes_auto, which always goes through it, and the region grows that take it (IVX_FLOOD_MODE=ccl,
-the escape after 48 frontier rounds, the capped resident launch).  Every input is 1030 or 1100 voxels wide -- three
+the escape after 48 frontier rounds, from the host mirror and from DeviceVolume.region_grow).  Every input is 1030 or 1100 voxels wide -- three
 tiles along x, a partial last word -- and comes from tests/_ccl_ref.py, whose cases tests/test_ccl_cases_host.py checks
 on the host.  The results are integers: every comparison is bit for bit, against the numpy / scipy recipe of
 _ccl_ref.py AND the oracle."""
@@ -180,33 +180,31 @@ def test_union_find_engine_from_the_start_in_a_fresh_process(ivxlib, oracle):
     assert "ivx flood: round" in inside and "ivx flood: round" not in head + tail, r.stderr[-2000:]
 
 
-_RESIDENT_CHILD = _CHILD_HEAD + (
-    "from invesalius3_amd.device import DeviceVolume\n"
-    "img = R.serpentine()\n"
-    "vol = DeviceVolume(img, spacing=(1.0, 1.0, 1.0))\n"
-    "for conn in (1, 3):\n"
-    "    s = generate_binary_structure(3, conn).astype(np.uint8)\n"
-    "    for _ in range(2):\n"
-    "        vol.zero_out_mask(); vol.threshold(1, 1)\n"
-    "        rounds = vol.region_grow([(0, 0, 1)], 1, 1, s, fill=1, select_value=254)\n"
-    "        assert rounds >= 1, rounds\n"
-    "    mask = np.where(img == 1, 255, 0).astype(np.uint8)\n"
-    "    out = np.zeros(img.shape, np.uint8)\n"
-    "    orc.floodfill_threshold(img, [(0, 0, 1)], 1, 1, 1, s, out)\n"
-    "    mask[out.astype(bool)] = 254\n"
-    "    assert np.array_equal(vol.download_out_mask(), out), conn\n"
-    "    assert np.array_equal(vol.download_mask(), mask), conn\n"
-    "    assert (mask == 254).sum() > 30 * 1100 and (mask[2] == 255).any() == (conn == 1), conn\n"
-    "vol.close()\n"
-    "print('resident-ok')\n")
-
-
-def test_capped_resident_launch_is_completed_by_the_union_find(ivxlib, oracle):
-    """IVX_FLOOD_RESIDENT=1 in a fresh process, DeviceVolume.region_grow on the corridor: the resident launch stops at
-    its round cap, ivx_dev_flood_wait completes the flood with the union-find engine and reports it as late, and the
-    caller queues `mask[reached] = 254` once more: same mask, same out_mask as the oracle, a positive round count.  The
-    trace names the launch's status: 2 = ended at the cap."""
-    env = dict(os.environ, IVX_FLOOD_RESIDENT="1", IVX_FLOOD_TRACE="1")
-    r = subprocess.run([sys.executable, "-c", _RESIDENT_CHILD], env=env, capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "resident-ok" in r.stdout, r.stdout + r.stderr
-    assert "resident launch ended with status 2" in r.stderr, r.stderr[-2000:]
+def test_region_grow_on_the_corridor_is_completed_by_the_union_find(ivxlib, oracle):
+    """DeviceVolume.region_grow on the corridor, twice per structure: the host escapes to the union-find engine once it has
+    seen round 48 start and adds one to the round count (CCL_ESCAPE_ROUNDS in flood_run_impl), and `mask[reached] = 254`
+    is queued behind the completed flood: same mask, same out_mask as the oracle.  Whether the 26-neighbour flood needs 48
+    rounds here as well is not asserted: the escape has to show once over the loop."""
+    from invesalius3_amd.device import DeviceVolume
+    img = R.serpentine()
+    vol = DeviceVolume(img, spacing=(1.0, 1.0, 1.0))
+    seen = []
+    try:
+        for conn in (1, 3):
+            s = generate_binary_structure(3, conn).astype(np.uint8)
+            for _ in range(2):
+                vol.zero_out_mask()
+                vol.threshold(1, 1)
+                rounds = vol.region_grow([(0, 0, 1)], 1, 1, s, fill=1, select_value=254)
+                assert rounds >= 1, rounds
+                seen.append(rounds)
+            mask = np.where(img == 1, 255, 0).astype(np.uint8)
+            out = np.zeros(img.shape, np.uint8)
+            oracle.floodfill_threshold(img, [(0, 0, 1)], 1, 1, 1, s, out)
+            mask[out.astype(bool)] = 254
+            assert np.array_equal(vol.download_out_mask(), out), conn
+            assert np.array_equal(vol.download_mask(), mask), conn
+            assert (mask == 254).sum() > 30 * 1100 and (mask[2] == 255).any() == (conn == 1), conn
+    finally:
+        vol.close()
+    assert max(seen) >= 49, seen
