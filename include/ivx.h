@@ -177,7 +177,14 @@ int ivx_image_ranges_bytes(int64_t dz, int64_t dy, int64_t dx, size_t *nbytes);
 int ivx_dev_image_ranges_i16(const int16_t *img, int64_t dz, int64_t dy, int64_t dx, uint32_t *ranges, void *stream);
 int ivx_dev_threshold_i16_bits_ranges(const int16_t *img, int64_t dz, int64_t dy, int64_t dx, int lo, int hi,
                                       uint8_t *mask, uint64_t *bits, uint32_t *ranges, int mode, void *stream);
-/* Host form.  `mask` points at the FULL (dz+1,dy+1,dx+1) matrix of invesalius/data/mask.py:422-431
+/* The plane-only forms of ivx_dev_threshold_i16_bits and ivx_dev_threshold_i16_bits_ranges: the same plane (and, in build
+ * mode, the same records), no mask.  For a caller that keeps "mask == 255 * plane" as a note and has the bytes written later,
+ * by ivx_dev_mask_from_planes.  Same argument rules without `mask`. */
+int ivx_dev_threshold_i16_plane(const int16_t *img, int64_t dz, int64_t dy, int64_t dx, int lo, int hi, uint64_t *bits,
+                                void *stream);
+int ivx_dev_threshold_i16_plane_ranges(const int16_t *img, int64_t dz, int64_t dy, int64_t dx, int lo, int hi, uint64_t *bits,
+                                       uint32_t *ranges, int mode, void *stream);
+/* Host form. `mask` points at the FULL (dz+1,dy+1,dx+1) matrix of invesalius/data/mask.py:422-431
  * (flag cells in the index-0 planes); strides in bytes.  With honour_flags the per-slice flag
  * mask[n,0,0] is tested and then set to 1 (slice_.py:1761-1767); without it every slice is
  * processed and the flag forced to 1 (slice_.py:1240-1247). */
@@ -693,6 +700,12 @@ int ivx_dev_flood_apply(const ivx_flood_plan *p, const uint64_t *reached, int dt
  * inside, else 0), a chunk without one is left alone.  dx % 64 == 0 and a 16-byte aligned mask only (IVX_EINVAL). */
 int ivx_dev_flood_apply_levels(const ivx_flood_plan *p, const uint64_t *reached, const uint64_t *inside_bits, uint8_t *mask,
                                int v_in, int v_sel, void *stream);
+/* Every byte of a uint8 mask from its planes: v_sel where `reached` has a bit (NULL: nowhere), else v_in where `inside_bits`
+ * has one, else 0.  Nothing of the mask is read and every 16-voxel chunk is written, so the mask may hold anything before:
+ * after a plane-only threshold this is the threshold's mask (reached = NULL) or the mask after `mask[reached] = v_sel`.
+ * dx % 64 == 0, a 16-byte aligned mask and 8-byte aligned planes only (IVX_EINVAL). */
+int ivx_dev_mask_from_planes(const ivx_flood_plan *p, const uint64_t *inside_bits, const uint64_t *reached, uint8_t *mask,
+                             int v_in, int v_sel, void *stream);
 /* both writes of a GUI region-grow in one pass: out[v] = fill and mask[v] = select where reached
  * (floodfill_threshold's out + `mask[out_mask.astype(bool)] = 254`, styles.py:3200-3214) */
 int ivx_dev_flood_apply2(const ivx_flood_plan *p, const uint64_t *reached, uint8_t *out, int fill, uint8_t *mask,

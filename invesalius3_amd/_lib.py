@@ -69,6 +69,11 @@ def _declare(lib):
                        ("ivx_dev_image_ranges_i16", [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
                        ("ivx_dev_threshold_i16_bits_ranges", [c_vp, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp,
                                                               ctypes.c_int, c_vp]),
+                       # the plane-only thresholds and the pass that writes the mask's bytes from its planes
+                       ("ivx_dev_threshold_i16_plane", [c_vp, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
+                       ("ivx_dev_threshold_i16_plane_ranges", [c_vp, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
+                                                               ctypes.c_int, c_vp]),
+                       ("ivx_dev_mask_from_planes", [ctypes.POINTER(FloodPlan), c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp]),
                        ("ivx_dev_flood_candidates_ranges", [ctypes.POINTER(FloodPlan), c_vp, ctypes.c_double, ctypes.c_double, c_vp,
                                                             ctypes.c_int, ctypes.c_double, c_vp, c_vp, c_vp])):
         fn = getattr(lib, name)

@@ -1188,7 +1188,10 @@ __global__ __launch_bounds__(256) void k_flood_apply16(const uint16_t *__restric
 // k_flood_apply16 for a mask whose bytes are KNOWN: v_in where `inside` (same layout as `reached`) has a bit, 0 elsewhere.  Every
 // byte of a chunk with a reached bit is then a function of the two bit fields -- v_sel where reached, else v_in where inside,
 // else 0 -- so the lane loads both fields together and stores; no byte of `out` is read (k_flood_apply16 loads a partial
-// chunk's 16 bytes after its bits have arrived: a second, dependent round trip).  Chunks without a reached bit are not written.
+// chunk's 16 bytes after its bits have arrived: a second, dependent round trip).  Chunks without a reached bit are not written
+// -- unless ALL: then `out` holds nothing yet (a plane-only threshold) and every chunk is written, `reached` may be NULL (no
+// bit), and a wave's four stores are 1 KiB contiguous each.
+template <bool ALL>
 __global__ __launch_bounds__(256) void k_flood_apply_levels16(const uint16_t *__restrict__ reached, const uint16_t *__restrict__ inside,
                                                               int64_t nchunks, uint4 *__restrict__ out, uint8_t v_in, uint8_t v_sel) {
     const int64_t stride = (int64_t)gridDim.x * 1024;
@@ -1198,12 +1201,12 @@ __global__ __launch_bounds__(256) void k_flood_apply_levels16(const uint16_t *__
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             const int64_t i = i0 + u * 256;
-            m[u] = i < nchunks ? reached[i] : 0u;
+            m[u] = i < nchunks && (!ALL || reached) ? reached[i] : 0u;
             b[u] = i < nchunks ? inside[i] : 0u;
         }
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-            if (!m[u]) continue;
+            if (ALL ? i0 + u * 256 >= nchunks : !m[u]) continue;
             // bit e of four -> 0xff in byte e (the products' bits e + 7 k are all different: no carries)
             auto bytes = [](unsigned int bits4) { return ((bits4 * 0x00204081u) & 0x01010101u) * 0xffu; };
             auto word = [&](unsigned int r4, unsigned int i4) {
@@ -1930,7 +1933,26 @@ extern "C" int ivx_dev_flood_apply_levels(const ivx_flood_plan *p, const uint64_
     const int64_t nchunks = t.dz * t.dy * t.dx / 16;
     if (!nchunks) return IVX_OK;
     const int64_t blocks = ivx::cdiv(nchunks, 1024);
-    hipLaunchKernelGGL(k_flood_apply_levels16, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, ivx::S(stream),
+    hipLaunchKernelGGL(k_flood_apply_levels16<false>, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, ivx::S(stream),
+                       (const uint16_t *)reached, (const uint16_t *)inside_bits, nchunks, (uint4 *)mask, (uint8_t)v_in, (uint8_t)v_sel);
+    IVX_LAUNCH_CHECK();
+    return IVX_OK;
+}
+
+// the whole mask from its planes: v_sel where reached (NULL: nowhere), else v_in where inside, else 0 -- every byte is written
+extern "C" int ivx_dev_mask_from_planes(const ivx_flood_plan *p, const uint64_t *inside_bits, const uint64_t *reached, uint8_t *mask,
+                                        int v_in, int v_sel, void *stream) {
+    Tiles t;
+    int rc = make_tiles(p, &t);
+    if (rc) return rc;
+    IVX_REQUIRE(inside_bits && mask, IVX_EINVAL, "mask_from_planes: null plane or mask");
+    IVX_REQUIRE(t.dx % 64 == 0 && ((uintptr_t)mask & 15) == 0 && (((uintptr_t)inside_bits | (uintptr_t)reached) & 7) == 0, IVX_EINVAL,
+                "mask_from_planes: rows of whole 64-voxel words, a 16-byte aligned mask and 8-byte aligned planes only");
+    IVX_REQUIRE(v_in >= 0 && v_in <= 255 && v_sel >= 0 && v_sel <= 255, IVX_EINVAL, "mask_from_planes: levels are bytes");
+    const int64_t nchunks = t.dz * t.dy * t.dx / 16;
+    if (!nchunks) return IVX_OK;
+    const int64_t blocks = ivx::cdiv(nchunks, 1024);
+    hipLaunchKernelGGL(k_flood_apply_levels16<true>, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, ivx::S(stream),
                        (const uint16_t *)reached, (const uint16_t *)inside_bits, nchunks, (uint4 *)mask, (uint8_t)v_in, (uint8_t)v_sel);
     IVX_LAUNCH_CHECK();
     return IVX_OK;

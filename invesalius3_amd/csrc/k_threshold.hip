@@ -135,6 +135,9 @@ __global__ __launch_bounds__(256) void k_threshold16_bits_build(const short8_t *
 // Measured: 193 MB instead of 422 MB, but 54 us instead of 65 -- the stores alone take 21 us and the sparse
 // reads of the mixed lines add their own time to that whatever the kernel's shape (several chunks in flight per lane, the
 // mixed words compacted through LDS and non-temporal mask stores all measured the same or slower), so this is the plain form.
+// Since the two halves add, the resident step no longer runs them in one kernel: k_threshold16_plane_use below is this kernel
+// without the mask (29.7 us), and the mask's bytes are written by the region growing's apply.  This form stays for callers
+// that want mask and plane from one call, for volumes past the Infinity Cache that no region growing follows, and for A/B.
 __global__ __launch_bounds__(256) void k_threshold16_bits_use(const short8_t *__restrict__ img, uchar16_t *__restrict__ mask,
                                                               uint16_t *__restrict__ bits, const unsigned *__restrict__ ranges,
                                                               int64_t nchunks, int lo, int hi) {
@@ -171,6 +174,69 @@ __global__ __launch_bounds__(256) void k_threshold16_bits_use(const short8_t *__
             }
         }
         mask[c] = r;
+        bits[c] = (uint16_t)m;
+        if (cn >= nchunks) break;
+        c = cn;
+        rec = rec_next;
+    }
+}
+
+// ---- plane-only forms ----------------------------------------------------------------------------------------------
+// The same three kernels without the dense mask: the caller keeps "mask == 255 * plane" as a note and has the bytes written
+// by the pass that has to write mask bytes anyway (ivx_dev_mask_from_planes, k_flood.hip).  The 134 MB of stores that the
+// 512^3 step's threshold spent on bytes nobody read before the flood rewrote them are gone from this pass.  Measured at 512^3
+// (profiles/mask_deferred_ab.md): use mode 55.0 -> 29.7 us, build mode 70.3 -> 58.6 us; the apply that now writes every chunk
+// 12.3 -> 22.2 us.
+__device__ __forceinline__ unsigned chunk_bits(const short8_t a, const short8_t b, int lo, int hi) {
+    unsigned m = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const bool in0 = (int)a[i] >= lo && (int)a[i] <= hi, in1 = (int)b[i] >= lo && (int)b[i] <= hi;
+        m |= (in0 ? 1u : 0u) << i;
+        m |= (in1 ? 1u : 0u) << (8 + i);
+    }
+    return m;
+}
+
+// k_threshold16_bits (BUILD = false) and k_threshold16_bits_build (BUILD = true) without the mask
+template <bool BUILD>
+__global__ __launch_bounds__(256) void k_threshold16_plane(const short8_t *__restrict__ img, uint16_t *__restrict__ bits,
+                                                           unsigned *__restrict__ ranges, int64_t nchunks, int lo, int hi) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < nchunks; c += stride) {
+        const short8_t a = __builtin_nontemporal_load(&img[2 * c]);
+        const short8_t b = __builtin_nontemporal_load(&img[2 * c + 1]);
+        bits[c] = (uint16_t)chunk_bits(a, b, lo, hi);
+        if (BUILD) {
+            const unsigned rec = word_record(a, b);
+            if ((c & 3) == 0) ranges[c >> 2] = rec;
+        }
+    }
+}
+
+// k_threshold16_bits_use without the mask: 4 B of record per word, the mixed words' lines, 2 B of plane per chunk
+__global__ __launch_bounds__(256) void k_threshold16_plane_use(const short8_t *__restrict__ img, uint16_t *__restrict__ bits,
+                                                               const unsigned *__restrict__ ranges, int64_t nchunks, int lo,
+                                                               int hi) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= nchunks) return;
+    unsigned rec = ranges[c >> 2];
+    for (;;) {
+        const int64_t cn = c + stride;
+        unsigned rec_next = 0;
+        if (cn < nchunks) rec_next = ranges[cn >> 2];
+        const int mn = (int)(short)(rec & 0xffffu), mx = (int)(short)(rec >> 16);
+        unsigned m;
+        if (mn >= lo && mx <= hi) {
+            m = 0xffffu;
+        } else if (mx < lo || mn > hi) {
+            m = 0;
+        } else {
+            const short8_t a = __builtin_nontemporal_load(&img[2 * c]);
+            const short8_t b = __builtin_nontemporal_load(&img[2 * c + 1]);
+            m = chunk_bits(a, b, lo, hi);
+        }
         bits[c] = (uint16_t)m;
         if (cn >= nchunks) break;
         c = cn;
@@ -291,6 +357,41 @@ extern "C" int ivx_dev_threshold_i16_bits_ranges(const int16_t *img, int64_t dz,
     else
         hipLaunchKernelGGL(k_threshold16_bits_use, dim3(ranges_grid(nchunks)), dim3(256), 0, ivx::S(stream),
                            (const short8_t *)img, (uchar16_t *)mask, (uint16_t *)bits, (const unsigned *)ranges, nchunks, lo, hi);
+    IVX_LAUNCH_CHECK();
+    return IVX_OK;
+}
+
+extern "C" int ivx_dev_threshold_i16_plane(const int16_t *img, int64_t dz, int64_t dy, int64_t dx, int lo, int hi, uint64_t *bits,
+                                           void *stream) {
+    IVX_REQUIRE(dz >= 0 && dy >= 0 && dx >= 0, IVX_EINVAL, "threshold: negative shape");
+    IVX_REQUIRE(dx % 64 == 0 && (((uintptr_t)img | (uintptr_t)bits) & 15) == 0, IVX_EINVAL,
+                "threshold_plane: needs dx %% 64 == 0 and 16-byte aligned buffers");
+    const int64_t n = dz * dy * dx;
+    if (n == 0) return IVX_OK;
+    IVX_REQUIRE(img && bits, IVX_EINVAL, "threshold_plane: null argument");
+    const int64_t nchunks = n / 16;
+    hipLaunchKernelGGL(k_threshold16_plane<false>, dim3(ranges_grid(nchunks)), dim3(256), 0, ivx::S(stream), (const short8_t *)img,
+                       (uint16_t *)bits, (unsigned *)nullptr, nchunks, lo, hi);
+    IVX_LAUNCH_CHECK();
+    return IVX_OK;
+}
+
+extern "C" int ivx_dev_threshold_i16_plane_ranges(const int16_t *img, int64_t dz, int64_t dy, int64_t dx, int lo, int hi,
+                                                  uint64_t *bits, uint32_t *ranges, int mode, void *stream) {
+    IVX_REQUIRE(dz >= 0 && dy >= 0 && dx >= 0, IVX_EINVAL, "threshold: negative shape");
+    IVX_REQUIRE(dx % 64 == 0 && (((uintptr_t)img | (uintptr_t)bits) & 15) == 0 && ((uintptr_t)ranges & 3) == 0, IVX_EINVAL,
+                "threshold_plane_ranges: needs dx %% 64 == 0, 16-byte aligned buffers and 4-byte aligned records");
+    IVX_REQUIRE(mode == IVX_RANGES_BUILD || mode == IVX_RANGES_USE, IVX_EINVAL, "threshold_plane_ranges: mode %d", mode);
+    const int64_t n = dz * dy * dx;
+    if (n == 0) return IVX_OK;
+    IVX_REQUIRE(img && bits && ranges, IVX_EINVAL, "threshold_plane_ranges: null argument");
+    const int64_t nchunks = n / 16;
+    if (mode == IVX_RANGES_BUILD)
+        hipLaunchKernelGGL(k_threshold16_plane<true>, dim3(ranges_grid(nchunks)), dim3(256), 0, ivx::S(stream),
+                           (const short8_t *)img, (uint16_t *)bits, (unsigned *)ranges, nchunks, lo, hi);
+    else
+        hipLaunchKernelGGL(k_threshold16_plane_use, dim3(ranges_grid(nchunks)), dim3(256), 0, ivx::S(stream),
+                           (const short8_t *)img, (uint16_t *)bits, (const unsigned *)ranges, nchunks, lo, hi);
     IVX_LAUNCH_CHECK();
     return IVX_OK;
 }

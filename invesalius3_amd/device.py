@@ -101,12 +101,13 @@ class DeviceBuffer:
 class TrackedBuffer(DeviceBuffer):
     """A DeviceBuffer that reports every access from outside its owner (`ptr`, and through it upload / zero / at):
     the owner then stops trusting what it derived from the contents (DeviceVolume's inside-bit plane of the mask,
-    the "out_mask is all zero" note).  The owner's own kernels use `raw`."""
+    the "out_mask is all zero" note).  The owner's own kernels use `raw`.  `on_read` is called before a download: an owner
+    that has deferred writing the bytes (DeviceVolume's mask) writes them then, and keeps its notes."""
 
-    def __init__(self, nbytes: int, on_touch):
-        self._on_touch = None
+    def __init__(self, nbytes: int, on_touch, on_read=None):
+        self._on_touch = self._on_read = None
         super().__init__(nbytes)
-        self._on_touch = on_touch
+        self._on_touch, self._on_read = on_touch, on_read
 
     @property
     def ptr(self):
@@ -123,6 +124,8 @@ class TrackedBuffer(DeviceBuffer):
         return self._p
 
     def download(self, shape, dtype, out=None) -> np.ndarray:  # reading changes nothing
+        if self._on_read is not None:
+            self._on_read()
         if out is None:
             out = np.empty(shape, dtype)
         else:
@@ -231,15 +234,19 @@ class DeviceVolume:
         self._gate_armed = False  # armed and no flood has run since (so nobody will open it)
         self._mbits_version = 0   # bumped whenever the inside plane is rewritten
         self._out_pending = None      # fill value of a deferred `out_mask[reached] = fill` (self.reached still holds it)
+        # the mask's bytes in HBM are stale: they are what _mask_levels says of _mbits (and self.reached), not yet written
+        self._mask_pending = False
+        self._defer_pays = True       # the last fused threshold's bytes were (or could have been) written by a flood's apply
         self._fuse = os.environ.get("IVX_NO_FUSE", "") == ""
         self._apply_levels = os.environ.get("IVX_APPLY_LEVELS", "1") != "0"  # (A/B: mask[reached] = v from the bit planes alone)
         self._use_ranges = os.environ.get("IVX_RANGES", "1") != "0"  # (A/B: threshold / candidates from the per-word records)
+        self._mask_defer = os.environ.get("IVX_MASK_DEFER", "1") != "0"  # (A/B: plane-only threshold, mask bytes written later)
         # (min, max) of every 64-voxel x-word of the image (ivx_dev_image_ranges_i16): written by the first fused threshold
         # after the image's bytes changed, read by every later one.  Dropped with the image (_image_touched), like _range_valid.
         self._ranges = None
         self._ranges_valid = False
         self.image = TrackedBuffer(self.n * 2, self._image_touched)
-        self.mask = TrackedBuffer(self.n, self._mask_touched)       # dense interior of mask.matrix[1:,1:,1:]
+        self.mask = TrackedBuffer(self.n, self._mask_touched, self._mask_read)  # dense interior of mask.matrix[1:,1:,1:]
         self.out_mask = TrackedBuffer(self.n, self._out_touched)    # region-growing `out` (styles.py:3190)
         if image is not None:
             self.image.upload_view(image)
@@ -271,11 +278,46 @@ class DeviceVolume:
         self._drop_volren()
 
     def _mask_touched(self):
+        self._mask_read()
         self._mp_cells_valid = False
         self._mbits_valid = False
         self._mbits_range = None
         self._mask_levels = None
         self._mbits_version += 1
+
+    # Two buffers whose bytes follow from bit planes are written when somebody needs them, not when they become known.
+    #
+    # mask: a fused threshold writes the inside plane only and leaves `_mask_pending`: the bytes are 255 * _mbits (in general
+    # what _mask_levels says of _mbits and self.reached), and the 134 MB of a 512^3 mask are stored once per step, by the pass
+    # that has to write mask bytes anyway -- `mask[reached] = v` of the region growing (ivx_dev_mask_from_planes in
+    # _apply_reached) -- or by _materialize_mask().  No public method but surface_prefetch returns with the note set unless
+    # it is a threshold itself: every other one writes all bytes or begins with _materialize_mask(), and so does everything
+    # that reads or hands out the bytes (mask.ptr, mask.download, mask_bytes()).
+    # Deferring pays only where the region growing's pass consumes the note: a pass of its own for the bytes costs more than
+    # the fused kernel's stores once the volume is past the Infinity Cache (2048^3: 1.25 + 2.15 ms against 2.97 ms).  So
+    # `_defer_pays` follows the last threshold's fate -- off when its bytes needed _materialize_mask(), on when a flood's
+    # apply took them (or would have) -- and a threshold that is not expected to pay runs the fused kernel.
+    def _materialize_mask(self):
+        if self._mask_pending:
+            self._defer_pays = False
+            lv = self._mask_levels
+            sel = self.reached.ptr if lv[1] is not None else None
+            with self.timer.span("mask_bytes"):
+                L.check(L.lib().ivx_dev_mask_from_planes(ctypes.byref(self.plan), self._mbits.ptr, sel, self.mask.raw, int(lv[0]),
+                                                         int(lv[0] if lv[1] is None else lv[1]), self.stream), "mask_from_planes")
+            self._mask_pending = False
+
+    def _mask_read(self):
+        """somebody outside the pipeline's stream is about to look at the mask's bytes (or to write some of them)"""
+        if self._mask_pending:
+            self._materialize_mask()
+            self.sync()  # (uploads and downloads do not run on self.stream)
+
+    def mask_bytes(self) -> ctypes.c_void_p:
+        """the mask's device pointer for a reader of the bytes that works on `self.stream`: written if they were pending,
+        notes kept (`mask.ptr` is for writers: it materializes too, then drops what the pipeline knew of the bytes)"""
+        self._materialize_mask()
+        return self.mask.raw
 
     # out_mask is the reference's throw-away `np.zeros_like` of styles.py:3190: the flood writes `fill` into it and the
     # caller turns it into `mask[out_mask.astype(bool)] = 254`.  The pipeline keeps it as what the flood really produces
@@ -298,17 +340,20 @@ class DeviceVolume:
 
     def zero_out_mask(self):
         """out_mask = zeros (the np.zeros of styles.py:3190)"""
+        self._materialize_mask()
         if not self._out_bytes_zero:
             L.check(L.lib().ivx_memset(self.out_mask.raw, 0, ctypes.c_size_t(self.n), self.stream))
         self._out_bytes_zero, self._out_pending = True, None
 
     def sync(self):
+        self._materialize_mask()
         L.check(L.lib().ivx_stream_synchronize(self.stream))
 
     def close(self):
         if getattr(self, "stream", None) is None:
             return  # already closed (or never fully built)
         self._out_pending = None
+        self._mask_pending = False
         self._prefetch = None
         if getattr(self, "flood_scratch", None) is not None and self.flood_scratch.ptr is not None:
             L.lib().ivx_dev_flood_disarm_gate(self.flood_scratch.ptr)  # an unconsumed arm must not outlive the buffers
@@ -346,10 +391,12 @@ class DeviceVolume:
             pass
 
     def download_mask(self, out: np.ndarray | None = None) -> np.ndarray:
+        self._materialize_mask()
         self.sync()
         return self.mask.download(self.shape, np.uint8, out)
 
     def download_out_mask(self) -> np.ndarray:
+        self._materialize_mask()
         self._materialize_out()
         self.sync()
         return self.out_mask.download(self.shape, np.uint8)
@@ -359,25 +406,38 @@ class DeviceVolume:
         """mask = 255 where lo <= image <= hi else 0 (with the preserve rule of do_threshold_to_a_slice when asked).
         When the rows are whole 64-voxel words the same pass also writes the mask's inside-bit plane (1/8 B/voxel
         more): it IS the candidate plane of a region growing with the same thresholds into a zero out_mask, and the
-        inside plane of marching cubes at iso 127 -- both then skip their own pass over the volume."""
+        inside plane of marching cubes at iso 127 -- both then skip their own pass over the volume.
+        That pass writes the plane ONLY while a region growing is expected to follow (`_defer_pays`): the mask's bytes are
+        then pending and the flood's `mask[reached] = v` writes all of them (see _materialize_mask)."""
         lib = L.lib()
         self._join_prefetch()  # a count still reading the plane must not see it change
         if self._fuse and not preserve and self.dx % 64 == 0:
             self._mbits_version += 1
             self._mp_cells_valid = False
+            dims = (c64(self.dz), c64(self.dy), c64(self.dx), int(lo), int(hi))
+            defer = self._mask_defer and self._defer_pays
             if self._use_ranges:
                 # the first threshold of an image leaves the records behind, every later one reads them and the mixed words only
                 mode = 1 if self._ranges_valid else 0  # IVX_RANGES_USE / IVX_RANGES_BUILD
-                L.check(lib.ivx_dev_threshold_i16_bits_ranges(self.image.raw, c64(self.dz), c64(self.dy), c64(self.dx), int(lo), int(hi),
-                                                              self.mask.raw, self._mbits.ptr, self._ranges_buffer().ptr, mode,
-                                                              self.stream), "threshold")
+                if defer:
+                    L.check(lib.ivx_dev_threshold_i16_plane_ranges(self.image.raw, *dims, self._mbits.ptr, self._ranges_buffer().ptr,
+                                                                   mode, self.stream), "threshold")
+                else:
+                    L.check(lib.ivx_dev_threshold_i16_bits_ranges(self.image.raw, *dims, self.mask.raw, self._mbits.ptr,
+                                                                  self._ranges_buffer().ptr, mode, self.stream), "threshold")
                 self._ranges_valid = True
+            elif defer:
+                L.check(lib.ivx_dev_threshold_i16_plane(self.image.raw, *dims, self._mbits.ptr, self.stream), "threshold")
             else:
-                L.check(lib.ivx_dev_threshold_i16_bits(self.image.raw, c64(self.dz), c64(self.dy), c64(self.dx), int(lo), int(hi),
-                                                       self.mask.raw, self._mbits.ptr, self.stream), "threshold")
+                L.check(lib.ivx_dev_threshold_i16_bits(self.image.raw, *dims, self.mask.raw, self._mbits.ptr, self.stream), "threshold")
+            # every byte is overwritten: an earlier pending note is dropped unwritten; with deferral this one takes its place
+            self._mask_pending = defer
             self._mbits_valid, self._mbits_range = True, (int(lo), int(hi))
             self._mask_levels = (255, None)  # mask == 255 * plane, byte for byte
             return
+        if preserve:
+            self._materialize_mask()  # the preserve rule reads the bytes
+        self._mask_pending = False
         L.check(lib.ivx_dev_threshold_i16(self.image.raw, c64(self.dz), c64(self.dy), c64(self.dx), int(lo), int(hi),
                                           int(bool(preserve)), None, self.mask.raw, self.stream), "threshold")
         self._mask_touched()
@@ -394,6 +454,7 @@ class DeviceVolume:
     def lut_image_255(self, ww, wl) -> DeviceBuffer:
         """get_LUT_value_255(image, ww, wl) (imagedata_utils.py:540-552) as a resident int16 volume: the image the
         "dynamic" and "confidence" region-growing modes flood when use_ww_wl is set (styles.py:3166-3171, 3222-3225)."""
+        self._materialize_mask()
         buf = DeviceBuffer(self.n * 2)
         L.check(L.lib().ivx_dev_lut_i16(self.image.raw, c64(self.n), ctypes.c_double(float(ww)), ctypes.c_double(float(wl)),
                                         1, buf.ptr, self.stream), "lut_image_255")
@@ -427,6 +488,7 @@ class DeviceVolume:
 
     def flood_visits(self):
         """(tile visits, length of the first round's list) of the last flood of this volume (L.flood_visits)"""
+        self._materialize_mask()
         return L.flood_visits(self.plan, self.flood_scratch.ptr, self.stream)
 
     def _before_flood(self):
@@ -434,6 +496,7 @@ class DeviceVolume:
         note that describes the mask's bytes through that plane dies with it"""
         self._materialize_out()
         if self._mask_levels is not None and self._mask_levels[1] is not None:
+            self._materialize_mask()
             self._mask_levels = None
 
     def _candidate_plane(self, image, t0, t1, fill):
@@ -464,9 +527,20 @@ class DeviceVolume:
         if select_value is not None:
             self._mp_cells_valid = False
         defer = self._out_logically_zero() and int(fill) != 0
+        levels = select_value is not None and self._mask_levels == (255, None) and self._mbits_valid and self._apply_levels
+        if not (defer and levels):
+            self._materialize_mask()
+        else:
+            self._defer_pays = True  # a threshold's mask met the flood's apply untouched: the next one defers (again)
         if defer:
             self._out_pending = int(fill)  # bytes stay zero; self.reached carries the result until it is needed
-            if select_value is not None and self._mask_levels == (255, None) and self._mbits_valid and self._apply_levels:
+            if levels and self._mask_pending:
+                # the mask's bytes are still to be written: this pass writes all of them, the selected ones as select_value
+                with self.timer.span("mask_bytes"):
+                    L.check(lib.ivx_dev_mask_from_planes(p, self._mbits.ptr, self.reached.ptr, self.mask.raw, 255, int(select_value),
+                                                         st), "mask_from_planes")
+                self._mask_pending = False
+            elif levels:
                 # mask == 255 * plane, byte for byte: a touched chunk's bytes follow from the two bit planes, no byte is read
                 L.check(lib.ivx_dev_flood_apply_levels(p, self.reached.ptr, self._mbits.ptr, self.mask.raw, 255, int(select_value), st),
                         "flood_apply_levels")
@@ -499,6 +573,7 @@ class DeviceVolume:
         SURVEY quirk Q4).  Statistics are exact integer sums on the GPU; mean/std are formed in float64 on the host
         (std = sqrt(E[x^2] - mean^2): differs from numpy's two-pass value by rounding only, far below the int()
         truncation the wrapper applies to t0/t1)."""
+        self._materialize_mask()
         lib = L.lib()
         x, y, z = (int(v) for v in seed_xyz)
         sel = np.zeros(self.shape, np.uint8)
@@ -527,6 +602,7 @@ class DeviceVolume:
         return rounds
 
     def reached_count(self) -> int:
+        self._materialize_mask()
         n = ctypes.c_int64(0)
         L.check(L.lib().ivx_dev_flood_count(ctypes.byref(self.plan), self.reached.ptr, ctypes.byref(n), self.stream))
         return n.value
@@ -677,6 +753,7 @@ class DeviceVolume:
         With download=False the count may come back while the triangle list and the emit are still queued or running: the
         soup in `self._tris` is complete in stream order.  Whatever is queued on `self.stream` afterwards (the next threshold,
         another surface) is ordered behind it by the stream; call sync() before reading the buffer from anywhere else."""
+        self._materialize_mask()
         lib = L.lib()
         if params is not None:
             p = params
@@ -749,6 +826,7 @@ class DeviceVolume:
                                params: L.McParams | None = None, z0: int = 0):
         """Same surface with coincident points merged (ivx.h "indexed surface").  Returns (n_verts, n_tris), or the
         (V,3) float32 / (T,3) int32 arrays when download=True; the device buffers stay in self._verts / self._faces."""
+        self._materialize_mask()
         lib = L.lib()
         if params is not None:
             p = params
@@ -800,6 +878,7 @@ class DeviceVolume:
         `ivx_dev_watershed_sk` for "Watershed", the GUI's default) -> ``mask`` gets 253 where the flood says 1 and 2 where
         it says 2 (only over cells that hold 0 / 2 / 253, or over everything after zeroing with `overwrite`).
         `markers`: int8 / int16 (0, 1, 2) array of the volume's shape, uploaded for the call.  Returns the flood's stats."""
+        self._materialize_mask()
         mk = np.ascontiguousarray(markers)
         if mk.shape != self.shape or mk.dtype.type not in (np.int8, np.int16):
             raise TypeError("markers must be an int8 / int16 array of the volume's shape")
@@ -852,6 +931,7 @@ class DeviceVolume:
 
     # -- projections ---------------------------------------------------------------------------------
     def project(self, axis: int, op: int, out: DeviceBuffer):
+        self._materialize_mask()
         L.check(L.lib().ivx_dev_mip_reduce(L.I16, self.image.raw, c64(self.dz), c64(self.dy), c64(self.dx), int(axis),
                                            int(op), out.ptr, self.stream), "project")
 
@@ -863,6 +943,7 @@ class DeviceVolume:
         `forget_image_range()` drops it by hand -- and every writer inside this package that goes to `image.raw` /
         `image.raw_at()` directly (past the tracked accessor) must call it -- or `_image_touched()`, which also drops the
         per-word records the threshold keeps (`_ranges`)."""
+        self._materialize_mask()
         if getattr(self, "_range_buf", None) is None:
             self._range_buf = DeviceBuffer(64)
             self._range_valid = False
@@ -872,6 +953,7 @@ class DeviceVolume:
         return self._range_buf
 
     def forget_image_range(self):
+        self._materialize_mask()
         self._range_valid = False
 
     # -- image filters (filters.py via Slice.__apply_image_filter, slice_.py:2330-2430) ----------------------------------
@@ -880,6 +962,7 @@ class DeviceVolume:
         4 despeckle, 5 border detection) with `value`, in HBM, no host round trip; ``dimension != "3D"`` filters every
         slice along the orientation's axis.  Everything derived from the image is dropped (``_image_touched``), so a
         threshold, region growing or surface after it works on the filtered image, as it does after _after_filter."""
+        self._materialize_mask()
         from . import filters as F
         from .slice_ import _FILTER_PLANES
 
@@ -923,6 +1006,7 @@ class DeviceVolume:
         """The U-Net segmentation of the resident image (get_LUT_value first if `apply_wwwl`) into the resident float32
         probability map `self.prob`, which is returned; `weights` as for segment.load_weights, or a segment.Unet3D.
         The image and the mask are left as they are: apply_segment_threshold writes the mask."""
+        self._materialize_mask()
         from . import segment as SG
 
         SG._check_args(patch_size, overlap)
@@ -954,6 +1038,7 @@ class DeviceVolume:
         """mask.matrix[1:, 1:, 1:] = (prob >= float32(threshold)) * 255 on the resident mask: one kernel per slider move;
         marching_cubes follows without an upload.  The per-slice flag lines live in the host mask's border
         (segment.apply_segment_threshold writes them there)."""
+        self._materialize_mask()
         if getattr(self, "prob", None) is None:
             raise RuntimeError("apply_segment_threshold: no probability map (run segment_unet3d first)")
         L.check(L.lib().ivx_dev_segment_threshold(self.prob.ptr, L.i64(self.shape), ctypes.c_float(float(threshold)),
@@ -1049,6 +1134,7 @@ class DeviceVolume:
         (see volume.shading).  Returns (height, width, 4) float32 RGBA (uint8 with `rgba8`), or the device buffer when not
         `download`.  The sample counts are left in ``last_render_stats`` by a downloading render; without `download`
         nothing is waited for, so they stay those of the last render that did."""
+        self._materialize_mask()
         from . import volume as V
 
         cam = V.resolve_camera(camera, self.shape, self.spacing, size)
@@ -1086,6 +1172,7 @@ class DeviceVolume:
         from . import volume as V
 
         key = int(apron_value)
+        self._materialize_mask()  # (the cells are made from the bytes, and the render reads them)
         if getattr(self, "_mp_cells_valid", False) and self._mp_cells_key == key:
             return self._mp_cells
         ncell = int(np.prod([-(-(s + 1) // V.CELL) for s in self.shape]))
@@ -1105,6 +1192,7 @@ class DeviceVolume:
         with `depth` (iso mode) also the (height, width) float32 distance of the hit, or the device buffer(s) when not
         `download`.  The sample counts are left in ``last_render_stats`` by a downloading render; without `download`
         nothing is waited for, so they stay those of the last render that did."""
+        self._materialize_mask()
         from . import volume as V
         from . import volume_mask as VM
 
@@ -1134,6 +1222,7 @@ class DeviceVolume:
     def volume_histogram(self) -> np.ndarray:
         """CalculateHistogram (volume.py:723-735) of the resident image: uint64 counts of the int(max - min) unit bins
         from min (voxels equal to max are not counted; a constant image gives an empty histogram)."""
+        self._materialize_mask()
         lo, hi = self._image_scale()
         nb = hi - lo
         if nb <= 0:
@@ -1152,6 +1241,7 @@ class DeviceVolume:
         volume's range comes from `image_range()`.  `status` (int32, zeroed by the caller) receives IVX_EDOM where the
         reference's NumCast would panic.  Window level / width are truncated like the reference's wrapper does
         (invesalius_rs/__init__.py:91-95: ``_native.mida(image, axis, int(wl), int(ww), out)``)."""
+        self._materialize_mask()
         L.check(L.lib().ivx_dev_mida(L.I16, self.image.raw, c64(self.dz), c64(self.dy), c64(self.dx), int(axis), ctypes.c_float(float(int(wl))),
                                      ctypes.c_float(float(int(ww))), self.image_range().ptr, L.I16, out.ptr, status.ptr, self.stream), "mida")
 

@@ -278,6 +278,7 @@ def _make_slab_volume():
 
         def reached_count(self) -> int:
             """Reached voxels of the INTERIOR slices only (halo slices belong to the neighbours)."""
+            self._materialize_mask()
             sub = L.FloodPlan(self.lay.nz, self.dy, self.dx, self.plan.wx, self.plan.strct_bits)
             n = ctypes.c_int64(0)
             L.check(L.lib().ivx_dev_flood_count(ctypes.byref(sub), self.reached.at(self.lay.hb * self.plane_words * 8),
@@ -287,6 +288,7 @@ def _make_slab_volume():
         def project_global(self, axis: int, op: str, gather: bool = True, source=None) -> np.ndarray:
             """MaxIP ("max") / MinIP ("min") / MeanIP ("mean") of the WHOLE volume along `axis`, from every rank's
             resident slab: local reduce over the interior slices on the GPU, then slab_project_combine."""
+            self._materialize_mask()
             lay = self.lay
             nint = lay.last_interior - lay.first_interior + 1
             code = {"max": L.MIP_MAX, "min": L.MIP_MIN, "mean": L.MIP_SUM if axis == 0 else L.MIP_MEAN}[op]
@@ -311,6 +313,7 @@ def _make_slab_volume():
             Rays along Z are order-dependent: the slabs are walked front to back, each rank resumes every ray from the
             state its lower neighbour hands over (5 doubles per pixel) and the last rank's image is broadcast.  MIDA
             normalises by the min / max of the whole volume: one all-reduce of two numbers first."""
+            self._materialize_mask()
             lay = self.lay
             code = {"lmip": 0, "mida": 1}[kind]
             nint = lay.nz
@@ -377,6 +380,7 @@ def _make_slab_volume():
             slices -- the halo slices give every owned voxel its true z neighbours, the clamped differences at the ends
             of the volume are the unsharded ones -- and then projected like any other volume (tmip 0 = MaxIP,
             1 = LMIP(700, 3033), 2 = MIDA)."""
+            self._materialize_mask()
             tmp, status = DeviceBuffer(self.n * 2 + 16), DeviceBuffer(64)
             status.zero(self.stream)
             L.check(L.lib().ivx_dev_fcm_volume(L.I16, self.image.raw, c64(self.dz), c64(self.dy), c64(self.dx), ctypes.c_float(n),

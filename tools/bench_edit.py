@@ -61,12 +61,12 @@ def main():
     work = DeviceBuffer(N)
 
     def cut():
-        lib.ivx_memcpy_d2d(work.ptr, vol.mask.raw, ctypes.c_size_t(N), vol.stream)
+        lib.ivx_memcpy_d2d(work.ptr, vol.mask_bytes(), ctypes.c_size_t(N), vol.stream)
         return lib.ivx_dev_mask_cut(work.ptr, c64(n), c64(n), c64(n), dbl(0.5), dbl(0.5), dbl(0.5), dbl(1e9), filt.ptr, c64(1024),
                                     c64(1024), a16, b16, 1, vol.stream)
 
     timed("mask_cut(+copy)", cut, 3 * N)
-    timed("mask_copy_only", lambda: lib.ivx_memcpy_d2d(work.ptr, vol.mask.raw, ctypes.c_size_t(N), vol.stream), 2 * N)
+    timed("mask_copy_only", lambda: lib.ivx_memcpy_d2d(work.ptr, vol.mask_bytes(), ctypes.c_size_t(N), vol.stream), 2 * N)
     ce = (dbl * 3)(n * 0.25, n * 0.25, n * 0.25)
     timed("brush_r20mm", lambda: lib.ivx_dev_brush_mask(work.ptr, None, c64(n), c64(n), c64(n), sp, ce, dbl(20.0), 1, vol.stream), 80 ** 3)
     pts = np.array([[100.0, 120.0], [900.0, 200.0], [700.0, 950.0], [150.0, 800.0]])
@@ -84,7 +84,7 @@ def main():
     sb = ctypes.c_size_t(0)
     lib.ivx_mask_area_scratch_bytes(c64(n), c64(n), c64(n), ctypes.byref(sb))
     scr, area = DeviceBuffer(sb.value), DeviceBuffer(64)
-    timed("mask_area", lambda: lib.ivx_dev_mask_area_u8(vol.mask.raw, c64(n), c64(n), c64(n), dk.ptr, scr.ptr, area.ptr, vol.stream), N)
+    timed("mask_area", lambda: lib.ivx_dev_mask_area_u8(vol.mask_bytes(), c64(n), c64(n), c64(n), dk.ptr, scr.ptr, area.ptr, vol.stream), N)
     if n <= 512:
         f64 = DeviceBuffer(N * 8)
         f64.upload((vol.download_mask() > 127) * 1.0)

@@ -52,9 +52,9 @@ def main():
         res["threshold_ms"] = round(timed(vol, "thr", lambda: vol.threshold(*THRESHOLD)), 4)
         cells = vol._maskren_cells(1)
         res["cells_ms"] = round(timed(vol, "cells", lambda: L.check(lib.ivx_dev_maskren_cells(
-            vol.mask.raw, shape, dense, 1, 1, c64(0), c64(-1), cells.ptr, vol.stream))), 4)
+            vol.mask_bytes(), shape, dense, 1, 1, c64(0), c64(-1), cells.ptr, vol.stream))), 4)
         res["cells_slab_16_ms"] = round(timed(vol, "cells16", lambda: L.check(lib.ivx_dev_maskren_cells(
-            vol.mask.raw, shape, dense, 1, 1, c64(n // 2), c64(n // 2 + 16), cells.ptr, vol.stream))), 4)
+            vol.mask_bytes(), shape, dense, 1, 1, c64(n // 2), c64(n // 2 + 16), cells.ptr, vol.stream))), 4)
         # the comparator's field: download, widen on the host, upload as an image (the parent commit has no other way)
         t = time.perf_counter()
         mask = vol.download_mask()
@@ -83,7 +83,7 @@ def main():
                     iso = int(setup["iso"])
 
                     def run():
-                        L.check(lib.ivx_dev_maskren_render(vol.mask.raw, cells.ptr, shape, dense, 1, 1, iso, tb.ptr,
+                        L.check(lib.ivx_dev_maskren_render(vol.mask_bytes(), cells.ptr, shape, dense, 1, 1, iso, tb.ptr,
                                                            tb.at(nb), ctypes.byref(p), outd.ptr, None, None, vol.stream))
                     ms = timed(vol, "render", run)
                     rec = {"mode": mode, "view": view, "size": size, "ms": round(ms, 4),

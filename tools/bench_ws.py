@@ -28,9 +28,9 @@ def main():
         "lut_u16": (lambda: lib.ivx_dev_lut_u16(vol.image.raw, c64(N), ctypes.c_double(2000.0), ctypes.c_double(300.0), 1, cost.ptr, vol.stream), 4 * N),
         "shift_min_u16": (lambda: lib.ivx_dev_shift_min_u16(vol.image.raw, c64(N), -1024, cost.ptr, vol.stream), 4 * N),
         "morph_gradient_3x3x3": (lambda: lib.ivx_dev_morph_gradient_u16(cost.ptr, c64(n), c64(n), c64(n), size, grad.ptr, vol.stream), 4 * N),
-        "watershed_merge": (lambda: lib.ivx_dev_watershed_merge(vol.mask.raw, tmp.ptr, c64(N), 0, vol.stream), 3 * N),
-        "mask_boolean_union": (lambda: lib.ivx_dev_mask_boolean(1, vol.mask.raw, m2.ptr, mo.ptr, c64(N), vol.stream), 3 * N),
-        "masked_density": (lambda: lib.ivx_dev_masked_density_i16(vol.image.raw, vol.mask.raw, c64(N), acc.ptr, vol.stream), 3 * N),
+        "watershed_merge": (lambda: lib.ivx_dev_watershed_merge(vol.mask_bytes(), tmp.ptr, c64(N), 0, vol.stream), 3 * N),
+        "mask_boolean_union": (lambda: lib.ivx_dev_mask_boolean(1, vol.mask_bytes(), m2.ptr, mo.ptr, c64(N), vol.stream), 3 * N),
+        "masked_density": (lambda: lib.ivx_dev_masked_density_i16(vol.image.raw, vol.mask_bytes(), c64(N), acc.ptr, vol.stream), 3 * N),
     }
     out = {"n": n}
     for name, (fn, nbytes) in stages.items():

@@ -53,7 +53,8 @@ def main():
         # steps of the kernel-trace run (warm-up + timed + the bench's instrumented extra steps); "auto" = the call count
         # of a kernel that runs exactly once per step
         # (k_flood_clear no longer runs in the fused start; the threshold is k_threshold16_bits_build once per upload and
-        # k_threshold16_bits_use in every other step: together once per step)
+        # k_threshold16_bits_use in every other step: together once per step; their plane-only forms k_threshold16_plane<..> and
+        # k_threshold16_plane_use keep the prefix)
         once = sum(stats[k][0] for k in stats if k.startswith("k_threshold16"))
         nsteps = once if sys.argv[4] == "auto" else int(sys.argv[4])
         stage_of = lambda k: ("threshold" if k.startswith("k_threshold") else "marching_cubes" if k.startswith("k_mc_")
