@@ -2080,15 +2080,17 @@ static int or_planes_dev_impl(const ivx_flood_plan *p, const uint64_t *cand, uin
     const FScratch s = make_fscratch(t);
     const int64_t nw = t.dy * t.wx;
     IVX_REQUIRE(changed_dev, IVX_EINVAL, "flood: null counter");
+    const int64_t zs[2] = {z_a, z_b};
+    const uint64_t *pl[2] = {plane_a, plane_b};
+    // both slices are checked before anything is queued: a refused call leaves the plane and the caller's word as they were
+    for (int q = 0; q < 2; q++)
+        IVX_REQUIRE(!pl[q] || (zs[q] >= 0 && zs[q] < t.dz), IVX_ERANGE, "flood: plane %lld outside slab", (long long)zs[q]);
     hipStream_t st = ivx::S(stream);
     if (zero) IVX_HIP(hipMemsetAsync(changed_dev, 0, 4, st));
     if (!nw || (!plane_a && !plane_b)) return IVX_OK;
     uint8_t *dirty = (uint8_t *)((char *)scratch_ + s.off_dirty0);
-    const int64_t zs[2] = {z_a, z_b};
-    const uint64_t *pl[2] = {plane_a, plane_b};
     for (int q = 0; q < 2; q++) {
         if (!pl[q]) continue;
-        IVX_REQUIRE(zs[q] >= 0 && zs[q] < t.dz, IVX_ERANGE, "flood: plane %lld outside slab", (long long)zs[q]);
         hipLaunchKernelGGL(k_flood_or_plane<true>, dim3((unsigned)ivx::cdiv(nw, 256)), dim3(256), 0, st,
                            (unsigned long long *)reached + zs[q] * nw, (const unsigned long long *)pl[q],
                            (const unsigned long long *)cand + zs[q] * nw, nw, (unsigned int *)changed_dev, t, zs[q], dirty);
@@ -2108,16 +2110,17 @@ extern "C" int ivx_dev_flood_or_planes(const ivx_flood_plan *p, const uint64_t *
     const FScratch s = make_fscratch(t);
     const int64_t nw = t.dy * t.wx;
     *changed = 0;
+    const int64_t zs[2] = {z_a, z_b};
+    const uint64_t *pl[2] = {plane_a, plane_b};
+    for (int q = 0; q < 2; q++) // (before anything is queued: a refused call changes nothing)
+        IVX_REQUIRE(!pl[q] || (zs[q] >= 0 && zs[q] < t.dz), IVX_ERANGE, "flood: plane %lld outside slab", (long long)zs[q]);
     if (!nw || (!plane_a && !plane_b)) return IVX_OK;
     hipStream_t st = ivx::S(stream);
     unsigned int *d_chg = (unsigned int *)((char *)scratch_ + s.off_status);
     uint8_t *dirty = (uint8_t *)((char *)scratch_ + s.off_dirty0);
     IVX_HIP(hipMemsetAsync(d_chg, 0, 4, st));
-    const int64_t zs[2] = {z_a, z_b};
-    const uint64_t *pl[2] = {plane_a, plane_b};
     for (int q = 0; q < 2; q++) {
         if (!pl[q]) continue;
-        IVX_REQUIRE(zs[q] >= 0 && zs[q] < t.dz, IVX_ERANGE, "flood: plane %lld outside slab", (long long)zs[q]);
         hipLaunchKernelGGL(k_flood_or_plane<true>, dim3((unsigned)ivx::cdiv(nw, 256)), dim3(256), 0, st,
                            (unsigned long long *)reached + zs[q] * nw, (const unsigned long long *)pl[q],
                            (const unsigned long long *)cand + zs[q] * nw, nw, d_chg, t, zs[q], dirty);

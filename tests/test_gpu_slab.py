@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 from _ptr_comm import LoopbackWorld  # noqa: E402  (N ranks as threads on ONE GPU, device-pointer protocol)
 
 
-@pytest.mark.parametrize("world,conn", [(2, 3), (3, 1)])
+@pytest.mark.parametrize("world,conn", [(2, 3), (3, 1), (8, 1)])
 def test_slab_volume_matches_single_volume_oracle(ivxlib, oracle, world, conn):
     from invesalius3_amd.parallel import SlabVolume
 
