@@ -565,6 +565,54 @@ int ivx_count_regions(int ldtype, const void *labels, const int64_t shape[3], co
                       int64_t number_regions, uint32_t *out);
 
 /* ------------------------------------------------------------------------------------------------
+ * Slice editing tools (csrc/k_slice_edit.hip, csrc/slice_edit_math.h)
+ *   ivx_*_mask_brush_stroke  the array work the three brushes share: Slice.edit_mask_pixel invesalius/data/slice_.py:656-744
+ *                            (operations 0 .. 5 = BRUSH_DRAW, ERASE, THRESH, THRESH_ERASE, THRESH_ADD_ONLY, THRESH_ERASE_ONLY,
+ *                            invesalius/constants.py:341-346), WaterShedInteractorStyle.edit_mask_pixel styles.py:2000-2069
+ *                            and BaseImageEditionInteractorStyle.edit_mask_pixel styles.py:392-461 (operation 6 = IVX_BRUSH_FILL:
+ *                            write `fill_value`).  `dabs` holds one (xi, yi) pair per dab: the first column and row of the
+ *                            footprint's UNCLIPPED window on the slice, ``int(px - w + (w / 2 + 1))`` (slice_.py:690-695;
+ *                            slice_edit_math.h computes it); a footprint pixel that falls outside the h x w slice is skipped
+ *                            by the kernel, which is what the reference's four clips (:697-709) leave, and a window that
+ *                            misses the slice writes nothing.  One operation per device call; the dabs of a call may overlap
+ *                            (the result is that of the dabs applied one after another).  thresh_min / thresh_max: the
+ *                            edition threshold range as integers (ceil / floor of the python numbers).
+ *       device form: a 2-D view of the slice -- `mask` points at pixel (0, 0), strides are signed bytes (a sagittal view has
+ *                    an element stride of one row pitch and a row stride of one plane) -- the matching int16 image view, or
+ *                    NULL for the operations that do not read it (DRAW, ERASE, FILL); footprint fh x fw bytes (non-zero =
+ *                    painted) and dabs in device memory.
+ *       host form:   the padded (dz+1, dy+1, dx+1) mask matrix with its byte strides (or, padded = 0, a matrix of the image's
+ *                    own shape: the watershed markers), the image matrix (image_shape is ITS shape; image may be NULL when no
+ *                    run reads it), orientation 0 AXIAL / 1 CORONAL / 2 SAGITAL and slice n.  The dabs come in `nruns` runs of
+ *                    one operation each (run_ops[r], run_lens[r] dabs), launched in order.  Only the slice is staged (from the
+ *                    mirror when the matrix is registered, ivx_host_register) and written back to host and mirror;
+ *                    set_flag: the slice's flag cell becomes 2 in both, the flag part of Slice.apply_slice_buffer_to_mask
+ *                    (slice_.py:1925-1967); previous: NULL, or h * w bytes that receive the slice as it was before (p_mask).
+ *   ivx_*_mask_crop          CropMaskInteractorStyle.CropMask styles.py:2654-2694: every byte of the (dz, dy, dx) block
+ *                            outside box = {z0, z1, y0, y1, x0, x1} (half-open) becomes 1.  The host form takes the whole
+ *                            padded matrix (flag planes included, as the reference's ``matrix[:] = 1``).
+ * ---------------------------------------------------------------------------------------------- */
+#define IVX_BRUSH_FILL 6
+int ivx_dev_mask_brush_stroke(uint8_t *mask, int64_t mask_row_stride, int64_t mask_elem_stride, const int16_t *image,
+                              int64_t image_row_stride, int64_t image_elem_stride, int64_t h, int64_t w, const uint8_t *footprint,
+                              int64_t fh, int64_t fw, const int32_t *dabs, int64_t ndabs, int operation, int thresh_min,
+                              int thresh_max, int fill_value, void *stream);
+int ivx_mask_brush_stroke(uint8_t *mask, const int64_t image_shape[3], const int64_t mask_strides[3], const int16_t *image,
+                          const int64_t image_strides[3], int orientation, int64_t n, const uint8_t *footprint, int64_t fh,
+                          int64_t fw, const int32_t *dabs, const int32_t *run_ops, const int64_t *run_lens, int64_t nruns,
+                          int thresh_min, int thresh_max, int fill_value, int padded, int set_flag, uint8_t *previous);
+/* slice_edit_math.h for host callers (pure host code, no device): a flat integer position as (px, py); the (xi, yi) windows of
+ * `ndabs` (px, py) positions; the four clips of one window, out = {x at, x skip, x count, y at, y skip, y count}; and what the
+ * kernel's bounds test leaves of one dab in a view with these strides, out = {pixels, lowest, highest byte offset (-1: none)} */
+int ivx_slice_flat_position(int64_t position, int64_t slice_width, double out_xy[2]);
+int ivx_slice_dab_windows(const double *positions_xy, int64_t ndabs, int64_t fh, int64_t fw, int32_t *dabs);
+int ivx_slice_dab_clip(int64_t xi, int64_t yi, int64_t fh, int64_t fw, int64_t h, int64_t w, int64_t out[6]);
+int ivx_slice_dab_extent(int64_t xi, int64_t yi, int64_t fh, int64_t fw, int64_t h, int64_t w, int64_t row_stride,
+                         int64_t elem_stride, int64_t out[3]);
+int ivx_dev_mask_crop(uint8_t *mask, int64_t dz, int64_t dy, int64_t dx, const int64_t box[6], void *stream);
+int ivx_mask_crop(uint8_t *mask, const int64_t shape[3], const int64_t mask_strides[3], const int64_t box[6]);
+
+/* ------------------------------------------------------------------------------------------------
  * whole-mask numpy expressions of invesalius/data/slice_.py
  *   ivx_*_mask_boolean        Slice.do_boolean_op slice_.py:1906-1916: out = 255 where op(m1 > 2, m2 > 2) else 0;
  *                             op = 1 union, 2 diff (m1 and not m2), 3 intersection, 4 xor (constants.py:818-821)

@@ -5,7 +5,8 @@ Host-side mirror of the reference interface for that path and the stages next to
     invesalius3_amd.invesalius_rs      <-> invesalius_rs/__init__.py (floodfill, mips, transforms, mesh, mask-editing names)
     invesalius3_amd.slice_             <-> invesalius/data/slice_.py threshold / projection / boolean / measurement call sites
     invesalius3_amd.mask               <-> invesalius/data/mask.py fill_holes_auto
-    invesalius3_amd.styles             <-> invesalius/data/styles.py region-growing tool (do_3d_seg, do_rg_confidence)
+    invesalius3_amd.styles             <-> invesalius/data/styles.py region-growing tool (do_3d_seg, do_rg_confidence), slice tools
+    invesalius3_amd.cursor             <-> invesalius/data/cursor_actors.py brush footprints, and the window a dab covers
     invesalius3_amd.surface_process    <-> invesalius/data/surface_process.py create_surface_piece, join_process_surface
     invesalius3_amd.watershed_process  <-> invesalius/data/watershed_process.py do_watershed
     invesalius3_amd.project            <-> invesalius/project.py .inv3 container (read / write, no wx / VTK)

@@ -601,6 +601,66 @@ class DeviceVolume:
         d_sel.close()
         return rounds
 
+    # -- slice editing tools ---------------------------------------------------------------
+    def _slice_geometry(self, orientation: str, n: int):
+        """(h, w, first element, row stride, element stride) of slice `n` in a dense (dz, dy, dx) block, in elements"""
+        ax = {"AXIAL": 0, "CORONAL": 1, "SAGITAL": 2}.get(orientation)
+        if ax is None:
+            raise ValueError("orientation must be AXIAL, CORONAL or SAGITAL")
+        if not 0 <= int(n) < self.shape[ax]:
+            raise IndexError("slice %d outside the volume" % n)
+        st = (self.dy * self.dx, self.dx, 1)
+        r, e = (a for a in range(3) if a != ax)
+        return self.shape[r], self.shape[e], int(n) * st[ax], st[r], st[e]
+
+    def brush_stroke(self, orientation: str, n: int, index, positions, operations=2, edition_threshold_range=(0, 0),
+                     fill_value: int = 0, target: DeviceBuffer | None = None):
+        """slice_.edit_mask_stroke on the resident mask (or on `target`, a uint8 block of the volume's shape, e.g. watershed
+        markers): the dabs of `positions` under the footprint `index` on slice `n`, in maximal runs of one operation launched
+        in order on the volume's stream (ivx_dev_mask_brush_stroke).  The resident mask has no flag cells."""
+        from . import cursor
+        from . import slice_ as sl
+
+        h, w, first, rs, es = self._slice_geometry(orientation, n)
+        if np.ndim(index) != 2:
+            raise TypeError("the footprint is a 2-D array")
+        fp = np.ascontiguousarray(np.asarray(index) != 0).view(np.uint8)
+        positions = list(positions)
+        runs = sl._op_runs(operations, len(positions))
+        if not runs or fp.size == 0:
+            return
+        dabs = cursor.dab_windows(positions, fp.shape, w)
+        lo, hi = sl._int_bounds(edition_threshold_range)
+        base = (target.ptr if target is not None else self.mask.ptr).value  # (mask.ptr: a writer's pointer, the notes drop)
+        d_fp, d_dabs = DeviceBuffer(fp.size), DeviceBuffer(dabs.nbytes)
+        try:
+            d_fp.upload(fp)
+            d_dabs.upload(dabs)
+            at = 0
+            for op, k in runs:
+                L.check(L.lib().ivx_dev_mask_brush_stroke(
+                    ctypes.c_void_p(base + first), c64(rs), c64(es), ctypes.c_void_p(self.image.raw.value + first * 2), c64(rs * 2),
+                    c64(es * 2), c64(h), c64(w), d_fp.ptr, c64(fp.shape[0]), c64(fp.shape[1]), d_dabs.at(at * 8), c64(k), int(op),
+                    int(lo), int(hi), int(fill_value) & 255, self.stream), "brush_stroke")
+                at += k
+            L.check(L.lib().ivx_stream_synchronize(self.stream))
+        finally:
+            d_fp.close()
+            d_dabs.close()
+
+    def brush_fill(self, orientation: str, n: int, fill_value: int, index, positions, target: DeviceBuffer | None = None):
+        """styles.brush_fill on a resident block: `fill_value` under the footprint at every position"""
+        self.brush_stroke(orientation, n, index, positions, 6, fill_value=fill_value, target=target)
+
+    def crop_mask(self, limits):
+        """styles.crop_mask on the resident mask -- the interior ``matrix[1:, 1:, 1:]`` -- so the kept box
+        ``[zi : zf + 2, ...]`` of the padded matrix is ``[zi - 1 : zf + 1, ...]`` here; everything else becomes 1."""
+        xi, xf, yi, yf, zi, zf = (int(v) for v in limits)
+        if min(xi, yi, zi) < 0 or min(xf, yf, zf) < -2:
+            raise ValueError("crop limits must not be negative")
+        box = L.i64([max(zi - 1, 0), min(zf + 1, self.dz), max(yi - 1, 0), min(yf + 1, self.dy), max(xi - 1, 0), min(xf + 1, self.dx)])
+        L.check(L.lib().ivx_dev_mask_crop(self.mask.ptr, c64(self.dz), c64(self.dy), c64(self.dx), box, self.stream), "crop_mask")
+
     def reached_count(self) -> int:
         self._materialize_mask()
         n = ctypes.c_int64(0)

@@ -119,6 +119,11 @@ def run(args) -> dict:
             vol.mask.zero(vol.stream)  # keep only the grown region
             L.check(lib.ivx_dev_flood_apply_where(vol.mask.ptr, vol.out_mask.ptr, c64(vol.n), 1, 255, vol.stream))
             out["region_grow"] = {"seeds": [list(s) for s in seeds], "rounds": rounds, "voxels": vol.reached_count()}
+        if getattr(args, "crop", None) is not None:
+            # the Crop mask tool (CropMaskInteractorStyle.CropMask, styles.py:2654-2694) on the resident mask
+            with vol.timer.span("crop"):
+                vol.crop_mask(args.crop)
+            out["crop"] = {"limits": list(args.crop)}
         if args.mask_preview is not None:
             # "Mask 3D preview" (Mask.create_3d_preview -> VolumeMask.create_volume, volume_mask.py:36-119) of the resident mask
             from . import volume as V
@@ -249,7 +254,7 @@ def _render_only(args) -> bool:
     """--render without anything that asks for a mask or a surface: the image is all there is to make"""
     return (args.threshold is None and args.segment is None and not args.seed and not args.stl and not args.save
             and not args.largest and not args.smooth and not args.remove_nonvisible and not args.surface_seed
-            and args.split is None and "--mask" not in (args.argv or []))
+            and args.split is None and getattr(args, "crop", None) is None and "--mask" not in (args.argv or []))
 
 
 def _strct(conn: int) -> np.ndarray:
@@ -272,6 +277,8 @@ def main(argv=None) -> int:
     ap.add_argument("--apply-wwwl", nargs=2, type=float, metavar=("WW", "WL"), default=None,
                     help="window the image (get_LUT_value) before --segment")
     ap.add_argument("--seed", nargs="+", type=int, default=None, metavar="X Y Z", help="keep the region grown (in the image, inside the threshold range) from these voxels; refused for a hand-edited --mask")
+    ap.add_argument("--crop", nargs=6, type=int, default=None, metavar=("XI", "XF", "YI", "YF", "ZI", "ZF"),
+                    help="crop the mask to this box of voxel limits (the Crop mask tool), after --threshold and --seed")
     ap.add_argument("--filter", nargs=2, metavar=("NAME", "VALUE"), default=None,
                     help="image filter applied before --threshold / --seed: NAME one of %s, VALUE the dialog's value "
                          "(sigma, or the size parameter)" % ",".join(FILTER_TYPES))

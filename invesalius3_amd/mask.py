@@ -25,7 +25,8 @@ def _structure(rank: int, connectivity: int) -> np.ndarray:
 def bind_matrix(matrix: np.ndarray) -> "resident.Resident":
     """Keep a mask's padded matrix in HBM: call it where the reference creates it (Mask.create_mask,
     invesalius/data/mask.py:422-431).  What the library writes into the matrix goes to the host and to the mirror alike; a
-    numpy write (the brush, ``matrix[:] = 0``) is followed by ``touch`` on the returned `Resident`."""
+    numpy write (``matrix[:] = 0``) is followed by ``touch`` on the returned `Resident`; the brush has its own entry points
+    that write host and mirror (slice_.edit_mask_stroke, styles.brush_fill)."""
     return resident.bind(matrix)
 
 

@@ -298,3 +298,150 @@ def apply_image_filter(matrix: np.ndarray, filter_type: int, value, dimension: s
         filters.mean_size(value)
     result = filters.image_filter(matrix, filter_type, value, plane)
     return result.astype(matrix.dtype)
+
+
+# ---- the manual edition panel -------------------------------------------------------------------------------------
+BRUSH_DRAW, BRUSH_ERASE, BRUSH_THRESH, BRUSH_THRESH_ERASE, BRUSH_THRESH_ADD_ONLY, BRUSH_THRESH_ERASE_ONLY = range(6)  # constants.py:341-346
+BRUSH_FILL = 6  # IVX_BRUSH_FILL: the marker brush and the generic brush write a given byte
+
+
+def _axis(orientation: str) -> int:
+    try:
+        return _AXIS[orientation]
+    except KeyError:
+        raise ValueError("orientation must be AXIAL, CORONAL or SAGITAL") from None
+
+
+def _slice_views(mask_matrix, image_matrix, orientation, n):
+    """(mask slice view, flag cell view, image slice view) of Slice.get_mask_slice (slice_.py:1142-1173)"""
+    ax = _axis(orientation)
+    n = int(n)
+    if mask_matrix.dtype != np.uint8 or mask_matrix.ndim != 3:
+        raise TypeError("mask matrix must be a 3-D uint8 array")
+    if not 0 <= n < mask_matrix.shape[ax] - 1:
+        raise IndexError("slice %d outside the volume" % n)
+    m = [slice(1, None)] * 3
+    m[ax] = n + 1
+    f = [slice(0, 1)] * 3
+    f[ax] = slice(n + 1, n + 2)
+    image = None
+    if image_matrix is not None:
+        if image_matrix.dtype != np.int16 or tuple(mask_matrix.shape) != tuple(s + 1 for s in image_matrix.shape):
+            raise TypeError("image must be int16 and the mask matrix one voxel larger on every axis (invesalius/data/mask.py:422-431)")
+        i = [slice(None)] * 3
+        i[ax] = n
+        image = image_matrix[tuple(i)]
+    return mask_matrix[tuple(m)], mask_matrix[tuple(f)], image
+
+
+def get_mask_slice(mask_matrix, image_matrix, orientation: str, n: int, threshold_range) -> np.ndarray:
+    """Slice.get_mask_slice (invesalius/data/slice_.py:1121-1175), the lazy threshold of one slice in any orientation: when
+    the slice's flag cell -- ``[n+1,0,0]`` AXIAL, ``[0,n+1,0]`` CORONAL, ``[0,0,n+1]`` SAGITAL -- is 0, the slice
+    ``matrix[n+1, 1:, 1:]`` (and siblings) is thresholded with the preserve rule and the flag set to 1, in place; returns
+    a copy of the slice.  (The buffer_slices cache in front of it stays with the caller.)"""
+    mview, flag, _ = _slice_views(mask_matrix, image_matrix, orientation, n)
+    if flag.reshape(-1)[0] == 0:
+        ax = _axis(orientation)
+        order = (ax,) + tuple(a for a in range(3) if a != ax)  # the slice's axis in front: one "axial" slice of a strided volume
+        mt, it = mask_matrix.transpose(order), image_matrix.transpose(order)
+        lo, hi = _int_bounds(threshold_range)
+        img1, m2 = it[n:n + 1], mt[n:n + 2]
+        L.check(L.lib().ivx_threshold_all_slices(L.ptr(img1), L.i64(img1.shape), L.i64(img1.strides), ctypes.c_int(lo), ctypes.c_int(hi),
+                                                 ctypes.c_int(1), ctypes.c_int(1), L.ptr(m2), L.i64(m2.strides)), "get_mask_slice")
+    return np.array(mview, dtype=mask_matrix.dtype)
+
+
+def _op_runs(operations, ndabs):
+    """maximal runs of one operation: [(operation, dabs)]"""
+    if not hasattr(operations, "__iter__"):
+        return [(int(operations), ndabs)] if ndabs else []
+    ops = [int(o) for o in operations]
+    if len(ops) != ndabs:
+        raise ValueError("one operation per position")
+    runs = []
+    for o in ops:
+        if runs and runs[-1][0] == o:
+            runs[-1][1] += 1
+        else:
+            runs.append([o, 1])
+    return [(o, k) for o, k in runs]
+
+
+def _brush_stroke(matrix, image_matrix, orientation, n, index, positions, operations, thresh=(0, 0), fill_value=0, padded=True,
+                  set_flag=False, want_previous=False):
+    """ivx_mask_brush_stroke: the dabs of `positions` under the footprint `index`, in runs of one operation, on slice `n`"""
+    from . import cursor
+
+    ax = _axis(orientation)
+    if np.ndim(index) != 2:
+        raise TypeError("the footprint is a 2-D array")
+    index = np.ascontiguousarray(np.asarray(index) != 0).view(np.uint8)
+    if matrix.dtype != np.uint8 or matrix.ndim != 3:
+        raise TypeError("the matrix must be a 3-D uint8 array")
+    ishape = tuple(s - 1 for s in matrix.shape) if padded else tuple(matrix.shape)
+    h, w = (ishape[a] for a in range(3) if a != ax)
+    positions = list(positions)
+    dabs = np.ascontiguousarray(cursor.dab_windows(positions, index.shape, w))
+    runs = _op_runs(operations, len(positions))
+    reads = any(BRUSH_THRESH <= o <= BRUSH_THRESH_ERASE_ONLY for o, _ in runs)
+    if reads and (image_matrix is None or image_matrix.dtype != np.int16 or tuple(image_matrix.shape) != ishape):
+        raise TypeError("the threshold operations need the int16 image the mask belongs to")
+    lo, hi = _int_bounds(thresh)
+    run_ops = (ctypes.c_int32 * max(len(runs), 1))(*[o for o, _ in runs])
+    run_lens = (L.c_i64 * max(len(runs), 1))(*[k for _, k in runs])
+    previous = np.empty((h, w), np.uint8) if want_previous else None
+    L.check(L.lib().ivx_mask_brush_stroke(
+        L.ptr(matrix), L.i64(ishape), L.i64(matrix.strides), L.ptr(image_matrix) if reads else None,
+        L.i64(image_matrix.strides) if reads else None, ctypes.c_int(ax), L.c_i64(int(n)), L.ptr(index), L.c_i64(index.shape[0]),
+        L.c_i64(index.shape[1]), L.ptr(dabs), run_ops, run_lens, L.c_i64(len(runs)), ctypes.c_int(lo), ctypes.c_int(hi),
+        ctypes.c_int(int(fill_value) & 255), ctypes.c_int(int(padded)), ctypes.c_int(int(set_flag)),
+        L.ptr(previous) if want_previous else None), "brush_stroke")
+    return previous
+
+
+def edit_mask_stroke(mask_matrix, image_matrix, orientation: str, n: int, index, positions, operations=BRUSH_THRESH,
+                     edition_threshold_range=(0, 0), threshold_range=None, set_flag: bool = True, return_previous: bool = False):
+    """A whole drag of the brush on slice `n`: Slice.edit_mask_pixel (invesalius/data/slice_.py:656-744) for every position,
+    then the write-back and flag of Slice.apply_slice_buffer_to_mask (:1925-1967) -- on the GPU, in place on the padded mask
+    matrix, staging the slice alone.  `index` is the footprint (cursor.cursor_pixels), `positions` the slice
+    pixels the cursor visited -- ``(px, py)`` pairs, floats allowed, or flat integers -- `operations` one BRUSH_* value or
+    one per position (the modifier keys can change during a drag: the stroke is split into maximal runs of one operation,
+    launched in order).  The slice is first brought up to date with `threshold_range` (the mask's own), as the reference's
+    viewer has done before any brush event (get_mask_slice); the range may be left out only for a slice whose flag says it
+    is up to date already.  Returns the slice as it was before the stroke (p_mask, for the caller's undo history) when
+    asked."""
+    if threshold_range is not None:
+        get_mask_slice(mask_matrix, image_matrix, orientation, n, threshold_range)
+    elif _slice_views(mask_matrix, image_matrix, orientation, n)[1].reshape(-1)[0] == 0:
+        raise ValueError("slice %d (%s) has not been thresholded yet (its flag is 0): pass the mask's threshold_range" % (n, orientation))
+    return _brush_stroke(mask_matrix, image_matrix, orientation, n, index, positions, operations, edition_threshold_range,
+                         padded=True, set_flag=set_flag, want_previous=return_previous)
+
+
+def edit_mask_pixel(mask_matrix, image_matrix, orientation: str, n: int, operation: int, index, position,
+                    edition_threshold_range=(0, 0), threshold_range=None, set_flag: bool = True, return_previous: bool = False):
+    """One dab: Slice.edit_mask_pixel (slice_.py:656-744) -- `edit_mask_stroke` with a single position."""
+    return edit_mask_stroke(mask_matrix, image_matrix, orientation, n, index, [position], operation, edition_threshold_range,
+                            threshold_range, set_flag, return_previous)
+
+
+def apply_slice_buffer_to_mask(mask_matrix, orientation: str, n: int, b_mask) -> np.ndarray:
+    """Slice.apply_slice_buffer_to_mask (slice_.py:1925-1967) for callers that keep the reference's buffer-slice flow: the
+    caller's edited slice goes into the matrix, the slice's flag becomes 2; returns the previous slice (p_mask).  The slice
+    travels through a device block, so that a bound matrix gets exactly these bytes in its mirror (a `touch` of a coronal or
+    sagittal view would upload nearly the whole matrix again)."""
+    from .device import DeviceBuffer
+
+    mview, flag, _ = _slice_views(mask_matrix, None, orientation, n)
+    b = np.ascontiguousarray(b_mask, dtype=np.uint8)
+    if b.shape != mview.shape:
+        raise ValueError("the buffer slice has shape %r, the mask's slice %r" % (b.shape, mview.shape))
+    p_mask = mview.copy()
+    buf = DeviceBuffer(b.size + 16)
+    try:
+        buf.upload(np.concatenate([b.reshape(-1), np.array([2], np.uint8)]))
+        buf.download_view(mview)
+        L.check(L.lib().ivx_download_strided(L.ptr(flag), L.i64((1, 1, 1)), L.i64((1, 1, 1)), buf.at(b.size), 1), "apply_slice_buffer")
+    finally:
+        buf.close()
+    return p_mask

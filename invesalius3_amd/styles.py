@@ -167,3 +167,98 @@ def watershed_brush_release(image_matrix: np.ndarray, mask_matrix: np.ndarray, m
     mask[...] = m2
     resident.touch(mask)
     return True
+
+
+# ---- the slice editing tools --------------------------------------------------------------------------------------
+def brush_fill(matrix: np.ndarray, orientation: str, n: int, fill_value: int, index, position=None, positions=None) -> None:
+    """The array work of WaterShedInteractorStyle.edit_mask_pixel (invesalius/data/styles.py:2000-2069, the marker brush:
+    `fill_value` is the marker) and of BaseImageEditionInteractorStyle.edit_mask_pixel (:392-461, the generic fill-value
+    brush): the footprint `index` at `position` of slice `n` gets `fill_value`.  `matrix` is a uint8 matrix of the image's
+    shape -- not padded, no flags.  `positions`: a whole drag in one call instead of one `position`."""
+    positions = [position] if positions is None else list(positions)
+    sl._brush_stroke(matrix, None, orientation, n, index, positions, sl.BRUSH_FILL, fill_value=int(fill_value), padded=False)
+
+
+def _slice_as_volume(a: np.ndarray, orientation: str, n: int) -> np.ndarray:
+    """slice `n` of a (dz, dy, dx) array as a strided (1, h, w) view"""
+    if orientation == "AXIAL":
+        return a[n:n + 1]
+    if orientation == "CORONAL":
+        return a[:, n:n + 1, :].transpose(1, 0, 2)
+    if orientation == "SAGITAL":
+        return a[:, :, n:n + 1].transpose(2, 0, 1)
+    raise ValueError("orientation must be AXIAL, CORONAL or SAGITAL")
+
+
+def do_2d_seg(image_matrix: np.ndarray, mask_matrix: np.ndarray, seed_xy, orientation: str, n: int, method: str = "dynamic",
+              con_2d: int = 4, fill_value: int = 254, t0=None, t1=None, dev_min=25, dev_max=25, use_ww_wl: bool = False,
+              ww=None, wl=None, confid_mult: float = 2.5, confid_iters: int = 3):
+    """The array work of FloodFillSegmentInteractorStyle.do_2d_seg (invesalius/data/styles.py:3082-3149): region growing
+    inside slice `n` from the clicked slice pixel ``seed_xy = (x, y)``.  The slice is a (1, h, w) volume -- a strided view of
+    the (resident) matrices -- flooded with the (1, 3, 3) structure of generate_binary_structure(2, 1 | 2), by the engine
+    of do_3d_seg.  "dynamic" with window/level floods get_LUT_value_255 of the slice, "confidence" is do_rg_confidence.
+    Returns False when the click is rejected (seed value outside [t0, t1], :3120: nothing changes), else the previous slice.
+    Kept from the reference: the slice goes into the volume WITHOUT touching its flag."""
+    if image_matrix.dtype != np.int16 or image_matrix.ndim != 3:
+        raise TypeError("image must be a 3-D int16 array")
+    if mask_matrix.dtype != np.uint8 or mask_matrix.shape != tuple(s + 1 for s in image_matrix.shape):
+        raise TypeError("mask matrix must be uint8 and one voxel larger than the image on every axis")
+    if method not in ("threshold", "dynamic", "confidence"):
+        raise ValueError("method must be threshold, dynamic or confidence")
+    image = _slice_as_volume(image_matrix, orientation, int(n))
+    mask = _slice_as_volume(mask_matrix[1:, 1:, 1:], orientation, int(n))
+    x, y = (int(v) for v in seed_xy)
+    _, h, w = image.shape
+    if not (0 <= y < h and 0 <= x < w):
+        raise IndexError("seed outside the slice")
+    strct = _structure(2, CON2D[con_2d]).reshape(1, 3, 3)
+    with DeviceVolume(image) as vol:
+        flood_image = None
+        if use_ww_wl and method in ("dynamic", "confidence"):
+            flood_image = vol.lut_image_255(ww, wl)
+        try:
+            if method != "confidence":
+                if method == "threshold":
+                    lo, hi = t0, t1
+                    v = int(image[0, y, x])
+                else:
+                    if flood_image is not None:
+                        one = np.zeros(1, np.int16)
+                        vol.sync()  # the LUT kernel runs on the volume's stream, the copy below does not
+                        L.check(L.lib().ivx_memcpy_d2h(L.ptr(one), flood_image.at((y * w + x) * 2), ctypes.c_size_t(2)))
+                        v = int(one[0])
+                    else:
+                        v = int(image[0, y, x])
+                    lo, hi = v - dev_min, v + dev_max
+                if v < lo or v > hi:
+                    return False
+            previous = np.array(mask[0])
+            vol.mask.upload_view(mask)
+            vol.zero_out_mask()
+            if method == "confidence":
+                vol.region_grow_confidence((x, y, 0), strct, confid_mult, confid_iters, select_value=int(fill_value), image=flood_image)
+            else:
+                vol.region_grow([(x, y, 0)], lo, hi, strct, fill=1, select_value=int(fill_value), image=flood_image)
+            vol.sync()
+            vol.mask.download_view(mask)  # host and mirror, the slice's bytes alone
+        finally:
+            if flood_image is not None:
+                flood_image.close()
+    return previous
+
+
+def crop_mask(mask_matrix: np.ndarray, image_matrix: np.ndarray | None, limits, threshold_range=None) -> None:
+    """The array work of CropMaskInteractorStyle.CropMask (invesalius/data/styles.py:2654-2694): the stale slices are
+    thresholded first (`image_matrix` and the mask's `threshold_range`), then ALL of the padded matrix becomes 1, flag
+    planes included, except the box ``[zi : zf + 2, yi : yf + 2, xi : xf + 2]`` in padded indices, with
+    ``limits = (xi, xf, yi, yf, zi, zf)`` as ``box.GetLimits()`` gives them: the reference's ``+ 1`` shift and
+    ``- 1 : + 1`` slice keep one extra layer on the low side.  In place."""
+    if mask_matrix.dtype != np.uint8 or mask_matrix.ndim != 3:
+        raise TypeError("mask matrix must be a 3-D uint8 array")
+    xi, xf, yi, yf, zi, zf = (int(v) for v in limits)
+    if min(xi, yi, zi) < 0 or xf + 2 < 0 or yf + 2 < 0 or zf + 2 < 0:
+        raise ValueError("crop limits must not be negative")  # (python's slices would count them from the far end)
+    if threshold_range is not None and image_matrix is not None:
+        sl.do_threshold_to_all_slices(mask_matrix, image_matrix, threshold_range)
+    box = L.i64([zi, min(zf + 2, mask_matrix.shape[0]), yi, min(yf + 2, mask_matrix.shape[1]), xi, min(xf + 2, mask_matrix.shape[2])])
+    L.check(L.lib().ivx_mask_crop(L.ptr(mask_matrix), L.i64(mask_matrix.shape), L.i64(mask_matrix.strides), box), "crop_mask")
