@@ -501,6 +501,60 @@ int ivx_mesh_select_seeded(const float *verts, int64_t nverts, const int32_t *fa
 int ivx_mesh_nearest_point(const float *verts, int64_t nverts, const double *xyz, int64_t *id);
 
 /* ------------------------------------------------------------------------------------------------
+ * the geodesic measure: shortest paths along the triangle edges of the indexed surface (csrc/k_meshgeo.hip)
+ *   replaces GeodesicMeasure._draw_line        invesalius/data/measures.py:1202-1256
+ *            (vtkDijkstraGraphGeodesicPath between consecutive picks, each snapped with vtkPointLocator.FindClosestPoint:
+ *             ivx_*_mesh_nearest_point above; the summed edge length is the measure's value in mm)
+ * Mesh graph.  The unique neighbours of every point in ascending id order, as a CSR in a caller-owned device buffer that is
+ * built once per mesh and read by every measure on it.  Neighbours come from the triangle sides, both directions; a side
+ * whose two ids are equal (a degenerate triangle) is no edge; a point no triangle uses has an empty list; the valence is
+ * not bounded.  The buffer holds int64 header[32] = {magic, nverts, ntris, stored neighbours, byte offset of the offsets,
+ * byte offset of the neighbours}, then uint32 offsets[nverts + 1], then the uint32 neighbour ids.
+ *   ivx_mesh_graph_bytes       an upper bound on the buffer's size for such a mesh
+ *   ivx_dev_mesh_graph_build   fills it (too small a buffer: IVX_ERANGE, "room for")
+ * Weights.  w(u, v) = sqrt((dx dx + dy dy) + dz dz) in float64 from the float32 positions widened to double, the root
+ * correctly rounded, nothing contracted; computed on the fly.  Coincident points joined by a side give zero-length edges,
+ * and those are edges.
+ * Distances.  dist[v] is the least fixed point of d[v] = min_u fl(d[u] + w(u, v)) with d[source] = 0: since fl(a + w) is
+ * monotone in a and never below a, no order of relaxation changes a bit of it (pinned to scipy.sparse.csgraph.dijkstra
+ * under array_equal).  Points the source does not reach get +inf and pred -1; the source gets 0 and pred -1.
+ *   delta            only frontier points below a threshold relax; when none is left the threshold moves to (smallest
+ *                    waiting distance) + delta.  +inf: plain frontier relaxation; tiny: Dijkstra's order; <= 0: the default,
+ *                    4 x the mesh's mean edge length (summed on the device in a fixed order, so the same from run to run).
+ *   rounds_per_look  rounds queued between two looks of the host at the device's "anything left" word (<= 0: the default, 16).
+ *                    Both defaults are the pair with the lowest median in the measured sweep of DESIGN 7j.
+ *   stop_at >= 0     a point whose distance is not below the current dist[stop_at] does not relax.  dist[stop_at] and every
+ *                    entry <= dist[stop_at] are exact then; ENTRIES ABOVE IT ARE UPPER BOUNDS OR +inf.  < 0: the whole field.
+ *   pred             recorded when a point's distance is lowered: among the neighbours whose offer won that round, the
+ *                    smallest id (ties between equal offers are therefore deterministic, and the predecessor graph stays
+ *                    acyclic across zero-length edges -- a rule applied after the fact would cycle there).  pred is the same
+ *                    from run to run for the same mesh, delta and rounds_per_look; BETWEEN SCHEDULES IT MAY DIFFER where two
+ *                    paths are equally short.  May be NULL.
+ *   stats            host int64[4], may be NULL: rounds, point relaxations, threshold advances, host looks.
+ * Rounds stop at 4 nverts + 64 and the back-trace at nverts steps: a wrong frontier is IVX_EHIP, never a hang.
+ * Path.  For every consecutive pair of ids: the distances with stop_at = the pair's end, then pred walked back from the end
+ * on the device; `path` (device int32[max_path]) takes the ids from START to END, segment after segment, seg_points[i] how
+ * many and seg_length[i] = dist[end].  At convergence fl(dist[pred[v]] + w) == dist[v], so seg_length equals the float64 sum
+ * of the path's edge lengths accumulated from the start, bit for bit.  start == end: one id, length 0.0; an end that cannot
+ * be reached: no ids, length +inf.  ids, seg_points, seg_length and stats are host arrays.
+ * Errors, before any launch: an id (source, stop_at, ids[]) outside [0, nverts) IVX_EDOM; nids < 2 IVX_EINVAL; a mesh too
+ * large for 32-bit ids IVX_EINVAL; too small a max_path IVX_ERANGE ("room for", known once the segment has been traced).
+ * Host forms take host pointers and the faces: they upload, build the graph, run and download (face ids are checked: IVX_EDOM).
+ * PARITY UNPINNED vs VTK; distances pinned to scipy: the reference sums the same edges in its filter's output order into one
+ * running double over all segments, which can differ from the sum of seg_length in the last bits; VTK is not installed here. */
+int ivx_mesh_graph_bytes(int64_t nverts, int64_t ntris, size_t *bytes);
+int ivx_dev_mesh_graph_build(const int32_t *faces, int64_t nverts, int64_t ntris, void *graph, size_t graph_bytes, void *stream);
+int ivx_dev_mesh_geodesic_distances(const float *verts, int64_t nverts, const void *graph, int64_t source, int64_t stop_at,
+                                    double delta, int rounds_per_look, double *dist, int32_t *pred, int64_t *stats, void *stream);
+int ivx_dev_mesh_geodesic_path(const float *verts, int64_t nverts, const void *graph, const int32_t *ids, int64_t nids,
+                               int32_t *path, int64_t max_path, int64_t *seg_points, double *seg_length, int64_t *stats,
+                               void *stream);
+int ivx_mesh_geodesic_distances(const float *verts, int64_t nverts, const int32_t *faces, int64_t ntris, int64_t source,
+                                int64_t stop_at, double delta, int rounds_per_look, double *dist, int32_t *pred, int64_t *stats);
+int ivx_mesh_geodesic_path(const float *verts, int64_t nverts, const int32_t *faces, int64_t ntris, const int32_t *ids,
+                           int64_t nids, int32_t *path, int64_t max_path, int64_t *seg_points, double *seg_length, int64_t *stats);
+
+/* ------------------------------------------------------------------------------------------------
  * context-aware smoothing of the indexed surface
  *   replaces context_aware_smoothing           invesalius_rs/src/mesh_py.rs:7-330 -> mesh.rs:27-86
  *            (python: invesalius_rs.Mesh.ca_smoothing / ca_smoothing, invesalius_rs/__init__.py:220-275;

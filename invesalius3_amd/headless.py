@@ -5,6 +5,7 @@
     python -m invesalius3_amd.headless CASE.inv3 --threshold 226 3071 --largest --remove-nonvisible --stl shell.stl
     python -m invesalius3_amd.headless CASE.inv3 --threshold 226 3071 --surface-seed 120.5 98.0 40.0 --stl part.stl
     python -m invesalius3_amd.headless CASE.inv3 --threshold 226 3071 --split parts/ --split-min-triangles 100
+    python -m invesalius3_amd.headless CASE.inv3 --threshold 226 3071 --largest --geodesic 120.5 98 40 80 60.5 75 --geodesic-npy path.npy
     python -m invesalius3_amd.headless CASE.inv3 --filter median 3 --threshold 226 3071 --stl bone.stl
     python -m invesalius3_amd.headless CASE.inv3 --segment brain --weights brain_mri_t1.pt --stl brain.stl
     python -m invesalius3_amd.headless CASE.inv3 --render "Bone + Skin" --presets-dir DIR --view iso --png out.png
@@ -197,6 +198,21 @@ def run(args) -> dict:
             faces = faces_buf.download((nt, 3), np.int32)
             sp.write_stl_binary(args.stl, verts[faces])
             out["stl"] = args.stl
+        if args.geodesic:
+            # the measurement panel's geodesic measure (GeodesicMeasure._draw_line, measures.py:1202-1256) on the final surface
+            from . import polydata_utils as pu
+            picks = [tuple(args.geodesic[i:i + 3]) for i in range(0, len(args.geodesic), 3)]
+            final = pu.DeviceMesh(verts_buf, nv, faces_buf, nt, vol.stream)
+            try:
+                with vol.timer.span("geodesic"):
+                    geo = final.geodesic(points=picks)
+            finally:
+                final.close()  # (frees the graph; the buffers are not its own)
+            out["geodesic"] = {"points": [list(xyz) for xyz in picks], "point_ids": [int(i) for i in geo.point_ids],
+                               "segment_lengths": geo.segment_lengths, "length_mm": geo.length, "path_points": len(geo.points)}
+            if args.geodesic_npy:
+                np.save(args.geodesic_npy, geo.points)
+                out["geodesic"]["npy"] = args.geodesic_npy
         if args.split is not None:
             # Surface.OnSplitSurface -> pu.SplitDisconectedParts (surface.py:319-361) on the final surface: one STL per part, in
             # region order, and every part's measures (CreateSurfaceFromPolydata takes them per part, surface.py:953-960)
@@ -254,7 +270,7 @@ def _render_only(args) -> bool:
     """--render without anything that asks for a mask or a surface: the image is all there is to make"""
     return (args.threshold is None and args.segment is None and not args.seed and not args.stl and not args.save
             and not args.largest and not args.smooth and not args.remove_nonvisible and not args.surface_seed
-            and args.split is None and getattr(args, "crop", None) is None and "--mask" not in (args.argv or []))
+            and args.split is None and not getattr(args, "geodesic", None) and getattr(args, "crop", None) is None and "--mask" not in (args.argv or []))
 
 
 def _strct(conn: int) -> np.ndarray:
@@ -307,6 +323,10 @@ def main(argv=None) -> int:
                          "a table of triangles, volume and area in the JSON line")
     ap.add_argument("--split-min-triangles", type=int, default=1, metavar="N",
                     help="leave parts with fewer than N triangles out of --split's files and table (default 1)")
+    ap.add_argument("--geodesic", nargs="+", type=float, default=None, metavar="X Y Z",
+                    help="the geodesic measure on the final surface: the shortest path along the triangle edges through the "
+                         "mesh points nearest to these two or more coordinates, its length in mm in the JSON line")
+    ap.add_argument("--geodesic-npy", metavar="FILE", default=None, help="write the path's coordinates, float32 (n, 3), as .npy")
     ap.add_argument("--remove-nonvisible", action="store_true",
                     help="remove the faces that cannot be seen from outside (the six axis views at 800 x 800 of the reference's "
                          "Remove non-visible faces), after --largest and before --smooth / --stl")
@@ -331,6 +351,10 @@ def main(argv=None) -> int:
         ap.error("--seed takes triples of x y z")
     if args.surface_seed and len(args.surface_seed) % 3:
         ap.error("--surface-seed takes triples of x y z")
+    if args.geodesic is not None and (len(args.geodesic) < 6 or len(args.geodesic) % 3):
+        ap.error("--geodesic takes two or more triples of x y z")
+    if args.geodesic_npy is not None and args.geodesic is None:
+        ap.error("--geodesic-npy needs --geodesic")
     if args.split_min_triangles != 1 and args.split is None:
         ap.error("--split-min-triangles needs --split DIR")
     if args.filter is not None:

@@ -11,6 +11,9 @@ The surface connectivity tools (polydata_utils.py:206-278; csrc/k_meshparts.hip,
 ``SplitDisconectedParts``, ``JoinSeedsParts`` and ``SelectLargestPart``, on arrays or on a `DeviceMesh`; `MeshParts` is the
 split resident in HBM, every part a view into two grouped buffers.
 
+`DeviceMesh.graph`, `geodesic_distances` and `geodesic` are the device side of the geodesic measure (`measures.py`;
+csrc/k_meshgeo.hip): the mesh graph built once per mesh, edge distances pinned to scipy's Dijkstra bit for bit.
+
 PARITY UNPINNED: VTK and its OpenGL rasteriser are not installed; the rules of DESIGN 7f / 7h are pinned bit for bit against
 their numpy restatements (tests/_meshvis_ref.py, tests/_mesh_regions_ref.py).  vtkCleanPolyData's merge of coincident points
 is not done."""
@@ -109,6 +112,7 @@ class DeviceMesh:
 
     def __init__(self, verts_buf, nverts: int, faces_buf, ntris: int, stream=None, owns: bool = False):
         self.verts, self.nverts, self.faces, self.ntris, self.stream, self._owns = verts_buf, int(nverts), faces_buf, int(ntris), stream, owns
+        self._graph = None  # the mesh graph of the geodesic measure, built on first use
 
     @classmethod
     def from_volume(cls, vol, counts=None):
@@ -231,11 +235,147 @@ class DeviceMesh:
                                            ctypes.byref(nr), self.stream), "mesh_split")
         return MeshParts(ov, nv.value, of, self.ntris if nr.value else 0, tb, nr.value, self.stream)
 
+    # ---- the geodesic measure ----
+    def graph(self):
+        """the mesh graph (unique neighbours per point, ascending, CSR) as a `DeviceBuffer`: built on first use, kept until
+        `close`, read by every measure on this mesh"""
+        if self._graph is None:
+            from .device import DeviceBuffer
+            nbytes = ctypes.c_size_t(0)
+            L.check(L.lib().ivx_mesh_graph_bytes(ctypes.c_int64(self.nverts), ctypes.c_int64(self.ntris), ctypes.byref(nbytes)),
+                    "mesh_graph_bytes")
+            g = DeviceBuffer(nbytes.value)
+            try:
+                L.check(L.lib().ivx_dev_mesh_graph_build(self.faces.ptr, ctypes.c_int64(self.nverts), ctypes.c_int64(self.ntris), g.ptr,
+                                                         ctypes.c_size_t(nbytes.value), self.stream), "mesh_graph_build")
+            except Exception:
+                g.close()
+                raise
+            self._graph = g
+        return self._graph
+
+    def graph_arrays(self):
+        """``(offsets uint32 (V + 1,), neighbours uint32 (E,))`` of `graph`, downloaded"""
+        g = self.graph()
+        self.sync()
+        head = g.download((32,), np.int64)
+        if int(head[1]) != self.nverts or int(head[2]) != self.ntris:
+            raise RuntimeError("mesh graph: header does not describe this mesh")
+        ne, at_off, at_adj = int(head[3]), int(head[4]), int(head[5])
+        off, adj = np.empty(self.nverts + 1, np.uint32), np.empty(ne, np.uint32)
+        L.check(L.lib().ivx_memcpy_d2h(L.ptr(off), g.at(at_off), ctypes.c_size_t(off.nbytes)))
+        if ne:
+            L.check(L.lib().ivx_memcpy_d2h(L.ptr(adj), g.at(at_adj), ctypes.c_size_t(adj.nbytes)))
+        return off, adj
+
+    def geodesic_distances(self, source, stop_at=None, delta=None, rounds_per_look=None, with_stats=False):
+        """``(dist float64 (V,), pred int32 (V,))`` from point `source` along the triangle edges (ivx.h: +inf / -1 where the
+        source does not reach; with `stop_at` the entries above ``dist[stop_at]`` are upper bounds).  `delta` /
+        `rounds_per_look`: the schedule, None for the library's default -- neither changes a bit of `dist`.
+        `with_stats` adds the dict of rounds, relaxations, threshold advances and host looks."""
+        from .device import DeviceBuffer
+        source, stop = _point_id(source, self.nverts, "source"), -1 if stop_at is None else _point_id(stop_at, self.nverts, "stop_at")
+        graph = self.graph()
+        d, p = DeviceBuffer(self.nverts * 8 + 16), DeviceBuffer(self.nverts * 4 + 16)
+        stats = (ctypes.c_int64 * 4)()
+        try:
+            L.check(L.lib().ivx_dev_mesh_geodesic_distances(self.verts.ptr, ctypes.c_int64(self.nverts), graph.ptr, ctypes.c_int64(source),
+                                                            ctypes.c_int64(stop), ctypes.c_double(0.0 if delta is None else float(delta)),
+                                                            ctypes.c_int(0 if rounds_per_look is None else int(rounds_per_look)),
+                                                            d.ptr, p.ptr, stats, self.stream), "mesh_geodesic_distances")
+            self.sync()
+            out = d.download((self.nverts,), np.float64), p.download((self.nverts,), np.int32)
+        finally:
+            d.close()
+            p.close()
+        return out + (_geo_stats(stats),) if with_stats else out
+
+    def geodesic(self, points=None, ids=None) -> "GeodesicPath":
+        """The shortest path along the triangle edges through two or more picks, in order: `points` are coordinates, each
+        snapped with `nearest_point` (the reference's vtkPointLocator.FindClosestPoint), or `ids` the point ids themselves."""
+        from .device import DeviceBuffer
+        if (points is None) == (ids is None):
+            raise ValueError("geodesic: give points or ids")
+        if ids is None:
+            pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+            if len(pts) < 2:
+                raise ValueError("geodesic: at least two points needed")
+            if self.nverts == 0:
+                raise ValueError("geodesic: the mesh has no points")
+            ids = [self.nearest_point(xyz) for xyz in pts]
+        ids = geodesic_ids(ids, self.nverts)
+        nseg = len(ids) - 1
+        graph = self.graph()
+        room = max(self.nverts, 1) * nseg
+        path = DeviceBuffer(room * 4 + 16)
+        seg_n, seg_len, stats = (ctypes.c_int64 * nseg)(), (ctypes.c_double * nseg)(), (ctypes.c_int64 * 4)()
+        try:
+            L.check(L.lib().ivx_dev_mesh_geodesic_path(self.verts.ptr, ctypes.c_int64(self.nverts), graph.ptr, L.ptr(ids),
+                                                       ctypes.c_int64(len(ids)), path.ptr, ctypes.c_int64(room), seg_n, seg_len, stats,
+                                                       self.stream), "mesh_geodesic_path")
+            self.sync()
+            total = int(sum(seg_n))
+            flat = path.download((total,), np.int32) if total else np.zeros(0, np.int32)
+            coords = np.zeros((total, 3), np.float32)
+            if total:
+                whole = self.verts.download((self.nverts, 3), np.float32)
+                coords = whole[flat]
+        finally:
+            path.close()
+        cuts = np.cumsum([0] + [int(n) for n in seg_n])
+        return GeodesicPath([flat[cuts[q]:cuts[q + 1]].copy() for q in range(nseg)], np.ascontiguousarray(coords),
+                            [float(x) for x in seg_len], ids, _geo_stats(stats))
+
     def close(self):
+        if self._graph is not None:
+            self._graph.close()
+            self._graph = None
         if self._owns:
             self.verts.close()
             self.faces.close()
         self._owns = False
+
+
+class GeodesicPath:
+    """What `DeviceMesh.geodesic` returns.  `ids`: one int32 array per segment, from its start to its end (empty when the end
+    cannot be reached, one id when start == end); `points`: float32 (n, 3), the segments' coordinates one after the other, the
+    joints repeated the way vtkAppendPolyData repeats them; `segment_lengths`: ``dist[end]`` per segment (+inf when
+    unreachable); `length`: the sum of the finite ones, in order; `point_ids`: the picks' ids; `stats`."""
+
+    def __init__(self, ids, points, segment_lengths, point_ids, stats):
+        self.ids, self.points, self.segment_lengths, self.point_ids, self.stats = ids, points, segment_lengths, point_ids, stats
+        total = 0.0
+        for x in segment_lengths:
+            if math.isfinite(x):
+                total += x
+        self.length = total
+
+
+def _geo_stats(stats) -> dict:
+    return {"rounds": int(stats[0]), "relaxations": int(stats[1]), "threshold_advances": int(stats[2]), "host_looks": int(stats[3])}
+
+
+def _point_id(i, nverts, what) -> int:
+    if isinstance(i, bool) or not isinstance(i, (int, np.integer)):
+        raise ValueError("%s must be an integer point id" % what)
+    if not 0 <= int(i) < int(nverts):
+        raise ValueError("%s %d outside [0, %d)" % (what, int(i), int(nverts)))
+    return int(i)
+
+
+def geodesic_ids(ids, nverts) -> np.ndarray:
+    """the picks' ids as int32, checked on the host before anything runs: fewer than two, or an id outside [0, nverts), is a
+    ValueError"""
+    a = np.asarray(list(ids) if not isinstance(ids, np.ndarray) else ids)
+    if a.size < 2:
+        raise ValueError("geodesic: at least two points needed")
+    if a.dtype.kind not in "iu":
+        raise ValueError("geodesic: point ids must be integers")
+    a = a.reshape(-1).astype(np.int64)
+    if a.min() < 0 or a.max() >= int(nverts):
+        bad = a[(a < 0) | (a >= int(nverts))][0]
+        raise ValueError("geodesic: point id %d outside [0, %d)" % (int(bad), int(nverts)))
+    return np.ascontiguousarray(a, dtype=np.int32)
 
 
 def _seed_ids(ids, nverts) -> np.ndarray:
