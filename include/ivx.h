@@ -667,6 +667,42 @@ int ivx_dev_mask_crop(uint8_t *mask, int64_t dz, int64_t dy, int64_t dx, const i
 int ivx_mask_crop(uint8_t *mask, const int64_t shape[3], const int64_t mask_strides[3], const int64_t box[6]);
 
 /* ------------------------------------------------------------------------------------------------
+ * image geometry tools: the three operations of the reference that rewrite the whole image
+ *   flip          Slice.OnFlipVolume (invesalius/data/slice_.py:2103-2149): m[:] = m[::-1] on axis 0 / 1 / 2 of (z, y, x)
+ *   swap axes     Slice.OnSwapVolumeAxes (:2151-2251): np.array(m.swapaxes(a, b)), a new block of the new shape
+ *   gantry tilt   imagedata_utils.FixGantryTilt (imagedata_utils.py:143-154): slice n becomes
+ *                 scipy.ndimage.shift(slice, (shifts[n], 0), order 3, mode "constant", cval = the matrix's minimum as it
+ *                 stands before slice n), int16, bit for bit (csrc/imagegeo_math.h has the arithmetic)
+ * `itemsize` 1 / 2 / 4 / 8: flip and swap move elements, whatever they mean.  The _dev_ forms work on dense device blocks
+ * and enqueue on `stream`; flip and tilt work in place, swap writes `dst` (same number of elements; `src` and `dst` must not
+ * overlap).  The host forms take host views (signed byte strides) through the copy helpers, so a registered array comes from
+ * its mirror and the result goes to the host and the mirror.
+ * Tilt: `shifts` is a HOST array of dz doubles, the first component of the shift the reference hands scipy for each slice.
+ * The device form needs `scratch`, 8-byte aligned: ivx_image_tilt_scratch_bytes reports the size it likes (a head of
+ * 20 bytes per slice rounded up to 256, then float64 coefficients for as many slices as fit 512 MiB); anything from the
+ * head plus ONE slice of coefficients (dy * dx * 8 bytes) is accepted -- more only lets a launch take more slices, the
+ * result does not depend on it.  It waits for `stream` once in the middle (the per-slice minima come to the host, where
+ * the chain of fill values is resolved) and returns with the fill pass queued.  `cvals_out` (host, dz ints, or NULL)
+ * receives the fill value of every slice.
+ * ivx_host_zero: memset(p, 0, nbytes) on the host and, where [p, p + nbytes) lies in a registered range, the same in its
+ * mirror -- no byte crosses the link (what the tools above do with every mask).  ivx_host_register_zero registers a range
+ * like ivx_host_register but uploads nothing: the mirror starts as zeros, and so must the host range (or the caller lets a
+ * host form of this header write all of it next).
+ * ---------------------------------------------------------------------------------------------- */
+int ivx_dev_image_flip(void *vol, int64_t dz, int64_t dy, int64_t dx, size_t itemsize, int axis, void *stream);
+int ivx_image_flip(void *vol, const int64_t shape[3], const int64_t strides[3], size_t itemsize, int axis);
+int ivx_dev_image_swap_axes(const void *src, int64_t dz, int64_t dy, int64_t dx, size_t itemsize, int axis_a, int axis_b, void *dst,
+                            void *stream);
+int ivx_image_swap_axes(const void *src, const int64_t shape[3], const int64_t strides[3], size_t itemsize, int axis_a, int axis_b,
+                        void *dst, const int64_t dst_strides[3]);
+int ivx_image_tilt_scratch_bytes(int64_t dz, int64_t dy, int64_t dx, size_t *nbytes);
+int ivx_dev_image_fix_gantry_tilt(int16_t *vol, int64_t dz, int64_t dy, int64_t dx, const double *shifts, void *scratch,
+                                  size_t scratch_bytes, int *cvals_out, void *stream);
+int ivx_image_fix_gantry_tilt(int16_t *vol, const int64_t shape[3], const int64_t strides[3], const double *shifts, int *cvals_out);
+int ivx_host_zero(void *p, size_t nbytes);
+int ivx_host_register_zero(const void *base, size_t nbytes, uint64_t *handle);
+
+/* ------------------------------------------------------------------------------------------------
  * whole-mask numpy expressions of invesalius/data/slice_.py
  *   ivx_*_mask_boolean        Slice.do_boolean_op slice_.py:1906-1916: out = 255 where op(m1 > 2, m2 > 2) else 0;
  *                             op = 1 union, 2 diff (m1 and not m2), 3 intersection, 4 xor (constants.py:818-821)

@@ -75,7 +75,16 @@ def _declare(lib):
                                                                ctypes.c_int, c_vp]),
                        ("ivx_dev_mask_from_planes", [ctypes.POINTER(FloodPlan), c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp]),
                        ("ivx_dev_flood_candidates_ranges", [ctypes.POINTER(FloodPlan), c_vp, ctypes.c_double, ctypes.c_double, c_vp,
-                                                            ctypes.c_int, ctypes.c_double, c_vp, c_vp, c_vp])):
+                                                            ctypes.c_int, ctypes.c_double, c_vp, c_vp, c_vp]),
+                       # the image geometry tools (flip, swap axes, gantry tilt) and the calls that keep a mask's zeros off the link
+                       ("ivx_dev_image_flip", [c_vp, c_i64, c_i64, c_i64, sz, ctypes.c_int, c_vp]),
+                       ("ivx_image_flip", [c_vp, i64p, i64p, sz, ctypes.c_int]),
+                       ("ivx_dev_image_swap_axes", [c_vp, c_i64, c_i64, c_i64, sz, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
+                       ("ivx_image_swap_axes", [c_vp, i64p, i64p, sz, ctypes.c_int, ctypes.c_int, c_vp, i64p]),
+                       ("ivx_image_tilt_scratch_bytes", [c_i64, c_i64, c_i64, ctypes.POINTER(sz)]),
+                       ("ivx_dev_image_fix_gantry_tilt", [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, sz, c_vp, c_vp]),
+                       ("ivx_image_fix_gantry_tilt", [c_vp, i64p, i64p, c_vp, c_vp]),
+                       ("ivx_host_zero", [c_vp, sz]), ("ivx_host_register_zero", [c_vp, sz, u64p])):
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = args, ctypes.c_int
 

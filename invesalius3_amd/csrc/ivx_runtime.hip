@@ -1140,6 +1140,52 @@ int ivx_host_register(const void *base, size_t nbytes, uint64_t *handle) {
     *handle = h;
     return IVX_OK;
 }
+// a registration whose mirror starts as zeros: nothing is uploaded (the new arrays of a swap, which a host form fills next)
+int ivx_host_register_zero(const void *base, size_t nbytes, uint64_t *handle) {
+    IVX_REQUIRE(base && nbytes && handle, IVX_EINVAL, "ivx_host_register_zero: null or empty range");
+    std::lock_guard<std::mutex> lk(g_res_mu);
+    int dev = 0;
+    IVX_HIP(hipGetDevice(&dev));
+    uint64_t h = 0;
+    IVX_REQUIRE(g_res.add((uintptr_t)base, nbytes, dev, &h) == resident::RES_OK, IVX_EINVAL,
+                "ivx_host_register_zero: [%p, +%zu) overlaps a registered range", base, nbytes);
+    resident::Range *r = g_res.get(h);
+    hipError_t e = hipMalloc(&r->mirror, nbytes);
+    if (e == hipSuccess) {
+        e = hipMemsetAsync(r->mirror, 0, nbytes, nullptr);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (e != hipSuccess) (void)hipFree(r->mirror);
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("ivx_host_register_zero: no zeroed mirror of %zu bytes (%s)", nbytes, hipGetErrorString(e));
+        g_res.release(h);
+        return e == hipErrorOutOfMemory ? IVX_ENOMEM : IVX_EHIP;
+    }
+    g_res_count.store(g_res.count(), std::memory_order_release);
+    *handle = h;
+    return IVX_OK;
+}
+// zeros on the host and, where the bytes are registered, in the mirror: nothing crosses the link
+int ivx_host_zero(void *p, size_t nbytes) {
+    IVX_REQUIRE(p || !nbytes, IVX_EINVAL, "ivx_host_zero: null");
+    if (!nbytes) return IVX_OK;
+    memset(p, 0, nbytes);
+    if (!g_res_count.load(std::memory_order_acquire)) return IVX_OK;
+    std::unique_lock<std::mutex> lk;
+    resident::Range *r;
+    int rc = res_acquire((uintptr_t)p, (uintptr_t)p + nbytes, false, lk, &r);
+    if (rc) return rc;
+    if (!r) {
+        res_invalidate((uintptr_t)p, (uintptr_t)p + nbytes);
+        return IVX_OK;
+    }
+    IVX_HIP(hipMemsetAsync((char *)r->mirror + ((uintptr_t)p - r->base), 0, nbytes, nullptr));
+    IVX_HIP(hipStreamSynchronize(nullptr));
+    r->stats[resident::ST_WRITES]++;
+    r->stats[resident::ST_WRITE_BYTES] += nbytes;
+    return IVX_OK;
+}
 int ivx_host_touch_range(uint64_t handle, size_t offset, size_t nbytes) {
     std::lock_guard<std::mutex> lk(g_res_mu);
     IVX_REQUIRE(g_res.get(handle), IVX_EINVAL, "ivx_host_touch: handle %llu is released or was never given out", (unsigned long long)handle);

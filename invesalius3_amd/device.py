@@ -661,6 +661,100 @@ class DeviceVolume:
         box = L.i64([max(zi - 1, 0), min(zf + 1, self.dz), max(yi - 1, 0), min(yf + 1, self.dy), max(xi - 1, 0), min(xf + 1, self.dx)])
         L.check(L.lib().ivx_dev_mask_crop(self.mask.ptr, c64(self.dz), c64(self.dy), c64(self.dx), box, self.stream), "crop_mask")
 
+    # -- image geometry tools ----------------------------------------------------------------
+    def _after_image_geometry(self, shape=None, spacing=None):
+        """The image's voxels moved (flip, swap axes, gantry tilt): everything derived from the image goes, as in
+        `_image_touched` -- min/max records, cached range, volume-render field -- and so does everything derived from the
+        mask, which the reference clears (slice_.py:2136-2146): the mask and the out mask become zeros, the notes about their
+        bytes, the mask-render cells, the flood's planes and its gate are dropped.  A new `shape` rebuilds what is sized by it."""
+        lib = L.lib()
+        self._mask_pending = False   # the deferred bytes are about to be zeros anyway
+        self._out_pending = None
+        self._image_touched()
+        self._drop_maskren()
+        self._mbits_valid, self._mbits_range, self._mask_levels = False, None, None
+        self._mbits_version += 1
+        self._mc_params_cache = {}
+        if self._gate_armed:
+            L.check(lib.ivx_dev_flood_disarm_gate(self.flood_scratch.ptr))
+            self._gate_armed = False
+        if spacing is not None:
+            self.spacing = tuple(float(s) for s in spacing)
+        if shape is not None and tuple(shape) != self.shape:
+            self.sync()
+            self.shape = tuple(int(s) for s in shape)
+            self.dz, self.dy, self.dx = self.shape
+            for name in ("cand", "reached", "_mbits", "flood_scratch", "_mc_scratch", "_tris", "_verts", "_faces", "_ranges", "_range_buf"):
+                b = getattr(self, name, None)
+                if b is not None:
+                    b.close()
+                setattr(self, name, None)
+            self._ranges_valid = self._range_valid = False
+            self.plan = L.FloodPlan(self.dz, self.dy, self.dx, (self.dx + 63) // 64, 0)
+            nb, ns = ctypes.c_size_t(0), ctypes.c_size_t(0)
+            L.check(lib.ivx_flood_bits_bytes(ctypes.byref(self.plan), ctypes.byref(nb)))
+            L.check(lib.ivx_flood_scratch_bytes(ctypes.byref(self.plan), ctypes.byref(ns)))
+            self.cand, self.reached, self._mbits = DeviceBuffer(nb.value), DeviceBuffer(nb.value), DeviceBuffer(nb.value)
+            self._plane_words = nb.value // 8
+            self.flood_scratch = DeviceBuffer(ns.value)
+        L.check(lib.ivx_memset(self.mask.raw, 0, ctypes.c_size_t(self.n), self.stream))
+        L.check(lib.ivx_memset(self.out_mask.raw, 0, ctypes.c_size_t(self.n), self.stream))
+        self._out_bytes_zero = True
+
+    def flip(self, axis: int):
+        """slice_.flip_volume on the resident image (Slice.OnFlipVolume, slice_.py:2103-2149): in place in HBM; the mask is
+        cleared and everything derived from image or mask is dropped."""
+        if axis not in (0, 1, 2):
+            raise ValueError("axis must be 0, 1 or 2")
+        self._join_prefetch()
+        L.check(L.lib().ivx_dev_image_flip(self.image.raw, c64(self.dz), c64(self.dy), c64(self.dx), 2, int(axis), self.stream), "flip")
+        self._after_image_geometry()
+
+    def swap_axes(self, axes):
+        """slice_.swap_volume_axes on the resident image (Slice.OnSwapVolumeAxes, slice_.py:2151-2251): the image becomes
+        ``np.array(image.swapaxes(*axes))`` through a second block in HBM, shape and spacing follow, the mask is cleared."""
+        from .slice_ import swapped_spacing
+
+        a, b = (int(v) for v in axes)
+        if a == b or not {a, b} <= {0, 1, 2}:
+            raise ValueError("axes must be two different ones of 0, 1, 2")
+        self._join_prefetch()
+        out = DeviceBuffer(self.n * 2)
+        try:
+            L.check(L.lib().ivx_dev_image_swap_axes(self.image.raw, c64(self.dz), c64(self.dy), c64(self.dx), 2, a, b, out.ptr, self.stream),
+                    "swap_axes")
+            L.check(L.lib().ivx_memcpy_d2d(self.image.raw, out.ptr, ctypes.c_size_t(self.n * 2), self.stream), "swap_axes copy")
+            L.check(L.lib().ivx_stream_synchronize(self.stream))  # the block goes out of scope here
+        finally:
+            out.close()
+        shape = list(self.shape)
+        shape[a], shape[b] = shape[b], shape[a]
+        self._after_image_geometry(shape, swapped_spacing(self.spacing, (a, b)))
+
+    def fix_gantry_tilt(self, tilt, scratch_bytes: int | None = None):
+        """slice_.fix_gantry_tilt on the resident image (imagedata_utils.FixGantryTilt, imagedata_utils.py:143-154), with the
+        volume's own spacing; `scratch_bytes` bounds the coefficient slab (the result does not depend on it).  Returns the
+        fill value of every slice."""
+        from .slice_ import gantry_tilt_shifts
+
+        shifts = gantry_tilt_shifts(self.dz, self.spacing, tilt)
+        cvals = np.zeros(self.dz, np.int32)
+        if self.n == 0:
+            return cvals
+        nb = ctypes.c_size_t(0)
+        L.check(L.lib().ivx_image_tilt_scratch_bytes(c64(self.dz), c64(self.dy), c64(self.dx), ctypes.byref(nb)), "tilt_scratch_bytes")
+        self._join_prefetch()
+        scratch = DeviceBuffer(nb.value if scratch_bytes is None else int(scratch_bytes))
+        try:
+            L.check(L.lib().ivx_dev_image_fix_gantry_tilt(self.image.raw, c64(self.dz), c64(self.dy), c64(self.dx), L.ptr(shifts),
+                                                          scratch.ptr, ctypes.c_size_t(scratch.nbytes), L.ptr(cvals), self.stream),
+                    "fix_gantry_tilt")
+            L.check(L.lib().ivx_stream_synchronize(self.stream))  # the scratch goes out of scope here
+        finally:
+            scratch.close()
+        self._after_image_geometry()
+        return cvals
+
     def reached_count(self) -> int:
         self._materialize_mask()
         n = ctypes.c_int64(0)

@@ -44,6 +44,7 @@ def run(args) -> dict:
     if proj.matrix.dtype != np.int16:
         raise TypeError("the GPU path takes int16 volumes (found %s)" % proj.matrix.dtype)
     bound = [resident.bind(proj.matrix)]  # the project's image, and below the mask the run works on, for its length
+    _image_geometry(args, proj, bound, out)
     vol = DeviceVolume(proj.matrix, spacing=proj.spacing)
     lib = L.lib()
     try:
@@ -266,6 +267,34 @@ def run(args) -> dict:
     return out
 
 
+def _image_geometry(args, proj, bound, out):
+    """--flip, --swap-axes, --gantry-tilt, in that order, on the project's bound image before anything else (Slice.OnFlipVolume,
+    Slice.OnSwapVolumeAxes, imagedata_utils.FixGantryTilt): the image versions follow, every mask of the project is cleared
+    (or recreated at the new shape), and the project records the new shape and spacing the way the reference updates
+    ``matrix_shape`` and ``spacing`` (slice_.py:2198-2200), so --save writes them."""
+    from . import slice_ as sl
+
+    flip, swap, tilt = getattr(args, "flip", None), getattr(args, "swap_axes", None), getattr(args, "gantry_tilt", None)
+    if flip is None and swap is None and tilt is None:
+        return
+    masks = list(proj.masks.values())
+    if flip is not None:
+        sl.flip_volume(proj.matrix, flip, masks=masks, versions=proj.image_versions)
+        out["flip"] = int(flip)
+    if swap is not None:
+        labels = [label for label, mat in proj.image_versions if mat is not proj.matrix]
+        new, spacing, _, versions = sl.swap_volume_axes(proj.matrix, swap, proj.spacing, masks=masks, versions=proj.image_versions)
+        swapped = dict(zip(labels, versions))
+        proj.image_versions = [(label, swapped.get(label, new)) for label, _ in proj.image_versions]
+        proj.matrix, proj.matrix_shape, proj.spacing = new, tuple(new.shape), tuple(spacing)
+        bound[0] = resident.find(new)
+        out["swap_axes"] = [int(v) for v in swap]
+    if tilt is not None:
+        sl.fix_gantry_tilt(proj.matrix, proj.spacing, tilt, masks=masks)
+        out["gantry_tilt"] = float(tilt)
+    out["shape"], out["spacing"] = list(proj.matrix.shape), list(proj.spacing)
+
+
 def _render_only(args) -> bool:
     """--render without anything that asks for a mask or a surface: the image is all there is to make"""
     return (args.threshold is None and args.segment is None and not args.seed and not args.stl and not args.save
@@ -295,6 +324,12 @@ def main(argv=None) -> int:
     ap.add_argument("--seed", nargs="+", type=int, default=None, metavar="X Y Z", help="keep the region grown (in the image, inside the threshold range) from these voxels; refused for a hand-edited --mask")
     ap.add_argument("--crop", nargs=6, type=int, default=None, metavar=("XI", "XF", "YI", "YF", "ZI", "ZF"),
                     help="crop the mask to this box of voxel limits (the Crop mask tool), after --threshold and --seed")
+    ap.add_argument("--flip", type=int, choices=(0, 1, 2), default=None, metavar="AXIS",
+                    help="flip the image along axis 0 (z), 1 (y) or 2 (x) first (the Flip tool); masks are cleared")
+    ap.add_argument("--swap-axes", nargs=2, type=int, default=None, metavar=("A", "B"),
+                    help="then swap two axes of the image (the Swap axes tool): new shape and spacing; masks are recreated")
+    ap.add_argument("--gantry-tilt", type=float, default=None, metavar="DEGREES",
+                    help="then correct a gantry tilt of this many degrees (FixGantryTilt), before any segmentation")
     ap.add_argument("--filter", nargs=2, metavar=("NAME", "VALUE"), default=None,
                     help="image filter applied before --threshold / --seed: NAME one of %s, VALUE the dialog's value "
                          "(sigma, or the size parameter)" % ",".join(FILTER_TYPES))

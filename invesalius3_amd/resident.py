@@ -23,6 +23,7 @@ from . import _lib as L
 _STAT_NAMES = ("hits", "hit_bytes", "refreshes", "refresh_bytes", "write_throughs", "write_through_bytes", "invalidations",
                "generation")
 _live = weakref.WeakValueDictionary()  # (address, nbytes) of a bound allocation -> its Resident
+_kept = {}  # the bindings the package made itself (bind_zeros(keep=True)): held until released
 
 
 def _byte_bounds(a: np.ndarray):
@@ -88,6 +89,7 @@ class Resident:
         self._released = True
         self._fin.detach()
         _live.pop((self.address, self.nbytes), None)
+        _kept.pop((self.address, self.nbytes), None)
         L.check(L.lib().ivx_host_release(self.handle), "resident.release")
 
     def __enter__(self):
@@ -116,6 +118,26 @@ def bind(array: np.ndarray) -> Resident:
     L.check(L.lib().ivx_host_register(ctypes.c_void_p(lo), hi - lo, ctypes.byref(h)), "resident.bind")
     r = Resident(root, h.value, lo, hi - lo)
     _live[(lo, hi - lo)] = r
+    return r
+
+
+def bind_zeros(array: np.ndarray, keep: bool = False) -> Resident:
+    """`bind` for an array of zeros (``np.zeros``) that a library call is about to fill: the mirror starts as zeros too and
+    nothing is uploaded (ivx_host_register_zero).  The caller answers for the zeros.  `keep`: the package made the binding
+    on the caller's behalf (the new arrays of slice_.swap_volume_axes) and holds it until ``find(array).release()``."""
+    if not isinstance(array, np.ndarray):
+        raise TypeError("resident.bind_zeros: a numpy array")
+    L.require_device()
+    root = _root(array)
+    lo, hi = _byte_bounds(root)
+    if hi == lo:
+        raise TypeError("resident.bind_zeros: empty array")
+    h = ctypes.c_uint64(0)
+    L.check(L.lib().ivx_host_register_zero(ctypes.c_void_p(lo), hi - lo, ctypes.byref(h)), "resident.bind_zeros")
+    r = Resident(root, h.value, lo, hi - lo)
+    _live[(lo, hi - lo)] = r
+    if keep:
+        _kept[(lo, hi - lo)] = r
     return r
 
 

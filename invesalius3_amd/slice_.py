@@ -445,3 +445,156 @@ def apply_slice_buffer_to_mask(mask_matrix, orientation: str, n: int, b_mask) ->
     finally:
         buf.close()
     return p_mask
+
+
+# ---- the image geometry tools ---------------------------------------------------------------------------------------
+def _volume(a, what):
+    if not isinstance(a, np.ndarray) or a.ndim != 3 or a.itemsize not in (1, 2, 4, 8):
+        raise TypeError("%s: a 3-D array with items of 1, 2, 4 or 8 bytes" % what)
+    return a
+
+
+def _versions(versions, matrix):
+    """the other image versions (Project.image_versions: arrays, or (label, array) pairs), without `matrix` itself"""
+    mats = [v[1] if isinstance(v, tuple) else v for v in versions]
+    return [m for m in mats if m is not matrix]
+
+
+def _mask_matrix(mask) -> np.ndarray:
+    return mask.matrix if hasattr(mask, "matrix") else mask
+
+
+def _clear_mask(mask):
+    """``mask.matrix[:] = 0`` (slice_.py:2136-2146), flag planes included: zeros on the host and, for a bound matrix, a
+    device memset of its mirror -- the mask crosses the link in neither direction"""
+    mm = _mask_matrix(mask)
+    if mm.flags["C_CONTIGUOUS"] and mm.size:
+        L.check(L.lib().ivx_host_zero(L.ptr(mm), mm.nbytes), "clear mask")
+    else:
+        mm[...] = 0
+        resident.touch(mm)
+    if hasattr(mm, "flush"):
+        mm.flush()
+    if hasattr(mask, "clear_history"):
+        mask.clear_history()
+
+
+def flip_volume(matrix: np.ndarray, axis: int, masks=(), versions=()):
+    """The array work of ``Slice.OnFlipVolume`` (invesalius/data/slice_.py:2103-2149), in place: ``matrix[:] = matrix[::-1]``
+    on `axis` 0 / 1 / 2 of the (z, y, x) matrix, the same for every other image version of `versions` (arrays, or the
+    (label, array) pairs of ``Project.image_versions``), then every mask of `masks` (objects with ``.matrix``, or the padded
+    matrices themselves) zeroed whole, flag planes included, so that the lazy per-slice threshold evaluates it again.  A
+    bound image (`bind_image`) is flipped in its mirror and written to the host once; its binding stays valid."""
+    if axis not in (0, 1, 2):
+        raise ValueError("axis must be 0, 1 or 2")
+    for m in [matrix] + _versions(versions, matrix):
+        _volume(m, "flip_volume")
+        L.check(L.lib().ivx_image_flip(L.ptr(m), L.i64(m.shape), L.i64(m.strides), m.itemsize, int(axis)), "flip_volume")
+        if hasattr(m, "flush"):
+            m.flush()
+    for mask in masks:
+        _clear_mask(mask)
+
+
+def swapped_spacing(spacing, axes):
+    """``spacing`` (sx, sy, sz) after the matrix axes `axes` changed places (slice_.py:2184-2189; the reference spells out
+    the three pairs its menu sends, (2, 1), (2, 0) and (1, 0) -- the same pair in the other order means the same here)"""
+    a, b = (int(v) for v in axes)
+    sp = list(spacing)
+    sp[2 - a], sp[2 - b] = sp[2 - b], sp[2 - a]
+    return tuple(sp)
+
+
+def _swapped(m, a, b, bound):
+    new_shape = list(m.shape)
+    new_shape[a], new_shape[b] = new_shape[b], new_shape[a]
+    new = np.empty(new_shape, m.dtype)
+    new.fill(0)  # (written by the host first: a download into pages nobody has touched faults them in one by one, 190 against 35 ms at 512^3)
+    if bound and new.size:
+        resident.bind_zeros(new, keep=True)  # (the call below writes the host array and this mirror: no upload)
+    L.check(L.lib().ivx_image_swap_axes(L.ptr(m), L.i64(m.shape), L.i64(m.strides), m.itemsize, a, b, L.ptr(new), L.i64(new.strides)),
+            "swap_volume_axes")
+    return new
+
+
+def _release_binding(a):
+    r = resident.find(a)
+    if r is not None and r.array is resident._root(a):
+        r.release()
+
+
+def swap_volume_axes(matrix: np.ndarray, axes, spacing, masks=(), versions=()):
+    """The array work of ``Slice.OnSwapVolumeAxes`` (invesalius/data/slice_.py:2151-2251): returns ``(new_matrix,
+    new_spacing, new_mask_matrices, new_versions)`` with ``new_matrix = np.array(matrix.swapaxes(*axes))``, the spacing
+    permuted (`swapped_spacing`), every other image version swapped alike and every mask a matrix of zeros of the new shape
+    + 1 (set on the mask object where `masks` holds objects with ``.matrix``).  What was bound stays bound: the new arrays
+    are registered with a mirror the swap itself fills, the old bindings are released; no image byte goes to the device.
+    The package holds the new bindings until ``resident.find(array).release()``.  The reference's memmap file replacement
+    stays with the caller."""
+    a, b = (int(v) for v in axes)
+    if a == b or not {a, b} <= {0, 1, 2}:
+        raise ValueError("axes must be two different ones of 0, 1, 2")
+    _volume(matrix, "swap_volume_axes")
+    others = _versions(versions, matrix)
+    new_matrix = None
+    new_versions = []
+    for m in [matrix] + others:
+        _volume(m, "swap_volume_axes")
+        bound = resident.find(m) is not None
+        new = _swapped(m, a, b, bound)
+        if bound:
+            _release_binding(m)
+        if m is matrix:
+            new_matrix = new
+        else:
+            new_versions.append(new)
+    new_mask_shape = tuple(s + 1 for s in new_matrix.shape)
+    new_masks = []
+    for mask in masks:
+        mm = _mask_matrix(mask)
+        if tuple(mm.shape) != new_mask_shape:  # Mask._recreate_mask_matrix (:2237-2239)
+            bound = resident.find(mm) is not None
+            new = np.zeros(new_mask_shape, mm.dtype)
+            if bound:
+                _release_binding(mm)
+                resident.bind_zeros(new, keep=True)
+            if hasattr(mask, "matrix"):
+                mask.matrix = new
+            if hasattr(mask, "clear_history"):
+                mask.clear_history()
+        else:
+            _clear_mask(mask)
+            new = mm
+        new_masks.append(new)
+    return new_matrix, swapped_spacing(spacing, (a, b)), new_masks, new_versions
+
+
+def gantry_tilt_shifts(depth: int, spacing, tilt) -> np.ndarray:
+    """the first component of the shift FixGantryTilt hands scipy for slice n (imagedata_utils.py:148-154), in its own
+    order of operations: ``-(tan(radians(tilt)) * n * spacing[2]) / spacing[1]``"""
+    gntan = math.tan(np.radians(tilt))
+    out = np.empty(int(depth), np.float64)
+    for n in range(int(depth)):
+        offset = gntan * n * spacing[2]
+        out[n] = -offset / spacing[1]
+    return out
+
+
+def fix_gantry_tilt(matrix: np.ndarray, spacing, tilt, masks=()):
+    """``imagedata_utils.FixGantryTilt(matrix, spacing, tilt)`` (invesalius/data/imagedata_utils.py:143-154), in place and
+    bit for bit: slice n becomes ``scipy.ndimage.shift(slice, (shift_n, 0), cval=matrix.min())`` -- cubic spline, mode
+    "constant", int16 -- with the minimum taken anew before every slice (HIP: csrc/k_imagegeo.hip; the arithmetic is
+    csrc/imagegeo_math.h).  A bound image is corrected in its mirror and written to the host once.  The reference runs this
+    at import, before any mask exists; masks handed in `masks` are cleared like a flip clears them.  Returns the fill value
+    every slice was given."""
+    if not isinstance(matrix, np.ndarray) or matrix.dtype != np.int16 or matrix.ndim != 3:
+        raise TypeError("matrix must be a 3-D int16 array")
+    shifts = gantry_tilt_shifts(matrix.shape[0], spacing, tilt)
+    cvals = np.zeros(matrix.shape[0], np.int32)
+    L.check(L.lib().ivx_image_fix_gantry_tilt(L.ptr(matrix), L.i64(matrix.shape), L.i64(matrix.strides), L.ptr(shifts), L.ptr(cvals)),
+            "fix_gantry_tilt")
+    if hasattr(matrix, "flush"):
+        matrix.flush()
+    for mask in masks:
+        _clear_mask(mask)
+    return cvals
