@@ -37,8 +37,7 @@
 #include <stdlib.h>
 
 #include "flood_tiles.h"
-
-typedef short short8_t __attribute__((ext_vector_type(8)));
+#include "words_from_records.h" // short8_t, words_from_records
 
 namespace {
 
@@ -89,10 +88,18 @@ __global__ __launch_bounds__(256) void k_flood_candidates16(const short8_t *__re
     }
 }
 
-// int16 data with valid per-word (min, max) records (k_threshold.hip): lane = 16 voxels as above, every lane reads its word's
-// record first.  Wholly outside [lo, hi]: 0, nothing loaded.  Wholly inside: the image is skipped (BAR 0: 0xffff, BAR 1:
-// the barrier alone decides).  Mixed: the arithmetic above.  The next trip's record is requested before this trip's store.
-template <int BAR>
+// int16 data with valid per-word (min, max) records (k_threshold.hip).  Without a barrier the candidates are the threshold's
+// plane: one word per lane, words_from_records.h.
+__global__ __launch_bounds__(256) void k_flood_candidates_words(const short8_t *__restrict__ data, const unsigned *__restrict__ ranges,
+                                                                int64_t nwords, double t0, double t1,
+                                                                unsigned long long *__restrict__ cand) {
+    const int lo = (int)ceil(t0 < -70000.0 ? -70000.0 : t0), hi = (int)floor(t1 > 70000.0 ? 70000.0 : t1); // integer data
+    words_from_records(data, ranges, nwords, lo, hi, cand);
+}
+
+// With a uint8 barrier (out != fill): lane = 16 voxels as in k_flood_candidates16, every lane reads its word's record first.
+// Wholly outside [lo, hi]: 0, nothing loaded.  Wholly inside: the image is skipped, the barrier alone decides.  Mixed: the
+// arithmetic above.  The next trip's record is loaded ahead in the source only: the compiler waits for it at the loop's head.
 __global__ __launch_bounds__(256) void k_flood_candidates16_ranges(const short8_t *__restrict__ data,
                                                                    const uint4 *__restrict__ bar,
                                                                    const unsigned *__restrict__ ranges, int64_t nchunks,
@@ -123,7 +130,7 @@ __global__ __launch_bounds__(256) void k_flood_candidates16_ranges(const short8_
                     m |= (v >= lo && v <= hi) ? (1u << e) : 0u;
                 }
             }
-            if (BAR == 1 && m) {
+            if (m) {
                 const uint4 q = bar[c];
                 const unsigned bw[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
@@ -1365,10 +1372,10 @@ extern "C" int ivx_dev_flood_candidates_ranges(const ivx_flood_plan *p, const in
     const int gg = (int)(blocks < 16384 ? blocks : 16384);
     hipStream_t st = ivx::S(stream);
     if (barrier_mode == 0)
-        hipLaunchKernelGGL((k_flood_candidates16_ranges<0>), dim3(gg), dim3(256), 0, st, (const short8_t *)data, (const uint4 *)barrier,
-                           (const unsigned *)ranges, nchunks, t0, t1, fill, (uint16_t *)cand);
+        hipLaunchKernelGGL(k_flood_candidates_words, dim3(words_grid(nchunks / 4)), dim3(WORDS_PER_WG), 0, st, (const short8_t *)data,
+                           (const unsigned *)ranges, nchunks / 4, t0, t1, (unsigned long long *)cand);
     else
-        hipLaunchKernelGGL((k_flood_candidates16_ranges<1>), dim3(gg), dim3(256), 0, st, (const short8_t *)data, (const uint4 *)barrier,
+        hipLaunchKernelGGL(k_flood_candidates16_ranges, dim3(gg), dim3(256), 0, st, (const short8_t *)data, (const uint4 *)barrier,
                            (const unsigned *)ranges, nchunks, t0, t1, fill, (uint16_t *)cand);
     IVX_LAUNCH_CHECK();
     return IVX_OK;

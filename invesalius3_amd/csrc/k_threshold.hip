@@ -10,8 +10,8 @@
 // (one 16-B store): 64 lanes x 16 B = 1 KiB per wave instruction, fully coalesced; a grid-stride loop over
 // <= 2048*8 workgroups keeps every CU's memory pipe full.  No LDS, no MFMA.
 #include "ivx_internal.h"
+#include "words_from_records.h" // short8_t, quad_xor1/2, words_from_records
 
-typedef short short8_t __attribute__((ext_vector_type(8)));
 typedef unsigned char uchar16_t __attribute__((ext_vector_type(16)));
 
 namespace {
@@ -76,9 +76,7 @@ __global__ __launch_bounds__(256) void k_threshold16_bits(const short8_t *__rest
 // so a threshold of an unchanged image reads 4 B per word and then only the mixed lines (2 B/voxel -> ~0.3 B/voxel).
 // The four lanes of a word are the four lanes of a DPP quad: c = 256 * k + threadIdx.x, so c & 3 == lane & 3, and
 // nchunks % 4 == 0 (dx % 64 == 0) keeps a quad together at the loop's end.
-__device__ __forceinline__ int quad_xor1(int v) { return __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xf, 0xf, true); } // quad_perm [1,0,3,2]
-__device__ __forceinline__ int quad_xor2(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xf, 0xf, true); } // quad_perm [2,3,0,1]
-
+// (quad_xor1 / quad_xor2: words_from_records.h)
 __device__ __forceinline__ unsigned word_record(const short8_t a, const short8_t b) {
     int mn = a[0], mx = a[0];
 #pragma unroll
@@ -130,13 +128,15 @@ __global__ __launch_bounds__(256) void k_threshold16_bits_build(const short8_t *
 }
 
 // The threshold of an image whose records are valid.  Every lane reads its word's record (the four lanes of a word share
-// the address; a wave reads 64 contiguous bytes) and only the lanes of a mixed word load voxels; the record of the next
-// trip is requested before this trip's stores.  The records are trusted: the image is not looked at where they decide.
-// Measured: 193 MB instead of 422 MB, but 54 us instead of 65 -- the stores alone take 21 us and the sparse
-// reads of the mixed lines add their own time to that whatever the kernel's shape (several chunks in flight per lane, the
+// the address; a wave reads 64 contiguous bytes) and only the lanes of a mixed word load voxels.  The next trip's record is
+// loaded ahead in the source only: the compiler waits for it (vmcnt(0)) at the loop's head, so a trip is up to two dependent
+// waits, record then voxels.  The records are trusted: the image is not looked at where they decide.
+// Measured: 193 MB instead of 422 MB, but 54 us instead of 65 -- the stores alone take 21 us and the reads of
+// the mixed lines add their time to that in every variant of this loop that was tried (several chunks in flight per lane, the
 // mixed words compacted through LDS and non-temporal mask stores all measured the same or slower), so this is the plain form.
-// Since the two halves add, the resident step no longer runs them in one kernel: k_threshold16_plane_use below is this kernel
-// without the mask (29.7 us), and the mask's bytes are written by the region growing's apply.  This form stays for callers
+// What those variants kept is the loop's chain of dependent waits; the plane-only kernel below sheds it and halves its time.
+// Since the two halves add, the resident step no longer runs them in one kernel: k_threshold16_plane_use below makes the
+// plane alone, and the mask's bytes are written by the region growing's apply.  This form stays for callers
 // that want mask and plane from one call, for volumes past the Infinity Cache that no region growing follows, and for A/B.
 __global__ __launch_bounds__(256) void k_threshold16_bits_use(const short8_t *__restrict__ img, uchar16_t *__restrict__ mask,
                                                               uint16_t *__restrict__ bits, const unsigned *__restrict__ ranges,
@@ -186,7 +186,7 @@ __global__ __launch_bounds__(256) void k_threshold16_bits_use(const short8_t *__
 // by the pass that has to write mask bytes anyway (ivx_dev_mask_from_planes, k_flood.hip).  The 134 MB of stores that the
 // 512^3 step's threshold spent on bytes nobody read before the flood rewrote them are gone from this pass.  Measured at 512^3
 // (profiles/mask_deferred_ab.md): use mode 55.0 -> 29.7 us, build mode 70.3 -> 58.6 us; the apply that now writes every chunk
-// 12.3 -> 22.2 us.
+// 12.3 -> 22.2 us.  Use mode has since gone to one word per lane: 30.2 -> 14.4 us (profiles/threshold_words_ab.md).
 __device__ __forceinline__ unsigned chunk_bits(const short8_t a, const short8_t b, int lo, int hi) {
     unsigned m = 0;
 #pragma unroll
@@ -214,34 +214,12 @@ __global__ __launch_bounds__(256) void k_threshold16_plane(const short8_t *__res
     }
 }
 
-// k_threshold16_bits_use without the mask: 4 B of record per word, the mixed words' lines, 2 B of plane per chunk
-__global__ __launch_bounds__(256) void k_threshold16_plane_use(const short8_t *__restrict__ img, uint16_t *__restrict__ bits,
-                                                               const unsigned *__restrict__ ranges, int64_t nchunks, int lo,
+// The plane alone from valid records: one word per lane (words_from_records.h), 4 B of record and 8 B of plane per word plus
+// the mixed words' lines.
+__global__ __launch_bounds__(256) void k_threshold16_plane_use(const short8_t *__restrict__ img, unsigned long long *__restrict__ bits,
+                                                               const unsigned *__restrict__ ranges, int64_t nwords, int lo,
                                                                int hi) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= nchunks) return;
-    unsigned rec = ranges[c >> 2];
-    for (;;) {
-        const int64_t cn = c + stride;
-        unsigned rec_next = 0;
-        if (cn < nchunks) rec_next = ranges[cn >> 2];
-        const int mn = (int)(short)(rec & 0xffffu), mx = (int)(short)(rec >> 16);
-        unsigned m;
-        if (mn >= lo && mx <= hi) {
-            m = 0xffffu;
-        } else if (mx < lo || mn > hi) {
-            m = 0;
-        } else {
-            const short8_t a = __builtin_nontemporal_load(&img[2 * c]);
-            const short8_t b = __builtin_nontemporal_load(&img[2 * c + 1]);
-            m = chunk_bits(a, b, lo, hi);
-        }
-        bits[c] = (uint16_t)m;
-        if (cn >= nchunks) break;
-        c = cn;
-        rec = rec_next;
-    }
+    words_from_records(img, ranges, nwords, lo, hi, bits);
 }
 
 // scalar path: tails, unaligned pointers, slices whose size is not a multiple of 16
@@ -390,8 +368,8 @@ extern "C" int ivx_dev_threshold_i16_plane_ranges(const int16_t *img, int64_t dz
         hipLaunchKernelGGL(k_threshold16_plane<true>, dim3(ranges_grid(nchunks)), dim3(256), 0, ivx::S(stream),
                            (const short8_t *)img, (uint16_t *)bits, (unsigned *)ranges, nchunks, lo, hi);
     else
-        hipLaunchKernelGGL(k_threshold16_plane_use, dim3(ranges_grid(nchunks)), dim3(256), 0, ivx::S(stream),
-                           (const short8_t *)img, (uint16_t *)bits, (const unsigned *)ranges, nchunks, lo, hi);
+        hipLaunchKernelGGL(k_threshold16_plane_use, dim3(words_grid(n / 64)), dim3(WORDS_PER_WG), 0, ivx::S(stream),
+                           (const short8_t *)img, (unsigned long long *)bits, (const unsigned *)ranges, n / 64, lo, hi);
     IVX_LAUNCH_CHECK();
     return IVX_OK;
 }
