@@ -1227,6 +1227,56 @@ int ivx_mask_preview(const uint8_t *matrix, const int64_t shape[3], const int64_
                      const uint32_t *prefix, const ivx_volren_params *p, void *out, float *depth);
 
 /* ------------------------------------------------------------------------------------------------
+ * slice display: window/level, colour tables, mask and aux overlays, blend -- one launch per picture
+ *   replaces Slice.GetSlices (invesalius/data/slice_.py:746-830) with do_ww_wl, do_colour_image, do_colour_mask,
+ *   do_custom_colour and do_blend (:1656-1695, :1771-1873).  The arithmetic of VTK's filters is stated as rules R1 - R7 in
+ *   DESIGN.md section 7l and csrc/slice_show_math.h; the byte tables come from invesalius3_amd/slice_display.py.
+ * Operands are 2-D views of h x w pixels with byte strides of any sign (row, element):
+ *   image  what image_kind says: int16 or float64 values (the window/level stage must be on), or a picture's bytes --
+ *          IVX_SHOW_U8 one grey byte per pixel (an element stride of 3 reads the first channel of an RGB picture),
+ *          IVX_SHOW_RGB8 three bytes per pixel (the window/level stage must be off)
+ *   mask   uint8 bytes coloured through table 1 when IVX_SHOW_MASK is on, else RGBA pixels (4 bytes each); may be null
+ *   aux    the same with IVX_SHOW_AUX and table 2; may be null
+ *   out    dense h x w x out_channels bytes.  3: the picture.  4: the one overlay given, coloured and not blended (the
+ *          reference's do_colour_mask / do_custom_colour seams); IVX_SHOW_BLEND must then be off.
+ * tables: 3 x 256 RGBA bytes (image table: the HSV table of R2, or the plist table of R3; mask table R5; aux table R6), then
+ *   n_nodes float64 node values (ascending) and 3 n_nodes float64 colours c / 255 (R4); 8-byte aligned.
+ * ivx_dev_slice_show  device pointers; only enqueues on `stream`.
+ * ivx_slice_show      host pointers.  Views of a registered array (ivx_host_register) are gathered from its mirror: nothing
+ *                     but the tables goes host -> device and exactly h * w * out_channels bytes come back; otherwise the
+ *                     views alone are uploaded.
+ * ---------------------------------------------------------------------------------------------- */
+#define IVX_SHOW_WWWL 1
+#define IVX_SHOW_COLOUR 2
+#define IVX_SHOW_MASK 4
+#define IVX_SHOW_AUX 8
+#define IVX_SHOW_BLEND 16
+#define IVX_SHOW_I16 0
+#define IVX_SHOW_F64 1
+#define IVX_SHOW_U8 2
+#define IVX_SHOW_RGB8 3
+#define IVX_SHOW_MAX_NODES 256
+typedef struct ivx_slice_show_params {
+    int32_t image_kind;   /* IVX_SHOW_I16 .. IVX_SHOW_RGB8 */
+    int32_t mode;         /* 0 OTHER (R1 + R2), 1 PLIST (R3), 2 WIDGET (R4) */
+    int32_t stages;       /* IVX_SHOW_* bits */
+    int32_t n_nodes;      /* WIDGET: 1 .. IVX_SHOW_MAX_NODES */
+    int32_t aux_max;      /* largest key of the aux colour dict (R6) */
+    int32_t out_channels; /* 3 or 4 */
+    double window_width, window_level;
+    double table_min, table_max; /* R2: get_LUT_value_255((image min, image max), ww, wl) */
+} ivx_slice_show_params;
+int ivx_slice_show_tables_bytes(int n_nodes, size_t *nbytes);
+int ivx_dev_slice_show(const void *image, int64_t image_row_stride, int64_t image_elem_stride, const uint8_t *mask,
+                       int64_t mask_row_stride, int64_t mask_elem_stride, const uint8_t *aux, int64_t aux_row_stride,
+                       int64_t aux_elem_stride, int64_t h, int64_t w, const ivx_slice_show_params *p, const void *tables,
+                       uint8_t *out, void *stream);
+int ivx_slice_show(const void *image, int64_t image_row_stride, int64_t image_elem_stride, const uint8_t *mask,
+                   int64_t mask_row_stride, int64_t mask_elem_stride, const uint8_t *aux, int64_t aux_row_stride,
+                   int64_t aux_elem_stride, int64_t h, int64_t w, const ivx_slice_show_params *p, const void *tables,
+                   uint8_t *out);
+
+/* ------------------------------------------------------------------------------------------------
  * bench / test input made in HBM (no reference counterpart): a CT-like int16 phantom -- six Gaussian blobs + sinusoid +
  * hashed N(0,25) noise, clipped to [-1024, 3071] -- for the slices [z0, z0 + dz) of a z_total-slice volume; deterministic
  * in (seed, global voxel index), so slabs made by different ranks tile the whole volume.  centres_zyx_sigma: 6 x (cz, cy,

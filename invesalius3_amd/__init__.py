@@ -5,6 +5,8 @@ Host-side mirror of the reference interface for that path and the stages next to
     invesalius3_amd.invesalius_rs      <-> invesalius_rs/__init__.py (floodfill, mips, transforms, mesh, mask-editing names)
     invesalius3_amd.slice_             <-> invesalius/data/slice_.py threshold / projection / boolean / measurement call sites, flip / swap axes;
                                            invesalius/data/imagedata_utils.py FixGantryTilt
+    invesalius3_amd.slice_display      <-> the display state of Slice (window/level, colour mode, nodes, aux) and the tables of
+                                           Slice.GetSlices' VTK filters (slice_.get_slices)
     invesalius3_amd.mask               <-> invesalius/data/mask.py fill_holes_auto
     invesalius3_amd.styles             <-> invesalius/data/styles.py region-growing tool (do_3d_seg, do_rg_confidence), slice tools
     invesalius3_amd.cursor             <-> invesalius/data/cursor_actors.py brush footprints, and the window a dab covers

@@ -84,7 +84,11 @@ def _declare(lib):
                        ("ivx_image_tilt_scratch_bytes", [c_i64, c_i64, c_i64, ctypes.POINTER(sz)]),
                        ("ivx_dev_image_fix_gantry_tilt", [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, sz, c_vp, c_vp]),
                        ("ivx_image_fix_gantry_tilt", [c_vp, i64p, i64p, c_vp, c_vp]),
-                       ("ivx_host_zero", [c_vp, sz]), ("ivx_host_register_zero", [c_vp, sz, u64p])):
+                       ("ivx_host_zero", [c_vp, sz]), ("ivx_host_register_zero", [c_vp, sz, u64p]),
+                       # the slice display: three 2-D views (pointer, row stride, element stride), h, w, parameters, tables, out
+                       ("ivx_slice_show_tables_bytes", [ctypes.c_int, ctypes.POINTER(sz)]),
+                       ("ivx_dev_slice_show", [c_vp, c_i64, c_i64] * 3 + [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
+                       ("ivx_slice_show", [c_vp, c_i64, c_i64] * 3 + [c_i64, c_i64, c_vp, c_vp, c_vp])):
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = args, ctypes.c_int
 

@@ -371,9 +371,10 @@ class DeviceVolume:
         for b in (self.image, self.mask, self.out_mask, self.cand, self.reached, self._mbits, self.flood_scratch,
                   self._mc_scratch, self._tris, self._verts, self._faces, self._gate, getattr(self, "_range_buf", None),
                   getattr(self, "_ranges", None),
-                  getattr(self, "prob", None)):
+                  getattr(self, "prob", None), getattr(self, "_show_tables", None), getattr(self, "_show_out", None)):
             if b is not None:
                 b.close()
+        self._show_tables = self._show_out = None
         if self.stream is not None:
             L.lib().ivx_stream_destroy(self.stream)
             self.stream = None
@@ -660,6 +661,70 @@ class DeviceVolume:
             raise ValueError("crop limits must not be negative")
         box = L.i64([max(zi - 1, 0), min(zf + 1, self.dz), max(yi - 1, 0), min(yf + 1, self.dy), max(xi - 1, 0), min(xf + 1, self.dx)])
         L.check(L.lib().ivx_dev_mask_crop(self.mask.ptr, c64(self.dz), c64(self.dy), c64(self.dx), box, self.stream), "crop_mask")
+
+    # -- slice display ---------------------------------------------------------------------
+    def _image_min_max(self):
+        """(min, max) of the resident image as int16 numbers, as ``Slice.matrix.min()`` gives them; kept while `image_range()`
+        holds"""
+        if not self._range_valid or getattr(self, "_range_host", None) is None:
+            buf = self.image_range()
+            L.check(L.lib().ivx_stream_synchronize(self.stream))
+            lo, hi = buf.download((2,), np.float32)
+            self._range_host = (np.int16(lo), np.int16(hi))
+        return self._range_host
+
+    def show_slice(self, orientation: str, n: int, state, image: DeviceBuffer | None = None, image_dtype=np.int16, mask: bool = True,
+                   aux: DeviceBuffer | None = None, image_range=None, download: bool = True):
+        """slice_.get_slices on the resident volume: the (h, w, 3) uint8 picture of slice `n` from one launch of
+        ivx_dev_slice_show on the volume's stream, reading the image, the resident mask and `aux` in place through their
+        strides (a sagittal slice is gathered by the kernel).  `image`: the dense (h, w) device output of a projection kernel
+        (`project`, `mida`, the resampler; `image_dtype` int16, or float64 for MeanIP) shown in place of the plain slice.
+        `mask`: there is a current mask (the resident one, drawn when ``state.mask_shown``; it has no flag cells, so no lazy
+        threshold).  `aux`: the uint8 block of the volume's shape that ``state.to_show_aux`` names (`self.mask` for SELECT).
+        Returns the picture, or with ``download=False`` the DeviceBuffer that holds it (valid until the next call, queued on
+        `self.stream`)."""
+        from . import slice_display as D
+
+        h, w, first, rs, es = self._slice_geometry(orientation, n)
+        kind = {np.dtype(np.int16): D.IMG_I16, np.dtype(np.float64): D.IMG_F64}.get(np.dtype(image_dtype))
+        if kind is None:
+            raise TypeError("image_dtype must be int16 or float64")
+        isz = 2 if kind == D.IMG_I16 else 8
+        if image is not None:
+            if image.nbytes < h * w * isz:
+                raise ValueError("the projection's block holds %d bytes, the picture needs %d" % (image.nbytes, h * w * isz))
+            ip, irs, ies = image.ptr, w * isz, isz
+        else:
+            if kind != D.IMG_I16:
+                raise TypeError("the resident image is int16")
+            ip, irs, ies = self.image.raw_at(first * 2), rs * 2, es * 2
+        mp = None
+        if mask and state.mask_shown:
+            mp = ctypes.c_void_p(self.mask_bytes().value + first)
+        aux_colours = D.aux_colour_dict(state, bool(mask))
+        ap = None
+        if aux_colours is not None:
+            if aux is None:
+                raise TypeError("the aux overlay %r needs its device block" % state.to_show_aux)
+            if aux.nbytes < self.n:
+                raise ValueError("the aux block is smaller than the volume")
+            base = self.mask_bytes() if aux is self.mask else aux.ptr
+            ap = ctypes.c_void_p(base.value + first)
+        if state.from_ == D.OTHER and image_range is None:
+            image_range = self._image_min_max()
+        p, blob = D.build(state, kind, D.ST_ALL, image_range=image_range, have_mask=mp is not None, aux_colours=aux_colours)
+        if getattr(self, "_show_tables", None) is None or self._show_tables.nbytes < blob.nbytes:
+            self._show_tables = DeviceBuffer(3072 + 32 * D.MAX_NODES)
+        if getattr(self, "_show_out", None) is None or self._show_out.nbytes < h * w * 3:
+            self._show_out = DeviceBuffer(h * w * 3)
+        L.check(L.lib().ivx_stream_synchronize(self.stream))  # (an earlier picture's launch may still read the tables block)
+        self._show_tables.upload(blob)
+        L.check(L.lib().ivx_dev_slice_show(ip, c64(irs), c64(ies), mp, c64(rs), c64(es), ap, c64(rs), c64(es), c64(h), c64(w), ctypes.byref(p),
+                                           self._show_tables.ptr, self._show_out.ptr, self.stream), "show_slice")
+        if not download:
+            return self._show_out
+        L.check(L.lib().ivx_stream_synchronize(self.stream))
+        return self._show_out.download((h, w, 3), np.uint8)
 
     # -- image geometry tools (DESIGN 7k) ----------------------------------------------------------------
     def _after_image_geometry(self, shape=None, spacing=None):
@@ -1102,6 +1167,7 @@ class DeviceVolume:
             self._range_buf = DeviceBuffer(64)
             self._range_valid = False
         if not self._range_valid:
+            self._range_host = None  # (show_slice's host copy of the two numbers)
             L.check(L.lib().ivx_dev_minmax_f32(L.I16, self.image.raw, c64(self.n), self._range_buf.ptr, self.stream), "minmax")
             self._range_valid = True
         return self._range_buf

@@ -10,6 +10,7 @@
     python -m invesalius3_amd.headless CASE.inv3 --segment brain --weights brain_mri_t1.pt --stl brain.stl
     python -m invesalius3_amd.headless CASE.inv3 --render "Bone + Skin" --presets-dir DIR --view iso --png out.png
     python -m invesalius3_amd.headless CASE.inv3 --threshold 226 3071 --mask-preview iso --mask-colour 0 1 0 --png mask.png
+    python -m invesalius3_amd.headless CASE.inv3 --threshold 226 3071 --show-slice AXIAL 40 --window 2000 300 --colour-table Rainbow --png slice.png
 
 What the reference does through its GUI for the same result: Slice.SetMaskThreshold / do_threshold_to_all_slices
 (invesalius/data/slice_.py:1240-1247, 1739-1769), the Image Filters dialog (slice_.py:2330-2539), the deep-learning segmentation (segmentation/deep_learning/segment.py), the 3-D view's volume rendering (data/volume.py:575-707), the region-growing tool (styles.py:3151-3216),
@@ -75,6 +76,10 @@ def run(args) -> dict:
             if _render_only(args):
                 out["gpu_ms"] = {k: round(float(sum(v)), 4) for k, v in vol.timer.collect().items()}
                 return out
+        if args.show_slice is not None and _show_only(args):
+            _show_slice(args, proj, vol, False, out)  # no mask was asked for: the image alone
+            out["gpu_ms"] = {k: round(float(sum(v)), 4) for k, v in vol.timer.collect().items()}
+            return out
         segmented = False
         if args.segment is not None:
             # the Segmentation menu's deep-learning tool (BrainSegmentProcess / TracheaSegmentProcess, segment.py:505-541,
@@ -137,6 +142,8 @@ def run(args) -> dict:
             if args.png:
                 V.write_png(args.png, rgba8)
                 out["mask_preview"]["png"] = args.png
+        if args.show_slice is not None:
+            _show_slice(args, proj, vol, True, out)
         mask = vol.download_mask()
         out["mask_voxels"] = int(np.count_nonzero(mask >= 127))
         with vol.timer.span("surface"):
@@ -295,6 +302,60 @@ def _image_geometry(args, proj, bound, out):
     out["shape"], out["spacing"] = list(proj.matrix.shape), list(proj.spacing)
 
 
+SHOW_PROJECTIONS = {"normal": 0, "maxip": 1, "minip": 2, "meanip": 3, "mida": 5, "contour_mip": 6, "contour_lmip": 7, "contour_mida": 8}
+
+
+def display_state(args, proj):
+    """the DisplayState of --show-slice: --window (default: the project's), --colour-table (one of const.SLICE_COLOR_TABLE,
+    or a colour list of --presets-dir, shown like the reference's PLIST mode), --mask-colour at the default mask opacity"""
+    from . import slice_display as D
+    from . import volume as V
+
+    ww, wl = args.window if args.window is not None else (proj.window, proj.level)
+    st = D.DisplayState(window_width=float(ww), window_level=float(wl), mask_colour=tuple(args.mask_colour))
+    name = args.colour_table
+    if name is not None:
+        tables = {k.strip().lower(): k for k in D.SLICE_COLOR_TABLE}
+        if name.strip().lower() in tables:
+            st.set_colour_table(tables[name.strip().lower()])
+        elif args.presets_dir is None:
+            raise KeyError("--colour-table %r is none of %s: a colour list needs --presets-dir DIR" % (name, sorted(tables.values())))
+        else:
+            st.set_plist(np.asarray(V.load_color_list(name, args.presets_dir)).astype(np.int64))
+    return st
+
+
+def _show_slice(args, proj, vol, with_mask, out):
+    """--show-slice: Slice.GetSlices (slice_.py:746-830) of one slice -- or of a slab's projection, computed from the bound
+    image and handed over on the device -- with the resident mask drawn over it; written as a PNG (alpha 255)"""
+    from . import slice_ as sl
+    from . import volume as V
+    from .device import DeviceBuffer
+
+    ori, n = args.show_slice[0].upper(), int(args.show_slice[1])
+    st = display_state(args, proj)
+    tp = SHOW_PROJECTIONS[args.projection]
+    block, dtype = None, np.int16
+    with vol.timer.span("show_slice"):
+        if tp != sl.PROJECTION_NORMAL:
+            image = sl.get_image_slice(proj.matrix, ori, n, args.slab, False, 1.0, tp, st.window_level)
+            block, dtype = DeviceBuffer(image.nbytes), image.dtype
+            block.upload(image)
+        rgb = vol.show_slice(ori, n, st, image=block, image_dtype=dtype, mask=with_mask)
+    if block is not None:
+        block.close()
+    out["show_slice"] = {"orientation": ori, "slice": n, "window": [st.window_width, st.window_level], "colour_table": args.colour_table,
+                         "projection": args.projection, "slab": args.slab if tp else 1, "mask": bool(with_mask), "size": [rgb.shape[1], rgb.shape[0]]}
+    if args.png:
+        V.write_png(args.png, np.concatenate([rgb, np.full(rgb.shape[:2] + (1,), 255, np.uint8)], axis=2))
+        out["show_slice"]["png"] = args.png
+
+
+def _show_only(args) -> bool:
+    """--show-slice without --threshold, --mask or --segment: there is no mask to draw"""
+    return args.threshold is None and args.segment is None and "--mask" not in (args.argv or [])
+
+
 def _render_only(args) -> bool:
     """--render without anything that asks for a mask or a surface: the image is all there is to make"""
     return (args.threshold is None and args.segment is None and not args.seed and not args.stl and not args.save
@@ -343,6 +404,14 @@ def main(argv=None) -> int:
                          "the reference's Mask 3D preview with rendering 0 (composite) or 1 (iso-surface at 127)")
     ap.add_argument("--mask-colour", nargs=3, type=float, metavar=("R", "G", "B"), default=(0.0, 1.0, 0.0),
                     help="the mask's colour, 0..1 each (default 0 1 0)")
+    ap.add_argument("--show-slice", nargs=2, metavar=("ORIENTATION", "N"), default=None,
+                    help="the slice viewer's picture of slice N (AXIAL, CORONAL or SAGITAL): window/level, colour table and the "
+                         "mask's overlay when --threshold or --mask is given; written to --png")
+    ap.add_argument("--window", nargs=2, type=float, metavar=("WW", "WL"), default=None, help="window width and level of --show-slice (default: the project's)")
+    ap.add_argument("--colour-table", metavar="NAME", default=None,
+                    help="colour table of --show-slice: Default, Hue, Saturation, Desert, Rainbow, Ocean, Inverse Gray, or a colour list of --presets-dir")
+    ap.add_argument("--projection", choices=tuple(SHOW_PROJECTIONS), default="normal", help="--show-slice shows this projection of a slab of --slab slices")
+    ap.add_argument("--slab", type=int, default=1, metavar="K", help="slices in the projected slab (default 1)")
     ap.add_argument("--presets-dir", metavar="DIR", default=None, help="the raycasting presets directory (with color_list/)")
     ap.add_argument("--view", choices=("front", "back", "left", "right", "top", "bottom", "iso"), default="iso")
     ap.add_argument("--size", nargs=2, type=int, metavar=("W", "H"), default=(512, 512), help="image size (default 512 512)")
@@ -413,8 +482,19 @@ def main(argv=None) -> int:
             ap.error("--size W H must be positive")
         if not all(0.0 <= c <= 1.0 for c in args.mask_colour):
             ap.error("--mask-colour R G B must lie in 0..1")
-    elif args.png is not None:
-        ap.error("--png needs --render or --mask-preview")
+    elif args.png is not None and args.show_slice is None:
+        ap.error("--png needs --render, --mask-preview or --show-slice")
+    if args.show_slice is not None:
+        if args.show_slice[0].upper() not in ("AXIAL", "CORONAL", "SAGITAL") or not args.show_slice[1].lstrip("-").isdigit():
+            ap.error("--show-slice takes AXIAL, CORONAL or SAGITAL and a slice number")
+        if args.render is not None or args.mask_preview is not None:
+            ap.error("--show-slice, --render and --mask-preview make one picture each: name one of them")
+        if args.slab < 1:
+            ap.error("--slab K must be positive")
+        if args.window is not None and not args.window[0] > 0:
+            ap.error("--window WW WL: the width must be positive")
+    elif args.window is not None or args.colour_table is not None or args.projection != "normal" or args.slab != 1:
+        ap.error("--window, --colour-table, --projection and --slab need --show-slice")
     print(json.dumps(run(args)))
     return 0
 

@@ -339,8 +339,16 @@ def get_mask_slice(mask_matrix, image_matrix, orientation: str, n: int, threshol
     the slice's flag cell -- ``[n+1,0,0]`` AXIAL, ``[0,n+1,0]`` CORONAL, ``[0,0,n+1]`` SAGITAL -- is 0, the slice
     ``matrix[n+1, 1:, 1:]`` (and siblings) is thresholded with the preserve rule and the flag set to 1, in place; returns
     a copy of the slice.  (The buffer_slices cache in front of it stays with the caller.)"""
+    mview = _thresholded_slice_view(mask_matrix, image_matrix, orientation, n, threshold_range)
+    return np.array(mview, dtype=mask_matrix.dtype)
+
+
+def _thresholded_slice_view(mask_matrix, image_matrix, orientation, n, threshold_range):
+    """the lazy threshold of get_mask_slice; returns the slice as a view of the matrix"""
     mview, flag, _ = _slice_views(mask_matrix, image_matrix, orientation, n)
     if flag.reshape(-1)[0] == 0:
+        if threshold_range is None:
+            raise ValueError("slice %d (%s) has not been thresholded yet (its flag is 0): pass the mask's threshold_range" % (n, orientation))
         ax = _axis(orientation)
         order = (ax,) + tuple(a for a in range(3) if a != ax)  # the slice's axis in front: one "axial" slice of a strided volume
         mt, it = mask_matrix.transpose(order), image_matrix.transpose(order)
@@ -348,7 +356,7 @@ def get_mask_slice(mask_matrix, image_matrix, orientation: str, n: int, threshol
         img1, m2 = it[n:n + 1], mt[n:n + 2]
         L.check(L.lib().ivx_threshold_all_slices(L.ptr(img1), L.i64(img1.shape), L.i64(img1.strides), ctypes.c_int(lo), ctypes.c_int(hi),
                                                  ctypes.c_int(1), ctypes.c_int(1), L.ptr(m2), L.i64(m2.strides)), "get_mask_slice")
-    return np.array(mview, dtype=mask_matrix.dtype)
+    return mview
 
 
 def _op_runs(operations, ndabs):
@@ -598,3 +606,118 @@ def fix_gantry_tilt(matrix: np.ndarray, spacing, tilt, masks=()):
     for mask in masks:
         _clear_mask(mask)
     return cvals
+
+
+# ---- the slice display ------------------------------------------------------------------------------------------------
+def _plane(a, orientation, n):
+    sl = [slice(None)] * 3
+    sl[_axis(orientation)] = int(n)
+    return a[tuple(sl)]
+
+
+def get_aux_slice(aux_matrix: np.ndarray, orientation: str, n: int) -> np.ndarray:
+    """Slice.get_aux_slice (invesalius/data/slice_.py:1177-1184): slice `n` of an aux matrix (of the image's shape)"""
+    return np.array(_plane(aux_matrix, orientation, n))
+
+
+def _picture(a, what, channels):
+    if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != channels:
+        raise TypeError("%s: a (h, w, %d) uint8 array" % (what, channels))
+    return a if a.strides[2] == 1 else np.ascontiguousarray(a)
+
+
+def _image_kind(image, what):
+    from . import slice_display as D
+
+    if not isinstance(image, np.ndarray) or image.ndim != 2 or image.dtype not in (np.dtype(np.int16), np.dtype(np.float64)):
+        raise TypeError("%s: a 2-D int16 (or, for MeanIP, float64) array" % what)
+    return D.IMG_I16 if image.dtype == np.int16 else D.IMG_F64
+
+
+def do_ww_wl(image: np.ndarray, state) -> np.ndarray:
+    """Slice.do_ww_wl (slice_.py:1656-1695) on a 2-D int16 / float64 slice: the (h, w, 3) picture of rule R1 (grey), R3 (PLIST)
+    or R4 (WIDGET)."""
+    from . import slice_display as D
+
+    p, blob = D.build(state, _image_kind(image, "do_ww_wl"), D.ST_WWWL)
+    return D.run(p, blob, image, None, None, *image.shape)
+
+
+def do_colour_image(imagedata: np.ndarray, state, image_range) -> np.ndarray:
+    """Slice.do_colour_image (slice_.py:1771-1795) on do_ww_wl's picture: the identity in the PLIST and WIDGET modes, else the
+    HSV table of rule R2 indexed by the first channel; `image_range` is the whole image's (min, max)."""
+    from . import slice_display as D
+
+    imagedata = _picture(imagedata, "do_colour_image", 3)
+    if state.from_ in (D.PLIST, D.WIDGET):
+        return imagedata
+    p, blob = D.build(state, D.IMG_U8, D.ST_COLOUR, image_range=image_range)
+    return D.run(p, blob, imagedata[:, :, 0], None, None, *imagedata.shape[:2])
+
+
+def do_colour_mask(mask_slice: np.ndarray, state) -> np.ndarray:
+    """Slice.do_colour_mask (slice_.py:1797-1827): the (h, w, 4) RGBA overlay of rule R5 for a 2-D uint8 mask slice"""
+    from . import slice_display as D
+
+    if mask_slice.dtype != np.uint8 or mask_slice.ndim != 2:
+        raise TypeError("do_colour_mask: a 2-D uint8 array")
+    p, blob = D.build(state, D.IMG_U8, D.ST_MASK, have_mask=True, out_channels=4)
+    return D.run(p, blob, None, mask_slice, None, *mask_slice.shape)
+
+
+def do_custom_colour(aux_slice: np.ndarray, map_colours: dict) -> np.ndarray:
+    """Slice.do_custom_colour (slice_.py:1829-1859): the (h, w, 4) RGBA overlay of rule R6; the smallest key must be 0"""
+    from . import slice_display as D
+
+    if aux_slice.dtype != np.uint8 or aux_slice.ndim != 2:
+        raise TypeError("do_custom_colour: a 2-D uint8 array")
+    p, blob = D.build(D.DisplayState(), D.IMG_U8, D.ST_AUX, aux_colours=map_colours, out_channels=4)
+    return D.run(p, blob, None, None, aux_slice, *aux_slice.shape)
+
+
+def do_blend(imagedata: np.ndarray, mask: np.ndarray) -> np.ndarray:
+    """Slice.do_blend (slice_.py:1861-1873): the RGBA overlay over the RGB picture at opacity 0.8, rule R7"""
+    from . import slice_display as D
+
+    imagedata, mask = _picture(imagedata, "do_blend", 3), _picture(mask, "do_blend", 4)
+    if imagedata.shape[:2] != mask.shape[:2]:
+        raise ValueError("do_blend: picture %r, overlay %r" % (imagedata.shape, mask.shape))
+    p, blob = D.build(D.DisplayState(), D.IMG_RGB8, D.ST_BLEND)
+    return D.run(p, blob, imagedata, mask, None, *imagedata.shape[:2])
+
+
+def get_slices(image_matrix, mask_matrix, orientation: str, slice_number: int, number_slices: int, state, inverted: bool = False,
+               border_size: float = 1.0, type_projection: int = PROJECTION_NORMAL, threshold_range=None, aux_matrix=None,
+               q_orientation=None, center=None, spacing=None, interp_method: int = 2, image_range=None) -> np.ndarray:
+    """``Slice.GetSlices`` (invesalius/data/slice_.py:746-830) without its buffer_slices cache: the final (h, w, 3) uint8
+    picture of slice `slice_number` -- window/level, colour table, the current mask's overlay (`mask_matrix`, the padded
+    matrix, or None; drawn when ``state.mask_shown``), then the aux overlay ``state.to_show_aux`` over `aux_matrix` -- from one
+    kernel launch (csrc/k_slice_show.hip; the rules are DESIGN 7l).  `state` is a slice_display.DisplayState.  A plain slice of
+    a bound image and mask crosses the link once, as the picture; a projection or a reoriented view is computed by
+    `get_image_slice` first (MIDA and the contour MIPs get ``state.window_level`` like in the reference).  A mask slice whose
+    flag is 0 is thresholded in place with `threshold_range` first, exactly like `get_mask_slice`.  `image_range`, the whole
+    image's (min, max) that the colour table's range needs, is taken with numpy per call like the reference does unless
+    given."""
+    from . import slice_display as D
+
+    reoriented = q_orientation is not None and bool(np.any(np.asarray(q_orientation)[1:]))
+    if type_projection == PROJECTION_NORMAL and not reoriented:
+        if not 0 <= int(slice_number) < image_matrix.shape[_axis(orientation)]:
+            raise IndexError("slice %d outside the volume" % slice_number)
+        image = _plane(image_matrix, orientation, slice_number)  # a view: a bound image is read from its mirror
+    else:
+        image = get_image_slice(image_matrix, orientation, slice_number, number_slices, inverted, border_size, type_projection,
+                                state.window_level, q_orientation, center, spacing, interp_method)
+    kind = _image_kind(image, "get_slices")
+    mask = None
+    if mask_matrix is not None and state.mask_shown:
+        mask = _thresholded_slice_view(mask_matrix, image_matrix, orientation, slice_number, threshold_range)
+    aux, aux_colours = None, D.aux_colour_dict(state, mask_matrix is not None)
+    if aux_colours is not None:
+        if aux_matrix is None or aux_matrix.dtype != np.uint8 or tuple(aux_matrix.shape) != tuple(image_matrix.shape):
+            raise TypeError("the aux overlay %r needs its uint8 matrix of the image's shape" % state.to_show_aux)
+        aux = _plane(aux_matrix, orientation, slice_number)
+    if state.from_ == D.OTHER and image_range is None:
+        image_range = (image_matrix.min(), image_matrix.max())
+    p, blob = D.build(state, kind, D.ST_ALL, image_range=image_range, have_mask=mask is not None, aux_colours=aux_colours)
+    return D.run(p, blob, image, mask, aux, *image.shape)
