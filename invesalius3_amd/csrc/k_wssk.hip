@@ -1020,7 +1020,7 @@ __global__ __launch_bounds__(256) void k_sk_level_plane(const uint16_t *__restri
 template <int CONN>
 __global__ __launch_bounds__(256) void k_sk_plateau_relax(WsGeom g, const uint16_t *__restrict__ I, const uint16_t *__restrict__ C,
                                                           unsigned long long *tau, const uint32_t *__restrict__ list, uint8_t *dirty,
-                                                          uint32_t c, SkState *st, const uint32_t *__restrict__ nlist, uint32_t offset,
+                                                          uint32_t c, uint32_t *__restrict__ tgen, const uint32_t *__restrict__ nlist, uint32_t offset,
                                                           const unsigned long long *__restrict__ P) {
     __shared__ unsigned long long s[NCELL];
     __shared__ uint32_t s_act[TY][TX];
@@ -1074,13 +1074,12 @@ __global__ __launch_bounds__(256) void k_sk_plateau_relax(WsGeom g, const uint16
         it++;
     }
     if (more && threadIdx.x == 0) dirty[tile] = 1; // iteration cap: come back
-    uint32_t dirs = 0, gmax = 0;
+    uint32_t dirs = 0;
     for (int zz = 0; zz < nz && chg; zz++) {
         if (!((chg >> zz) & 1u)) continue;
         const int z = z0 + zz, y = y0 + ly, x = x0 + lx;
         const unsigned long long t = s[((zz + 1) * BY + (ly + 1)) * BX + (lx + 1)];
         tau[(int64_t)z * g.hw + (int64_t)y * g.w + x] = t;
-        gmax = max(gmax, (uint32_t)(t >> 32));
         const bool edge = lx == 0 || lx == TX - 1 || ly == 0 || ly == TY - 1 || zz == 0 || zz == TZ - 1;
         if (!edge) continue;
 #pragma unroll
@@ -1094,6 +1093,16 @@ __global__ __launch_bounds__(256) void k_sk_plateau_relax(WsGeom g, const uint16
         }
     }
     if (dirs & ~(1u << 13)) atomicOr(&s_ev2, dirs);
+    // The tile's latest generation AS IT STANDS after this visit, over all its voxels of the level, changed or not.  (A running
+    // maximum over the visits' changes -- what this kernel kept in SkState::gen before -- also remembers stamps that did not last:
+    // a voxel first reached by a detour inside its tile and later, through a neighbour's halo, by the short way.  The labels never
+    // saw that; the generation counter handed to the next level did, and depended on the order of the visits.)
+    uint32_t gmax = 0;
+    if (col)
+        for (int zz = 0; zz < nz; zz++) {
+            const unsigned long long t = s[((zz + 1) * BY + (ly + 1)) * BX + (lx + 1)];
+            if (t < TNM) gmax = max(gmax, (uint32_t)(t >> 32));
+        }
     if (gmax) atomicMax(&s_gmax, gmax);
     __syncthreads();
     if (threadIdx.x < 27 && threadIdx.x != 13 && ((s_ev2 >> threadIdx.x) & 1u)) {
@@ -1101,7 +1110,21 @@ __global__ __launch_bounds__(256) void k_sk_plateau_relax(WsGeom g, const uint16
         const int tz = z0 / TZ + k / 9 - 1, ty = y0 / TY + (k / 3) % 3 - 1, tx = x0 / TX + k % 3 - 1;
         if (tz >= 0 && tz < g.ntz && ty >= 0 && ty < g.nty && tx >= 0 && tx < g.ntx) dirty[((int64_t)tz * g.nty + ty) * g.ntx + tx] = 1;
     }
-    if (threadIdx.x == 0 && s_gmax > __hip_atomic_load(&st->gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&st->gen, s_gmax);
+    if (threadIdx.x == 0) tgen[tile] = s_gmax; // (a tile is visited at most once per round; its last visit has the last word)
+}
+
+// the tile-wise level's last generation: the largest of the tiles' (k_sk_plateau_relax; 0: never visited), never below the level's first
+__global__ __launch_bounds__(256) void k_sk_tile_gen(const uint32_t *__restrict__ tgen, int64_t ntiles, SkState *st) {
+    __shared__ uint32_t s_m;
+    if (threadIdx.x == 0) s_m = 0;
+    __syncthreads();
+    uint32_t m = 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < ntiles; i += (int64_t)gridDim.x * 256) m = max(m, tgen[i]);
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(&s_m, m);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_m > __hip_atomic_load(&st->gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&st->gen, s_m);
 }
 
 // ---- small levels: everything a level needs in ONE workgroup and ONE launch, and a run of consecutive small levels in the
@@ -1340,7 +1363,7 @@ struct SkBufs {
     uint8_t *kind, *dirty, *pending;
     unsigned long long *tau, *ekey[2];
     SkSortBufs sort[2];
-    uint32_t *comp, *zmask, *pmask, *elist, *dlist, *droot, *lists[2], *eval[2], *hist, *cursor, *dhist, *dcursor, *lhist, *mbits, *bcount, *bsum, *tlist, *total;
+    uint32_t *comp, *zmask, *pmask, *elist, *dlist, *droot, *lists[2], *eval[2], *hist, *cursor, *dhist, *dcursor, *lhist, *mbits, *bcount, *bsum, *tlist, *tgen, *total;
     int32_t *runlabel;
     WsState *wst;
     SkState *st;
@@ -1372,6 +1395,7 @@ static void sk_layout(const WsGeom &g, char *base, SkBufs *b) {
     b->bcount = (uint32_t *)take((size_t)(nblk + 1) * 4);
     b->bsum = (uint32_t *)take((size_t)(std::max<int64_t>(cdiv(nblk, 4096), 64) + 2) * 4);
     b->tlist = (uint32_t *)take((size_t)g.ntiles * 4);
+    b->tgen = (uint32_t *)take((size_t)g.ntiles * 4); // a tile-wise level's latest generation per tile
     b->dirty = (uint8_t *)take((size_t)g.ntiles);
     b->pending = (uint8_t *)take((size_t)g.ntiles);
     b->wst = (WsState *)take(sizeof(WsState));
@@ -1897,6 +1921,7 @@ static int sk_run_tile_level(SkCtx<MT> &x, SkCursor &cur, uint32_t c) {
         hipLaunchKernelGGL(k_sk_level_plane, dim3((unsigned)cdiv(cdiv(g.n, 64) * 8, 256)), dim3(256), 0, st, b.C, x.I, g.n, c, x.carve.plane);
         IVX_LAUNCH_CHECK();
     }
+    IVX_HIP(hipMemsetAsync(b.tgen, 0, (size_t)g.ntiles * 4, st)); // (no tile has been visited: k_sk_tile_gen takes the visited ones' maximum)
     // Rounds of dirty tiles.  The host never stands between two rounds' kernels: a round's relaxation is launched with a grid
     // guessed from the previous round's list (1.5 x + 64: the wave front grows slowly) BEFORE the host has read how long this
     // round's list is -- the read then overlaps the kernel (110 us), and a list longer than the guess gets a second launch
@@ -1909,7 +1934,7 @@ static int sk_run_tile_level(SkCtx<MT> &x, SkCursor &cur, uint32_t c) {
         if (rc != IVX_OK) return rc;
         parity ^= 1;
         if (guess) {
-            WS_CONN_SWITCH(x.conn, hipLaunchKernelGGL(k_sk_plateau_relax<CC>, dim3(guess), dim3(256), 0, st, g, x.I, b.C, b.tau, b.tlist, b.dirty, c, b.st,
+            WS_CONN_SWITCH(x.conn, hipLaunchKernelGGL(k_sk_plateau_relax<CC>, dim3(guess), dim3(256), 0, st, g, x.I, b.C, b.tau, b.tlist, b.dirty, c, b.tgen,
                                                         lcur, 0u, P));
             IVX_LAUNCH_CHECK();
         }
@@ -1919,11 +1944,13 @@ static int sk_run_tile_level(SkCtx<MT> &x, SkCursor &cur, uint32_t c) {
         x.ntile_rounds++;
         if (nl > guess) {
             WS_CONN_SWITCH(x.conn, hipLaunchKernelGGL(k_sk_plateau_relax<CC>, dim3(nl - guess), dim3(256), 0, st, g, x.I, b.C, b.tau, b.tlist, b.dirty, c,
-                                                        b.st, lcur, guess, P));
+                                                        b.tgen, lcur, guess, P));
             IVX_LAUNCH_CHECK();
         }
         guess = (uint32_t)std::min<int64_t>(g.ntiles, (int64_t)nl + nl / 2 + 64);
     }
+    hipLaunchKernelGGL(k_sk_tile_gen, dim3((unsigned)std::min<int64_t>(cdiv(g.ntiles, 256), 256)), dim3(256), 0, st, b.tgen, g.ntiles, b.st);
+    IVX_LAUNCH_CHECK();
     return cur.read_state(b.st, st, false);
 }
 

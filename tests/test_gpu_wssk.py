@@ -164,7 +164,7 @@ def test_odd_shaped_volume_with_wide_frontiers(ivxlib, oracle):
         assert (cost >= grad).all() and (cost[mk != 0] == grad[mk != 0]).all()  # minimax of the values ON the path
 
 
-def test_one_voxel_wide_volumes_and_markers_on_tile_faces(ivxlib, oracle):
+def test_one_voxel_wide_volumes_and_markers_on_tile_faces(ivxlib, oracle, monkeypatch):
     """A marker never changes, so it cannot wake the tile across the face it sits on; in a one-voxel-wide volume nothing
     else does either (regression: the cost map stopped at the tile boundary).  Both floods, all three axes."""
     from invesalius3_amd import watershed_process as wp
@@ -190,6 +190,15 @@ def test_one_voxel_wide_volumes_and_markers_on_tile_faces(ivxlib, oracle):
     for conn in (1, 2, 3):
         st = ndimage.generate_binary_structure(3, conn)
         assert np.array_equal(wp.watershed(flat, mk, st), oracle.watershed_sk(flat, mk, st, 1)), conn
+    # ... forced: the level has 3 generation-0 voxels and 14 400 voxels, a small level, and the chain asks for small levels first --
+    # so the one-workgroup path is switched off too, and the statistics say that the tiles ran
+    monkeypatch.setenv("IVX_SK_TILE_LEVEL", "1")
+    monkeypatch.setenv("IVX_SK_SMALL", "0")
+    for conn in (1, 2, 3):
+        st = ndimage.generate_binary_structure(3, conn)
+        got, stats = wp.watershed(flat, mk, st, want_stats=True)
+        assert np.array_equal(got, oracle.watershed_sk(flat, mk, st, 1)), conn
+        assert stats["tile_rounds"] > 0 and stats["small_level_runs"] == 0 and stats["frontier_launches"] == 0, (conn, stats)
 
 
 def test_edge_cases(ivxlib, oracle):
