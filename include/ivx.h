@@ -703,6 +703,37 @@ int ivx_host_zero(void *p, size_t nbytes);
 int ivx_host_register_zero(const void *base, size_t nbytes, uint64_t *handle);
 
 /* ------------------------------------------------------------------------------------------------
+ * mask edit history (csrc/k_maskhist.hip, csrc/mask_history_math.h): volume snapshots of a mask's bytes for
+ * EditionHistory (invesalius/data/mask.py:40-203), kept in HBM in the `blocks64` format.  A dense stream of n bytes is cut
+ * into B = ceil(n / 64) blocks of 64 bytes and W = ceil(B / 64) words of 64 blocks.
+ *   header  value[B] u8 (the block's first byte; padded with zeros to a multiple of 8 bytes), literal[W] u64 (bit b of
+ *           word w set <=> block 64 w + b holds a byte, at an offset < n, that differs from its first byte), base[W] u32
+ *           (literal blocks before word w).  Its size depends on n alone: ivx_mask_snapshot_header_bytes.
+ *   pool    the L literal blocks in stream order, 64 bytes each; bytes of the last block past n are stored as 0.
+ * Device forms (blocks in device memory, enqueued on `stream`; header 8-byte and pool 16-byte aligned, src / dst any):
+ *   scan     one pass over src: writes the header and returns L on the host -- it waits for `stream` once, because the
+ *            pool is sized from L.  Reads no byte at or past src + n.
+ *   pack     copies the literal blocks into `pool` (room for literal_blocks * 64 bytes).
+ *   restore  decodes the snapshot, compares with what dst holds and stores only where a byte differs; never a byte at or
+ *            past dst + n.  plane_flags (ceil(n / plane_bytes) bytes, zeroed by the caller; may be NULL): byte p becomes 1
+ *            for every plane p = offset / plane_bytes that holds a differing byte.
+ * Host forms take the C-contiguous host bytes of the matrix.  A matrix inside a registered range (ivx_host_register) is
+ * encoded straight from its mirror; any other one is staged once.  ivx_mask_snapshot returns header and pool as device
+ * blocks the caller frees with ivx_free.  ivx_mask_snapshot_restore on a registered matrix restores into the mirror and
+ * copies each run of consecutive changed planes mirror -> host (counted by ivx_transfer_stats; the flags themselves are a
+ * small argument and are not), so both hold the same bytes afterwards; on any other matrix all n bytes are decoded and
+ * downloaded.  *planes_written (may be NULL) = planes copied to the host.
+ * ---------------------------------------------------------------------------------------------- */
+int ivx_mask_snapshot_header_bytes(int64_t n, size_t *nbytes);
+int ivx_dev_mask_snapshot_scan(const uint8_t *src, int64_t n, void *header, int64_t *literal_blocks, void *stream);
+int ivx_dev_mask_snapshot_pack(const uint8_t *src, int64_t n, const void *header, void *pool, int64_t literal_blocks, void *stream);
+int ivx_dev_mask_snapshot_restore(uint8_t *dst, int64_t n, const void *header, const void *pool, int64_t literal_blocks,
+                                  int64_t plane_bytes, uint8_t *plane_flags, void *stream);
+int ivx_mask_snapshot(const uint8_t *matrix, size_t nbytes, void **header, void **pool, int64_t *literal_blocks);
+int ivx_mask_snapshot_restore(uint8_t *matrix, size_t nbytes, const void *header, const void *pool, int64_t literal_blocks,
+                              size_t plane_bytes, int64_t *planes_written);
+
+/* ------------------------------------------------------------------------------------------------
  * whole-mask numpy expressions of invesalius/data/slice_.py
  *   ivx_*_mask_boolean        Slice.do_boolean_op slice_.py:1906-1916: out = 255 where op(m1 > 2, m2 > 2) else 0;
  *                             op = 1 union, 2 diff (m1 and not m2), 3 intersection, 4 xor (constants.py:818-821)

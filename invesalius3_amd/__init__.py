@@ -7,7 +7,8 @@ Host-side mirror of the reference interface for that path and the stages next to
                                            invesalius/data/imagedata_utils.py FixGantryTilt
     invesalius3_amd.slice_display      <-> the display state of Slice (window/level, colour mode, nodes, aux) and the tables of
                                            Slice.GetSlices' VTK filters (slice_.get_slices)
-    invesalius3_amd.mask               <-> invesalius/data/mask.py fill_holes_auto
+    invesalius3_amd.mask               <-> invesalius/data/mask.py fill_holes_auto, save_history / undo_history / redo_history
+    invesalius3_amd.history            <-> invesalius/data/mask.py EditionHistory: undo / redo with the states kept in HBM
     invesalius3_amd.styles             <-> invesalius/data/styles.py region-growing tool (do_3d_seg, do_rg_confidence), slice tools
     invesalius3_amd.cursor             <-> invesalius/data/cursor_actors.py brush footprints, and the window a dab covers
     invesalius3_amd.surface_process    <-> invesalius/data/surface_process.py create_surface_piece, join_process_surface

@@ -88,7 +88,14 @@ def _declare(lib):
                        # the slice display: three 2-D views (pointer, row stride, element stride), h, w, parameters, tables, out
                        ("ivx_slice_show_tables_bytes", [ctypes.c_int, ctypes.POINTER(sz)]),
                        ("ivx_dev_slice_show", [c_vp, c_i64, c_i64] * 3 + [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
-                       ("ivx_slice_show", [c_vp, c_i64, c_i64] * 3 + [c_i64, c_i64, c_vp, c_vp, c_vp])):
+                       ("ivx_slice_show", [c_vp, c_i64, c_i64] * 3 + [c_i64, c_i64, c_vp, c_vp, c_vp]),
+                       # the mask edit history's volume snapshots (blocks64): header size, scan / pack / restore, host forms
+                       ("ivx_mask_snapshot_header_bytes", [c_i64, ctypes.POINTER(sz)]),
+                       ("ivx_dev_mask_snapshot_scan", [c_vp, c_i64, c_vp, i64p, c_vp]),
+                       ("ivx_dev_mask_snapshot_pack", [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
+                       ("ivx_dev_mask_snapshot_restore", [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
+                       ("ivx_mask_snapshot", [c_vp, sz, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), i64p]),
+                       ("ivx_mask_snapshot_restore", [c_vp, sz, c_vp, c_vp, c_i64, sz, i64p])):
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = args, ctypes.c_int
 

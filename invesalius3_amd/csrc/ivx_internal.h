@@ -89,6 +89,18 @@ int download_strided2(void *dst, const int64_t shape[2], const int64_t strides[2
 // Does nothing when the view lies in no registered range.
 int mirror_host_view(const void *view, const int64_t shape[3], const int64_t strides[3], size_t isz, void *d_scratch, int hslot);
 
+// A host-level entry point that works on a registered range's mirror itself (the mask edit history, k_maskhist.hip):
+// mirror_acquire hands out the device address that stands for host byte `p` when all of [p, p + n) lies in one registration
+// of the current device, with the registry lock held until mirror_release (the host's pending writes are brought in first;
+// `reads`: the stale check, when on, runs over the bytes).  *mirror stays NULL, and nothing is held, on a miss.  The caller
+// works on the null stream and synchronises it before the release, like every other user of a mirror.
+// mirror_fetch: mirror bytes -> the host bytes they stand for, counted like every other download; `mirror` and `host` are
+// the addresses of the same offset.  mirror_release(written): the bytes the caller wrote into the mirror, for the statistics.
+struct MirrorHold;
+int mirror_acquire(const void *p, size_t n, bool reads, MirrorHold **hold, void **mirror);
+int mirror_fetch(MirrorHold *hold, void *host, const void *mirror, size_t n);
+void mirror_release(MirrorHold *hold, size_t written);
+
 // run-based union-find flood (k_ccl.hip)
 void ccl_forget_stream(void *stream);
 void ccl_invalidate(const void *scratch);

@@ -860,6 +860,42 @@ int download_strided2(void *dst, const int64_t shape[2], const int64_t st[2], co
     return download_strided(dst, sh3, st3, src_dev, isz, hslot);
 }
 
+// ---- a mirror handed to a host-level entry point (ivx_internal.h) ----
+struct MirrorHold {
+    std::unique_lock<std::mutex> lk;
+    resident::Range *r = nullptr;
+};
+int mirror_acquire(const void *p, size_t n, bool reads, MirrorHold **hold, void **mirror) {
+    *hold = nullptr;
+    *mirror = nullptr;
+    if (!n || !g_res_count.load(std::memory_order_acquire)) return IVX_OK;
+    MirrorHold *h = new MirrorHold();
+    int rc = res_acquire((uintptr_t)p, (uintptr_t)p + n, reads, h->lk, &h->r);
+    if (rc || !h->r) {
+        delete h; // (drops the lock when the stale check failed with it held)
+        return rc;
+    }
+    *hold = h;
+    *mirror = (char *)h->r->mirror + ((uintptr_t)p - h->r->base);
+    if (reads) {
+        h->r->stats[resident::ST_HITS]++;
+        h->r->stats[resident::ST_HIT_BYTES] += n;
+    }
+    return IVX_OK;
+}
+int mirror_fetch(MirrorHold *hold, void *host, const void *mirror, size_t n) {
+    (void)hold; // (the lock it holds is what keeps the mirror at rest)
+    return raw_d2h(host, mirror, n);
+}
+void mirror_release(MirrorHold *hold, size_t written) {
+    if (!hold) return;
+    if (written) {
+        hold->r->stats[resident::ST_WRITES]++;
+        hold->r->stats[resident::ST_WRITE_BYTES] += written;
+    }
+    delete hold;
+}
+
 // ---- mailbox ------------------------------------------------------------------------------------------------
 static uint32_t *g_mb = nullptr; // pinned host memory, 64 dwords per slot x 64 slots (ring)
 static uint32_t g_mb_seq = 0;     // the newest sequence number handed out (mailbox_slot.h has the ring's arithmetic)

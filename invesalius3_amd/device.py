@@ -396,6 +396,25 @@ class DeviceVolume:
         self.sync()
         return self.mask.download(self.shape, np.uint8, out)
 
+    # -- edit history ---------------------------------------------------------------------------
+    def snapshot_mask(self):
+        """the dense mask's bytes as a `history.Snapshot` (blocks64), encoded on the volume's stream: no host byte moves"""
+        from . import history
+
+        return history.snapshot_device(self.mask_bytes(), self.n, self.shape, self.stream)
+
+    def restore_mask(self, snapshot):
+        """mask = the snapshot's state, in place on the volume's stream; what the pipeline derived from the mask's bytes
+        (planes, levels, the early triangle count) is dropped as after any other mask write"""
+        if snapshot.closed:
+            raise ValueError("restore_mask: the snapshot has been closed")
+        if snapshot.n != self.n or tuple(snapshot.shape) != self.shape:
+            raise ValueError("restore_mask: the snapshot holds shape %r, the volume has %r" % (tuple(snapshot.shape), self.shape))
+        self._materialize_mask()
+        L.check(L.lib().ivx_dev_mask_snapshot_restore(self.mask.raw, self.n, snapshot.header.ptr, snapshot.pool.ptr,
+                                                      snapshot.literal_blocks, 1, None, self.stream), "restore_mask")
+        self._mask_touched()
+
     def download_out_mask(self) -> np.ndarray:
         self._materialize_mask()
         self._materialize_out()

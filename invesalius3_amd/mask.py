@@ -1,6 +1,6 @@
 """Host mirror of the mask operations of invesalius/data/mask.py that sit on the voxel path.
 
-`fill_holes_auto` is Mask.fill_holes_auto (mask.py:519-562) without the undo history: the reference labels the
+`fill_holes_auto` is Mask.fill_holes_auto (mask.py:519-562) without its save_history call (`history.recorded` adds it): the reference labels the
 inverted mask with scipy.ndimage.label on the host (the dominant cost) and hands the labels to the Rust function; here
 labelling and filling are one device pass over bit planes (csrc/k_holes.hip), no label volume is ever built."""
 from __future__ import annotations
@@ -61,3 +61,22 @@ def fill_holes_auto(matrix: np.ndarray, target: str, conn: int, orientation: str
                                         ctypes.c_uint32(min(int(size), 0xFFFFFFFF)), ctypes.byref(modified)),
             "fill_holes_auto")
     return bool(modified.value)
+
+
+# ---- the edit history -----------------------------------------------------------------------------------------------
+def save_history(matrix: np.ndarray, history, index, orientation, array, p_array, clean=False) -> None:
+    """Mask.save_history (invesalius/data/mask.py:267-268): `history` is the mask's `history.EditionHistory`; `array` and
+    `p_array` are the edited slice after and before -- or, for ``orientation="VOLUME"``, the whole padded matrix as numpy
+    arrays or as `history.Snapshot`s (`matrix` itself is not read: it is here for the symmetry of the three calls)."""
+    history.new_node(index, orientation, array, p_array, clean)
+
+
+def undo_history(matrix: np.ndarray, history, actual_slices=None) -> None:
+    """Mask.undo_history (mask.py:270-276) without ``modified()`` and ``session.ChangeProject()``, which stay with the
+    caller: the matrix goes one step back, host and mirror alike."""
+    history.undo(matrix, actual_slices)
+
+
+def redo_history(matrix: np.ndarray, history, actual_slices=None) -> None:
+    """Mask.redo_history (mask.py:278-284), see `undo_history`."""
+    history.redo(matrix, actual_slices)

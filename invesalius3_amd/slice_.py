@@ -416,7 +416,7 @@ def edit_mask_stroke(mask_matrix, image_matrix, orientation: str, n: int, index,
     one per position (the modifier keys can change during a drag: the stroke is split into maximal runs of one operation,
     launched in order).  The slice is first brought up to date with `threshold_range` (the mask's own), as the reference's
     viewer has done before any brush event (get_mask_slice); the range may be left out only for a slice whose flag says it
-    is up to date already.  Returns the slice as it was before the stroke (p_mask, for the caller's undo history) when
+    is up to date already.  Returns the slice as it was before the stroke (p_mask, what `history.EditionHistory.new_node` takes as the state before) when
     asked."""
     if threshold_range is not None:
         get_mask_slice(mask_matrix, image_matrix, orientation, n, threshold_range)

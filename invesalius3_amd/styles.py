@@ -1,7 +1,7 @@
 """Host mirror of the array work behind the 3-D region-growing tool,
 FloodFillSegmentInteractorStyle.do_3d_seg + do_rg_confidence (invesalius/data/styles.py:3151-3251): everything between
-the mouse click and `save_history`, on the GPU.  The GUI parts (picker, progress dialog, undo history) stay with the
-caller; the function takes what they produce -- the clicked voxel and the dialog's configuration -- and edits the mask
+the mouse click and `save_history`, on the GPU.  The GUI parts (picker, progress dialog) stay with the caller, and so
+does the call of `save_history` (`history.recorded` wraps a tool with it); the function takes what they produce -- the clicked voxel and the dialog's configuration -- and edits the mask
 matrix in place."""
 from __future__ import annotations
 
