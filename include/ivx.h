@@ -454,6 +454,51 @@ int ivx_mesh_remove_nonvisible(const float *verts, int64_t nverts, const int32_t
                                const ivx_mesh_view *views, int nviews, int remove_visible, float *out_verts,
                                int32_t *out_faces, int64_t *out_nverts, int64_t *out_ntris);
 
+/* Surface view: shaded pictures of up to IVX_SURFACE_MAX_LAYERS surfaces (Surface._show_surface, invesalius/data/surface.py:
+ * 1061-1116: vtkPolyDataMapper + vtkActor with back-face culling, a colour, an opacity and an interpolation mode, under the
+ * parallel-projection camera of viewer_volume.SetViewAngle), DESIGN 7n.  float64 + - * / (and sqrt in the shading) in one order:
+ *   px = 2 parallel_scale / height;  d = v - focal;  a dot product is (d.x a.x + d.y a.y) + d.z a.z;
+ *   X = (d.right) / px + 0.5 width;  Y = 0.5 height - (d.up) / px (row 0 is the top);  t = d.dir (smaller is nearer).
+ *   ivx_dev_surface_raster   keys[height][width] of ONE surface: a front-facing triangle (area < 0 in (X, Y), edge functions
+ *                            as for ivx_*_mesh_depth_raster) covers a centre when its three edge functions are <= 0; the key is
+ *                            (ord(float32 t at the centre) << 32) | triangle index with ord(bits) = bits ^ 0x80000000 for a
+ *                            non-negative float and ~bits for a negative one; the 64-bit unsigned minimum is kept (an empty
+ *                            pixel holds all ones), so the buffer does not depend on the order the triangles arrive in.
+ *                            `stages`: IVX_RASTER_* bits, as for ivx_dev_mesh_depth_raster.
+ *   ivx_dev_surface_resolve  per pixel: the layers' fragments sorted by (ord depth, layer index), everything behind the first
+ *                            opaque one dropped, the rest blended far to near over the background, one white headlight along
+ *                            `dir` (ambient 0, diffuse 1, specular 0).  `rgba`: float32[height][width][4], or uint8 with out_u8
+ *                            (floor(255 v + 0.5) clamped).  ids (may be NULL): int32[height][width][2] = (layer, triangle) of
+ *                            the nearest fragment, -1 where empty; depth (may be NULL): its float32 t, +inf where empty.
+ *   ivx_surface_render       the whole picture from host arrays (the layers' `keys` are ignored).
+ * PARITY UNPINNED vs VTK's OpenGL renderer (third party, not installable here). */
+typedef struct ivx_surface_camera {
+    double focal[3], right[3], up[3], dir[3]; /* orthonormal frame; dir is the direction of projection */
+    double parallel_scale;                    /* half the viewport's height in world units */
+    int32_t width, height;
+} ivx_surface_camera;
+typedef struct ivx_surface_layer {
+    const float *verts;
+    int64_t nverts;
+    const int32_t *faces;
+    int64_t ntris;
+    const float *normals; /* one unit normal per point, or NULL: shaded flat */
+    const uint64_t *keys; /* width * height keys from ivx_dev_surface_raster */
+    float rgb[3];
+    float opacity; /* 1 - transparency */
+} ivx_surface_layer;
+#define IVX_SURFACE_MAX_LAYERS 8
+#define IVX_SURFACE_FLAT 0
+#define IVX_SURFACE_GOURAUD 1
+#define IVX_SURFACE_PHONG 2
+int ivx_dev_surface_raster(const float *verts, int64_t nverts, const int32_t *faces, int64_t ntris,
+                           const ivx_surface_camera *cam /* host */, int stages, uint64_t *keys, void *stream);
+int ivx_dev_surface_resolve(const ivx_surface_layer *layers /* host */, int nlayers, const ivx_surface_camera *cam /* host */,
+                            int interpolation, const float *background /* 3 */, int out_u8, void *rgba, int32_t *ids, float *depth,
+                            void *stream);
+int ivx_surface_render(const ivx_surface_layer *layers, int nlayers, const ivx_surface_camera *cam, int interpolation,
+                       const float *background, int out_u8, void *rgba, int32_t *ids, float *depth);
+
 /* Surface connectivity tools beyond keep-largest (Surface.OnSplitSurface / OnSeedSurface, invesalius/data/surface.py:319-411;
  * pu.SplitDisconectedParts / pu.JoinSeedsParts, invesalius/data/polydata_utils.py:206-278: vtkPolyDataConnectivityFilter in its
  * SpecifiedRegions and PointSeededRegions modes), DESIGN 7h.  Regions are keep-largest's: triangles joined through shared point

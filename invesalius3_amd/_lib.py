@@ -95,7 +95,11 @@ def _declare(lib):
                        ("ivx_dev_mask_snapshot_pack", [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
                        ("ivx_dev_mask_snapshot_restore", [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
                        ("ivx_mask_snapshot", [c_vp, sz, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), i64p]),
-                       ("ivx_mask_snapshot_restore", [c_vp, sz, c_vp, c_vp, c_i64, sz, i64p])):
+                       ("ivx_mask_snapshot_restore", [c_vp, sz, c_vp, c_vp, c_i64, sz, i64p]),
+                       # the surface view: mesh, camera, stages, keys; layers, camera, mode, background, out_u8, picture, ids, depth
+                       ("ivx_dev_surface_raster", [c_vp, c_i64, c_vp, c_i64, c_vp, ctypes.c_int, c_vp, c_vp]),
+                       ("ivx_dev_surface_resolve", [c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
+                       ("ivx_surface_render", [c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp, c_vp])):
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = args, ctypes.c_int
 

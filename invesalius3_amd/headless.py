@@ -10,6 +10,7 @@
     python -m invesalius3_amd.headless CASE.inv3 --segment brain --weights brain_mri_t1.pt --stl brain.stl
     python -m invesalius3_amd.headless CASE.inv3 --render "Bone + Skin" --presets-dir DIR --view iso --png out.png
     python -m invesalius3_amd.headless CASE.inv3 --threshold 226 3071 --mask-preview iso --mask-colour 0 1 0 --png mask.png
+    python -m invesalius3_amd.headless CASE.inv3 --threshold 226 3071 --largest --view iso --surface-png bone.png --surface-interpolation phong
     python -m invesalius3_amd.headless CASE.inv3 --threshold 226 3071 --show-slice AXIAL 40 --window 2000 300 --colour-table Rainbow --png slice.png
 
 What the reference does through its GUI for the same result: Slice.SetMaskThreshold / do_threshold_to_all_slices
@@ -201,11 +202,29 @@ def run(args) -> dict:
         m = mass.download((8,), np.float64)
         out["volume"], out["area"] = float(m[0]), float(m[1])
         mass.close()
+        verts = faces = None
         if args.stl:
             verts = verts_buf.download((nv, 3), np.float32)
             faces = faces_buf.download((nt, 3), np.int32)
             sp.write_stl_binary(args.stl, verts[faces])
             out["stl"] = args.stl
+        if getattr(args, "surface_png", None):
+            # the 3-D view's picture of the final surface (Surface._show_surface, surface.py:1061-1116, under the viewer's
+            # camera of the IMAGE: the picture overlays --render), with the point normals the reference's actor carries
+            from . import surface_view as SV
+            from . import volume as V
+            if verts is None:
+                verts = verts_buf.download((nv, 3), np.float32)
+                faces = faces_buf.download((nt, 3), np.int32)
+            pv, pf, pn, _ = sp.point_normals(verts, faces)
+            w, h = args.size
+            actor = SV.SurfaceActor(pv, pf, pn, colour=args.surface_colour, transparency=args.surface_transparency)
+            rgba8 = SV.render_surfaces([actor], args.view, (w, h), shape=vol.shape, spacing=vol.spacing,
+                                       interpolation=args.surface_interpolation, rgba8=True)
+            V.write_png(args.surface_png, rgba8)
+            out["surface_view"] = {"png": args.surface_png, "view": args.view, "size": [w, h], "colour": list(args.surface_colour),
+                                   "transparency": args.surface_transparency, "interpolation": args.surface_interpolation,
+                                   "vertices": int(len(pv)), "triangles": int(len(pf))}
         if args.geodesic:
             # the measurement panel's geodesic measure (GeodesicMeasure._draw_line, measures.py:1202-1256) on the final surface
             from . import polydata_utils as pu
@@ -360,7 +379,8 @@ def _render_only(args) -> bool:
     """--render without anything that asks for a mask or a surface: the image is all there is to make"""
     return (args.threshold is None and args.segment is None and not args.seed and not args.stl and not args.save
             and not args.largest and not args.smooth and not args.remove_nonvisible and not args.surface_seed
-            and args.split is None and not getattr(args, "geodesic", None) and getattr(args, "crop", None) is None and "--mask" not in (args.argv or []))
+            and args.split is None and not getattr(args, "geodesic", None) and getattr(args, "crop", None) is None
+            and not getattr(args, "surface_png", None) and "--mask" not in (args.argv or []))
 
 
 def _strct(conn: int) -> np.ndarray:
@@ -440,6 +460,14 @@ def main(argv=None) -> int:
     ap.add_argument("--min-weight", type=float, default=0.5)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--stl", help="write the surface as binary STL")
+    ap.add_argument("--surface-png", metavar="OUT", default=None,
+                    help="write a shaded picture of the final surface (after --largest / --surface-seed / --remove-nonvisible / "
+                         "--smooth) as an RGBA PNG, from --view at --size with the camera of the image: it overlays --render")
+    ap.add_argument("--surface-colour", nargs=3, type=float, metavar=("R", "G", "B"), default=(0.33, 1.0, 0.33),
+                    help="the surface's colour, 0..1 each (default: the reference's first surface colour)")
+    ap.add_argument("--surface-transparency", type=float, default=0.0, metavar="T", help="the surface's transparency, 0..1 (default 0)")
+    ap.add_argument("--surface-interpolation", choices=("flat", "gouraud", "phong"), default="gouraud",
+                    help="shading of --surface-png (default gouraud, the reference's default)")
     ap.add_argument("--save", help="write the project back with the new mask appended")
     ap.add_argument("--mask-name", default="GPU mask")
     args = ap.parse_args(argv)
@@ -484,6 +512,11 @@ def main(argv=None) -> int:
             ap.error("--mask-colour R G B must lie in 0..1")
     elif args.png is not None and args.show_slice is None:
         ap.error("--png needs --render, --mask-preview or --show-slice")
+    if args.surface_png is not None:
+        if args.size[0] <= 0 or args.size[1] <= 0:
+            ap.error("--size W H must be positive")
+        if not all(0.0 <= c <= 1.0 for c in args.surface_colour) or not 0.0 <= args.surface_transparency <= 1.0:
+            ap.error("--surface-colour R G B and --surface-transparency T must lie in 0..1")
     if args.show_slice is not None:
         if args.show_slice[0].upper() not in ("AXIAL", "CORONAL", "SAGITAL") or not args.show_slice[1].lstrip("-").isdigit():
             ap.error("--show-slice takes AXIAL, CORONAL or SAGITAL and a slice number")

@@ -326,6 +326,15 @@ class DeviceMesh:
         return GeodesicPath([flat[cuts[q]:cuts[q + 1]].copy() for q in range(nseg)], np.ascontiguousarray(coords),
                             [float(x) for x in seg_len], ids, _geo_stats(stats))
 
+    # ---- surface view ----
+    def render(self, normals=None, colour=None, transparency=0.0, **kwargs):
+        """A shaded picture of this mesh alone: `surface_view.Scene.render` (whose keywords these are, ``download=False``
+        apart) of one actor; `normals`: a device buffer of one float32 normal per point, or None (flat shading)."""
+        from . import surface_view as sv
+        actor = sv.SurfaceActor(self, normals=normals, colour=sv.SURFACE_COLOUR[0] if colour is None else colour, transparency=transparency)
+        with sv.Scene([actor], self.stream) as scene:
+            return scene.render(download=True, **kwargs)
+
     def close(self):
         if self._graph is not None:
             self._graph.close()

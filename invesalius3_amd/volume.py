@@ -346,6 +346,11 @@ def camera_for_view(view: str, shape, spacing, viewport) -> dict:
     parallel scale = radius; restated, unverified) and RepositionCamera's parallel scale.  Returns focal point, unit
     direction of projection, orthonormal screen right / up, parallel scale (half the viewport height in world units),
     camera position and the viewport."""
+    return camera_from_bounds(view, volume_bounds(shape, spacing), viewport)
+
+
+def camera_from_bounds(view: str, b, viewport) -> dict:
+    """camera_for_view's camera of a scene with the bounds `b` = (xmin, xmax, ymin, ymax, zmin, zmax)"""
     view = view.lower()
     if view not in VIEWS:
         raise ValueError("unknown view %r (one of %s)" % (view, ", ".join(VIEWS)))
@@ -353,7 +358,6 @@ def camera_for_view(view: str, shape, spacing, viewport) -> dict:
     if w_px <= 0 or h_px <= 0:
         raise ValueError("viewport %r must be positive" % (viewport,))
     up, pos = VIEWS[view]
-    b = volume_bounds(shape, spacing)
     center = np.array([(b[0] + b[1]) / 2, (b[2] + b[3]) / 2, (b[4] + b[5]) / 2])
     vpn = _norm(pos)  # focal point 0 -> position
     w = np.array([b[1] - b[0], b[3] - b[2], b[5] - b[4]])
