@@ -1353,6 +1353,46 @@ int ivx_slice_show(const void *image, int64_t image_row_stride, int64_t image_el
                    uint8_t *out);
 
 /* ------------------------------------------------------------------------------------------------
+ * density measures: the statistics of the pixels an ellipse or a polygon selects on a slice -- a batch of R regions per launch
+ *   replaces CircleDensityMeasure.calc_density and PolygonDensityMeasure.calc_density (invesalius/data/measures.py:2019-2107,
+ *   2229-2319).  Which pixels a region selects is stated as rules E and P in DESIGN.md section 7o and csrc/density_roi_math.h.
+ * A region reads a 2-D view of h x w int16 pixels with byte strides of any sign (row, element), the convention of
+ * ivx_dev_slice_show: one form serves the three orientations of a volume and a plain 2-D array.
+ *   ellipse  pixel (row j, column i) is selected iff (i sx - cx)^2 / a2 + (j sy - cy)^2 / b2 <= 1 in float64; a2 and b2 are
+ *            the squares as the caller computes them (Python's a ** 2)
+ *   polygon  n_points points (x, y) in pixel units, from index first_point of the call's points block; pixel (j, i) is
+ *            selected iff its centre (i + 0.5, j + 0.5) is inside by the odd-even crossing test of ivx_polygon2mask.  Fewer
+ *            than 3 points select nothing; more than IVX_ROI_MAX_POINTS (they sit in LDS) is IVX_EINVAL.
+ * The library fills x0 .. n_blocks of its own copy of every descriptor (the box of pixels the region can select, clipped to
+ * the slice and one pixel wider than the bound; the workgroups' prefix sums); what the caller puts there is ignored.
+ * records: five 8-byte integers per region -- cnt, s1 (sum), s2 (sum of squares), lo, hi; lo = hi = 0 when cnt is 0.
+ * ivx_dev_roi_density  the images, points_dev and records are device pointers, the descriptors host memory (read before the
+ *                      call returns); points_host: the same points for the polygons' boxes, or NULL (whole slices are then
+ *                      scanned).  One memset and one launch on `stream`, whatever n_rois is; only enqueues.
+ * ivx_roi_density      host pointers.  Regions on a registered array (ivx_host_register) are read from its mirror in place:
+ *                      nothing but descriptors and points goes host -> device; otherwise the boxes alone are uploaded.
+ *                      Exactly IVX_ROI_RECORD_BYTES * n_rois bytes come back.
+ * ---------------------------------------------------------------------------------------------- */
+#define IVX_ROI_ELLIPSE 0
+#define IVX_ROI_POLYGON 1
+#define IVX_ROI_MAX_POINTS 2048 /* 32 KB of LDS */
+#define IVX_ROI_RECORD_BYTES 40
+typedef struct ivx_roi {
+    const void *image;               /* element [0][0] of the int16 view */
+    int64_t row_stride, elem_stride; /* bytes, any sign */
+    int64_t h, w;
+    int32_t kind;     /* IVX_ROI_ELLIPSE, IVX_ROI_POLYGON */
+    int32_t n_points; /* polygon */
+    int64_t first_point;
+    double sx, sy, cx, cy, a2, b2;   /* ellipse */
+    int64_t x0, y0, x1, y1;          /* filled by the library: columns [x0, x1), rows [y0, y1) */
+    int64_t first_block, n_blocks;   /* filled by the library */
+} ivx_roi;
+int ivx_dev_roi_density(const ivx_roi *rois, int64_t n_rois, const double *points_host, const double *points_dev, int64_t n_points,
+                        int64_t *records, void *stream);
+int ivx_roi_density(const ivx_roi *rois, int64_t n_rois, const double *points, int64_t n_points, int64_t *records);
+
+/* ------------------------------------------------------------------------------------------------
  * bench / test input made in HBM (no reference counterpart): a CT-like int16 phantom -- six Gaussian blobs + sinusoid +
  * hashed N(0,25) noise, clipped to [-1024, 3071] -- for the slices [z0, z0 + dz) of a z_total-slice volume; deterministic
  * in (seed, global voxel index), so slabs made by different ranks tile the whole volume.  centres_zyx_sigma: 6 x (cz, cy,

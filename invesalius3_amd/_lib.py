@@ -52,6 +52,20 @@ class VolrenParams(ctypes.Structure):
     ]
 
 
+ROI_ELLIPSE, ROI_POLYGON, ROI_MAX_POINTS, ROI_RECORD_BYTES = 0, 1, 2048, 40
+
+
+class Roi(ctypes.Structure):
+    """struct ivx_roi (include/ivx.h): one region of interest of the density measures"""
+    _fields_ = [
+        ("image", c_vp), ("row_stride", c_i64), ("elem_stride", c_i64), ("h", c_i64), ("w", c_i64),
+        ("kind", ctypes.c_int32), ("n_points", ctypes.c_int32), ("first_point", c_i64),
+        ("sx", ctypes.c_double), ("sy", ctypes.c_double), ("cx", ctypes.c_double), ("cy", ctypes.c_double),
+        ("a2", ctypes.c_double), ("b2", ctypes.c_double),
+        ("x0", c_i64), ("y0", c_i64), ("x1", c_i64), ("y1", c_i64), ("first_block", c_i64), ("n_blocks", c_i64),
+    ]
+
+
 class StaleError(RuntimeError):
     """IVX_ESTALE: a registered host array (resident.bind) was written without a touch; raised only with the stale check on."""
 
@@ -99,7 +113,10 @@ def _declare(lib):
                        # the surface view: mesh, camera, stages, keys; layers, camera, mode, background, out_u8, picture, ids, depth
                        ("ivx_dev_surface_raster", [c_vp, c_i64, c_vp, c_i64, c_vp, ctypes.c_int, c_vp, c_vp]),
                        ("ivx_dev_surface_resolve", [c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
-                       ("ivx_surface_render", [c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp, c_vp])):
+                       ("ivx_surface_render", [c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
+                       # the density measures: descriptors, count, points (host; device), count, records
+                       ("ivx_dev_roi_density", [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
+                       ("ivx_roi_density", [c_vp, c_i64, c_vp, c_i64, c_vp])):
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = args, ctypes.c_int
 

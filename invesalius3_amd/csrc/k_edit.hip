@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "density_roi_math.h"
 #include "ivx_internal.h"
 
 typedef unsigned char uchar16_t __attribute__((ext_vector_type(16)));
@@ -124,13 +125,7 @@ __global__ __launch_bounds__(256) void k_polygon2mask(uint8_t *__restrict__ out,
         const int64_t r = i / h, c = i % h;
         bool inside = false;
         if ((uint64_t)r >= min_x && (uint64_t)r <= max_x && (uint64_t)c >= min_y && (uint64_t)c <= max_y) {
-            const double px = (double)r, py = (double)c;
-            int64_t j = n - 1;
-            for (int64_t k = 0; k < n; k++) {
-                const double xi = pts[2 * k], yi = pts[2 * k + 1], xj = pts[2 * j], yj = pts[2 * j + 1];
-                if (((yi > py) != (yj > py)) && (px < (xj - xi) * (py - yi) / (yj - yi) + xi)) inside = !inside;
-                j = k;
-            }
+            inside = ivx_density_roi_math::polygon_contains(pts, n, (double)r, (double)c); // the crossing test the density measures share
         }
         out[i] = inside ? 1 : 0;
     }

@@ -745,6 +745,40 @@ class DeviceVolume:
         L.check(L.lib().ivx_stream_synchronize(self.stream))
         return self._show_out.download((h, w, 3), np.uint8)
 
+    # -- density measures ---------------------------------------------------------------------
+    def roi_records(self, measures, spacing=None) -> np.ndarray:
+        """the (R, 5) int64 records cnt, s1, s2, lo, hi of `measures` (measures.CircleDensityMeasure / PolygonDensityMeasure) on
+        the resident image: one memset and one launch of ivx_dev_roi_density on the volume's stream, reading the slices in
+        place through their strides; descriptors and points go up, 40 bytes per measure come down"""
+        from . import measures as M
+
+        grid = M._Grid(self.image.raw_at(0).value, self.shape, (self.dy * self.dx * 2, self.dx * 2, 2))
+        q, points = M.describe_rois(grid, self.spacing if spacing is None else spacing, measures)
+        n = len(measures)
+        out = np.zeros((n, 5), np.int64)
+        if not n:
+            return out
+        if getattr(self, "_roi_records", None) is None or self._roi_records.nbytes < n * L.ROI_RECORD_BYTES:
+            self._roi_records = DeviceBuffer(max(n, 64) * L.ROI_RECORD_BYTES)
+        pp = None
+        if len(points):
+            if getattr(self, "_roi_points", None) is None or self._roi_points.nbytes < points.nbytes:
+                self._roi_points = DeviceBuffer(max(points.nbytes, 4096))
+            L.check(L.lib().ivx_stream_synchronize(self.stream))  # (an earlier batch's launch may still read the points block)
+            self._roi_points.upload(points)
+            pp = self._roi_points.ptr
+        L.check(L.lib().ivx_dev_roi_density(q, c64(n), L.ptr(points) if len(points) else None, pp, c64(len(points)), self._roi_records.ptr,
+                                            self.stream), "roi_density")
+        L.check(L.lib().ivx_stream_synchronize(self.stream))
+        return self._roi_records.download((n, 5), np.int64, out)
+
+    def roi_density(self, rois):
+        """`measures.density_of` on the resident image: a list of density measures or ``measurements.plist`` dicts in, their
+        results out, no host array involved"""
+        from . import measures as M
+
+        return M.density_of(self, self.spacing, rois)
+
     # -- image geometry tools (DESIGN 7k) ----------------------------------------------------------------
     def _after_image_geometry(self, shape=None, spacing=None):
         """The image's voxels moved (flip, swap axes, gantry tilt): everything derived from the image goes, as in

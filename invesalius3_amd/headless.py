@@ -12,6 +12,7 @@
     python -m invesalius3_amd.headless CASE.inv3 --threshold 226 3071 --mask-preview iso --mask-colour 0 1 0 --png mask.png
     python -m invesalius3_amd.headless CASE.inv3 --threshold 226 3071 --largest --view iso --surface-png bone.png --surface-interpolation phong
     python -m invesalius3_amd.headless CASE.inv3 --threshold 226 3071 --show-slice AXIAL 40 --window 2000 300 --colour-table Rainbow --png slice.png
+    python -m invesalius3_amd.headless CASE.inv3 --density-ellipse AXIAL 40 120 98 40 140 98 40 120 110 40 --remeasure --measures-json m.json --save CASE_out.inv3
 
 What the reference does through its GUI for the same result: Slice.SetMaskThreshold / do_threshold_to_all_slices
 (invesalius/data/slice_.py:1240-1247, 1739-1769), the Image Filters dialog (slice_.py:2330-2539), the deep-learning segmentation (segmentation/deep_learning/segment.py), the 3-D view's volume rendering (data/volume.py:575-707), the region-growing tool (styles.py:3151-3216),
@@ -75,6 +76,14 @@ def run(args) -> dict:
                 V.write_png(args.png, rgba8)
                 out["render"]["png"] = args.png
             if _render_only(args):
+                out["gpu_ms"] = {k: round(float(sum(v)), 4) for k, v in vol.timer.collect().items()}
+                return out
+        if _measures_asked(args):
+            _density(args, proj, vol, out)
+            if _measure_only(args):
+                if args.save:
+                    prj.save_inv3(args.save, proj)
+                    out["saved"] = args.save
                 out["gpu_ms"] = {k: round(float(sum(v)), 4) for k, v in vol.timer.collect().items()}
                 return out
         if args.show_slice is not None and _show_only(args):
@@ -370,6 +379,57 @@ def _show_slice(args, proj, vol, with_mask, out):
         out["show_slice"]["png"] = args.png
 
 
+def _measures_asked(args) -> bool:
+    return bool(getattr(args, "density_ellipse", None) or getattr(args, "density_polygon", None) or getattr(args, "remeasure", False))
+
+
+def _density(args, proj, vol, out):
+    """--density-ellipse / --density-polygon / --remeasure: the measurement panel's density measures (DensityMeasureEllipseStyle,
+    DensityMeasurePolygonStyle, styles.py:1023-1166; calc_density, measures.py:2019-2107, 2229-2319) on the resident image
+    (after --filter), all of them in one launch.  --remeasure first recomputes every density entry the project holds; the new
+    measures are appended to ``project.measurements`` under ``str(index)``, index = len(dict), as Project.AddMeasurement does
+    (project.py:173-177), so --save writes them."""
+    from . import measures as M
+
+    block = {}
+    with vol.timer.span("density"):
+        if getattr(args, "remeasure", False):
+            block["remeasured"] = M.recompute_measurements(proj.measurements, vol, proj.spacing)
+        new = []
+        for spec in getattr(args, "density_ellipse", None) or []:
+            c = [float(v) for v in spec[2:]]
+            new.append((M.CircleDensityMeasure(spec[0].upper(), int(spec[1]), tuple(c[0:3]), tuple(c[3:6]), tuple(c[6:9])), M.DENSITY_ELLIPSE))
+        for spec in getattr(args, "density_polygon", None) or []:
+            c = [float(v) for v in spec[2:]]
+            new.append((M.PolygonDensityMeasure(spec[0].upper(), int(spec[1]), [tuple(c[i:i + 3]) for i in range(0, len(c), 3)]), M.DENSITY_POLYGON))
+        for m, kind in new:
+            dm = M.DensityMeasurement()
+            dm.location, dm.type, dm.slice_number = M.LOCATIONS[m.orientation], kind, m.slice_number
+            m.set_measurement(dm)
+        results = M.density_of(vol, proj.spacing, [m for m, _ in new])
+        for m, _ in new:
+            dm = m._measurement
+            dm.index = len(proj.measurements)
+            dm.name = M.MEASURE_NAME_PATTERN % (dm.index + 1)
+            dm.points = [list(p) for p in dm.points]
+            proj.measurements[str(dm.index)] = dm.get_as_dict()
+    block["measures"] = [{"orientation": m.orientation, "slice": m.slice_number, "type": kind, "index": m._measurement.index, **r}
+                         for (m, kind), r in zip(new, results)]
+    out["density"] = block
+    if getattr(args, "measures_json", None):
+        with open(args.measures_json, "w") as f:
+            json.dump({"measures": block["measures"], "measurements": proj.measurements}, f)
+        out["density"]["json"] = args.measures_json
+
+
+def _measure_only(args) -> bool:
+    """the density flags without anything that asks for a mask, a surface or a picture: the numbers (and --save) are all"""
+    return (args.threshold is None and args.segment is None and not args.seed and not args.stl and not args.largest and not args.smooth
+            and not args.remove_nonvisible and not args.surface_seed and args.split is None and not getattr(args, "geodesic", None)
+            and getattr(args, "crop", None) is None and not getattr(args, "surface_png", None) and args.render is None
+            and args.mask_preview is None and args.show_slice is None and "--mask" not in (args.argv or []))
+
+
 def _show_only(args) -> bool:
     """--show-slice without --threshold, --mask or --segment: there is no mask to draw"""
     return args.threshold is None and args.segment is None and "--mask" not in (args.argv or [])
@@ -468,7 +528,15 @@ def main(argv=None) -> int:
     ap.add_argument("--surface-transparency", type=float, default=0.0, metavar="T", help="the surface's transparency, 0..1 (default 0)")
     ap.add_argument("--surface-interpolation", choices=("flat", "gouraud", "phong"), default="gouraud",
                     help="shading of --surface-png (default gouraud, the reference's default)")
-    ap.add_argument("--save", help="write the project back with the new mask appended")
+    ap.add_argument("--density-ellipse", nargs=11, action="append", default=None,
+                    metavar=("ORIENTATION", "N", "CX", "CY", "CZ", "P1X", "P1Y", "P1Z", "P2X", "P2Y", "P2Z"),
+                    help="the ellipse density measure on slice N (AXIAL, CORONAL or SAGITAL): centre and the two handle points in mm; "
+                         "min, max, mean, std, area and perimeter in the JSON line; repeatable")
+    ap.add_argument("--density-polygon", nargs="+", action="append", default=None, metavar="ORIENTATION N X Y Z",
+                    help="the polygon density measure on slice N through three or more points x y z in mm; repeatable")
+    ap.add_argument("--remeasure", action="store_true", help="recompute every density measure the project holds from the image")
+    ap.add_argument("--measures-json", metavar="FILE", default=None, help="write the measures' results and the project's measurements as JSON")
+    ap.add_argument("--save", help="write the project back with the new mask (and the new measures) appended")
     ap.add_argument("--mask-name", default="GPU mask")
     args = ap.parse_args(argv)
     args.argv = list(sys.argv[1:] if argv is None else argv)
@@ -487,6 +555,18 @@ def main(argv=None) -> int:
         ap.error("--geodesic takes two or more triples of x y z")
     if args.geodesic_npy is not None and args.geodesic is None:
         ap.error("--geodesic-npy needs --geodesic")
+    for spec in (args.density_ellipse or []) + (args.density_polygon or []):
+        if spec[0].upper() not in ("AXIAL", "CORONAL", "SAGITAL") or len(spec) < 2 or not spec[1].lstrip("-").isdigit():
+            ap.error("--density-ellipse / --density-polygon take AXIAL, CORONAL or SAGITAL and a slice number first")
+        try:
+            [float(v) for v in spec[2:]]
+        except ValueError:
+            ap.error("--density-ellipse / --density-polygon take coordinates in mm")
+    for spec in args.density_polygon or []:
+        if len(spec) < 5 or (len(spec) - 2) % 3:
+            ap.error("--density-polygon takes ORIENTATION N and triples of x y z")
+    if args.measures_json is not None and not _measures_asked(args):
+        ap.error("--measures-json needs --density-ellipse, --density-polygon or --remeasure")
     if args.split_min_triangles != 1 and args.split is None:
         ap.error("--split-min-triangles needs --split DIR")
     if args.filter is not None:
