@@ -1393,6 +1393,56 @@ int ivx_dev_roi_density(const ivx_roi *rois, int64_t n_rois, const double *point
 int ivx_roi_density(const ivx_roi *rois, int64_t n_rois, const double *points, int64_t n_points, int64_t *records);
 
 /* ------------------------------------------------------------------------------------------------
+ * The 3-D mask editor (csrc/k_mask3d.hip, csrc/mask3d_math.h): Mask3DEditorState of
+ * invesalius/data/mask3d_editor_state.py on mask_cut.rs, brush_mask.rs and polygon_mask.rs, in place on the padded mask matrix.
+ * `matrix` is element [0][0][0] of the (d+1, h+1, w+1) uint8 matrix, `shape` its interior (d, h, w), `strides` its byte
+ * strides, which must be the dense ((h+1)(w+1), w+1, 1).  (With the strides (h w, w, 1) `matrix` is a dense block of the voxels
+ * alone, as a DeviceVolume keeps its mask: cut and brush stroke take that too, with d plane flags.)  Row 0 of every axis (the slice flags) is never read as a voxel and
+ * never written.  edit_mode: 0 include, 1 exclude.  `plane_flags`: d+1 bytes, one per matrix[z]; a kernel stores 1 where it
+ * changed a byte of that plane and never stores 0 (the caller clears them).
+ * ivx_dev_m3e_filter         out[y * w + x] = OR_k polygon2mask_rs((w, h), polygon k)[x][y], inverted for include: an (h, w)
+ *                            byte image.  points_dev: all polygons' display points (x, y) as float64, polygon k being points
+ *                            offsets_dev[k] .. offsets_dev[k+1]-1 (n_polygons + 1 int64 offsets, device).  Any number of
+ *                            points: they are read from global memory, there is no cap.  n_polygons == 0: all 0 (all 1).
+ * ivx_dev_m3e_cut            mask_cut on the interior; `filter` is the dense (mh, mw) byte image, m / mv 16 doubles each, row-major
+ *                            (host).  One launch; no staging copy.
+ * ivx_dev_m3e_brush_stroke   n_centres dabs of brush_mask_rs with one radius, equal to the calls made one after another.
+ *                            centres: (x, y, z) float64 in the kernel's coordinates, given twice: centres_host for the boxes,
+ *                            centres_dev for the kernel.  `orig`: a padded matrix of the same strides, or NULL.  One launch per
+ *                            ivx_m3e_brush_capacity() centres, over the union of their clipped boxes.  Any edit_mode but 0 and 1
+ *                            touches nothing.
+ * ivx_dev_m3e_equal          *equal = the n bytes at a and b are the same (one int comes back; waits for `stream`)
+ * The host forms take the host matrix.  On a registered matrix (ivx_host_register) they work in its mirror and copy the runs of
+ * changed planes mirror -> host, so both hold the same bytes afterwards; any other matrix is staged once, up, and its changed
+ * planes come down.  ivx_m3e_cut takes the filter as an (mh, mw) byte image, or -- with filter == NULL -- the polygons, from
+ * which it makes the (mh, mw) filter on the device.  *planes_written: the planes copied to the host.
+ * ---------------------------------------------------------------------------------------------- */
+int ivx_m3e_brush_capacity(void);
+int ivx_dev_m3e_filter(int64_t w, int64_t h, const double *points_dev, const int64_t *offsets_dev, int64_t n_polygons, int edit_mode,
+                       uint8_t *out, void *stream);
+int ivx_dev_m3e_cut(uint8_t *matrix, const int64_t shape[3], const int64_t strides[3], const double spacing[3], double max_depth,
+                    const uint8_t *filter, int64_t mh, int64_t mw, const double *m, const double *mv, int edit_mode,
+                    uint8_t *plane_flags, void *stream);
+int ivx_dev_m3e_brush_stroke(uint8_t *matrix, const uint8_t *orig, const int64_t shape[3], const int64_t strides[3],
+                             const double spacing[3], const double *centres_host, const double *centres_dev, int64_t n_centres,
+                             double radius, int edit_mode, uint8_t *plane_flags, void *stream);
+int ivx_dev_m3e_equal(const uint8_t *a, const uint8_t *b, int64_t n, int *equal, void *stream);
+/* matrix[1:, 1:, 1:] = src[1:, 1:, 1:] (update_views:262) for a padded device block `src` of the matrix's shape; only bytes that
+ * differ are stored.  The host form follows the rules of the other host forms. */
+int ivx_dev_m3e_apply(uint8_t *matrix, const uint8_t *src, const int64_t shape[3], const int64_t strides[3], uint8_t *plane_flags,
+                      void *stream);
+int ivx_m3e_apply(uint8_t *matrix, const uint8_t *src_dev, const int64_t shape[3], const int64_t strides[3], int64_t *planes_written);
+/* Mask.modified(all_volume=True): matrix[0] = matrix[:, 0, :] = matrix[:, :, 0] = 1, by the CPU on the host and by a kernel in a
+ * registered matrix's mirror; no byte crosses the link. */
+int ivx_m3e_flag_planes(uint8_t *matrix, const int64_t shape[3], const int64_t strides[3]);
+int ivx_m3e_filter(int64_t w, int64_t h, const double *points, const int64_t *offsets, int64_t n_polygons, int edit_mode, uint8_t *out);
+int ivx_m3e_cut(uint8_t *matrix, const int64_t shape[3], const int64_t strides[3], const double spacing[3], double max_depth,
+                const uint8_t *filter, int64_t mh, int64_t mw, const double *points, const int64_t *offsets, int64_t n_polygons,
+                const double *m, const double *mv, int edit_mode, int64_t *planes_written);
+int ivx_m3e_brush_stroke(uint8_t *matrix, const uint8_t *orig, const int64_t shape[3], const int64_t strides[3], const double spacing[3],
+                         const double *centres, int64_t n_centres, double radius, int edit_mode, int64_t *planes_written);
+
+/* ------------------------------------------------------------------------------------------------
  * bench / test input made in HBM (no reference counterpart): a CT-like int16 phantom -- six Gaussian blobs + sinusoid +
  * hashed N(0,25) noise, clipped to [-1024, 3071] -- for the slices [z0, z0 + dz) of a z_total-slice volume; deterministic
  * in (seed, global voxel index), so slabs made by different ranks tile the whole volume.  centres_zyx_sigma: 6 x (cz, cy,

@@ -116,7 +116,19 @@ def _declare(lib):
                        ("ivx_surface_render", [c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
                        # the density measures: descriptors, count, points (host; device), count, records
                        ("ivx_dev_roi_density", [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
-                       ("ivx_roi_density", [c_vp, c_i64, c_vp, c_i64, c_vp])):
+                       ("ivx_roi_density", [c_vp, c_i64, c_vp, c_i64, c_vp]),
+                       # the 3-D mask editor: screen filter, cut, brush stroke, equal, apply; host forms
+                       ("ivx_dev_m3e_filter", [c_i64, c_i64, c_vp, c_vp, c_i64, ctypes.c_int, c_vp, c_vp]),
+                       ("ivx_dev_m3e_cut", [c_vp, i64p, i64p, c_vp, ctypes.c_double, c_vp, c_i64, c_i64, c_vp, c_vp, ctypes.c_int, c_vp, c_vp]),
+                       ("ivx_dev_m3e_brush_stroke", [c_vp, c_vp, i64p, i64p, c_vp, c_vp, c_vp, c_i64, ctypes.c_double, ctypes.c_int, c_vp,
+                                                     c_vp]),
+                       ("ivx_dev_m3e_equal", [c_vp, c_vp, c_i64, ctypes.POINTER(ctypes.c_int), c_vp]),
+                       ("ivx_dev_m3e_apply", [c_vp, c_vp, i64p, i64p, c_vp, c_vp]),
+                       ("ivx_m3e_filter", [c_i64, c_i64, c_vp, c_vp, c_i64, ctypes.c_int, c_vp]),
+                       ("ivx_m3e_cut", [c_vp, i64p, i64p, c_vp, ctypes.c_double, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp,
+                                        ctypes.c_int, i64p]),
+                       ("ivx_m3e_brush_stroke", [c_vp, c_vp, i64p, i64p, c_vp, c_vp, c_i64, ctypes.c_double, ctypes.c_int, i64p]),
+                       ("ivx_m3e_apply", [c_vp, c_vp, i64p, i64p, i64p]), ("ivx_m3e_flag_planes", [c_vp, i64p, i64p])):
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = args, ctypes.c_int
 

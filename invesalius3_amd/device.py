@@ -681,6 +681,64 @@ class DeviceVolume:
         box = L.i64([max(zi - 1, 0), min(zf + 1, self.dz), max(yi - 1, 0), min(yf + 1, self.dy), max(xi - 1, 0), min(xf + 1, self.dx)])
         L.check(L.lib().ivx_dev_mask_crop(self.mask.ptr, c64(self.dz), c64(self.dy), c64(self.dx), box, self.stream), "crop_mask")
 
+    # -- the 3-D mask editor ---------------------------------------------------------------
+    def _m3e_flags(self) -> DeviceBuffer:
+        f = getattr(self, "_m3e_plane_flags", None)
+        if f is None or f.nbytes < self.dz:
+            if f is not None:
+                f.close()
+            f = self._m3e_plane_flags = DeviceBuffer(self.dz)
+        f.zero(self.stream)
+        return f
+
+    def _m3e_geometry(self):
+        return L.i64(self.shape), L.i64((self.dy * self.dx, self.dx, 1))  # the voxels alone: no flag planes
+
+    def cut_mask(self, polygons, size, m, mv, depth, edit_mode) -> np.ndarray:
+        """mask3d_editor.cut_mask on the resident mask, on the volume's stream: the screen filter of the `polygons` (display
+        points) for the viewport `size` = (w, h), then mask_cut with the matrices `m` / `mv` down to the distance `depth`.
+        Returns one flag per axial slice that changed.  Planes, levels and the early triangle count go, as after any write."""
+        from . import mask3d_editor as M3
+
+        w, h = int(size[0]), int(size[1])
+        mode = M3._filter_mode(edit_mode)
+        points, offsets = M3._pack_polygons(polygons)
+        m, mv = M3._mat4(m, "m"), M3._mat4(mv, "mv")
+        lib = L.lib()
+        blk = DeviceBuffer(points.nbytes + offsets.nbytes + 16 + h * w)
+        try:
+            blk.upload(np.concatenate([offsets.view(np.uint8), points.reshape(-1).view(np.uint8)]))
+            d_f = blk.at(offsets.nbytes + points.nbytes)
+            L.check(lib.ivx_dev_m3e_filter(w, h, blk.at(offsets.nbytes), blk.at(0), len(offsets) - 1, mode, d_f, self.stream), "cut_mask")
+            shape, strides = self._m3e_geometry()
+            flags = self._m3e_flags()
+            L.check(lib.ivx_dev_m3e_cut(self.mask.ptr, shape, strides, M3._d3(self.spacing), float(depth), d_f, h, w, L.ptr(m), L.ptr(mv),
+                                        mode, flags.ptr, self.stream), "cut_mask")
+            L.check(lib.ivx_stream_synchronize(self.stream))
+            return flags.download((self.dz,), np.uint8).astype(bool)
+        finally:
+            blk.close()
+
+    def brush_mask_stroke(self, world_coords, brush_size, edit_mode, orig: DeviceBuffer | None = None) -> np.ndarray:
+        """mask3d_editor.brush_stroke on the resident mask, on the volume's stream: one dab per world point, the whole drag in
+        one launch per `mask3d_editor.brush_capacity()` dabs.  `orig`: a uint8 block of the volume's shape that include mode
+        reveals (None: 255 is painted).  Returns one flag per axial slice that changed."""
+        from . import mask3d_editor as M3
+
+        centres = M3.brush_centres(world_coords, self.spacing)
+        d_c = DeviceBuffer(max(centres.nbytes, 16))
+        try:
+            d_c.upload(centres)
+            shape, strides = self._m3e_geometry()
+            flags = self._m3e_flags()
+            L.check(L.lib().ivx_dev_m3e_brush_stroke(self.mask.ptr, orig.ptr if orig is not None else None, shape, strides,
+                                                     M3._d3(self.spacing), L.ptr(centres), d_c.ptr, len(centres), float(brush_size) / 2.0,
+                                                     int(edit_mode), flags.ptr, self.stream), "brush_mask_stroke")
+            L.check(L.lib().ivx_stream_synchronize(self.stream))
+            return flags.download((self.dz,), np.uint8).astype(bool)
+        finally:
+            d_c.close()
+
     # -- slice display (DESIGN 7l) ---------------------------------------------------------------------
     def _image_min_max(self):
         """(min, max) of the resident image as int16 numbers, as ``Slice.matrix.min()`` gives them; kept while `image_range()`

@@ -141,6 +141,8 @@ def run(args) -> dict:
             with vol.timer.span("crop"):
                 vol.crop_mask(args.crop)
             out["crop"] = {"limits": list(args.crop)}
+        if getattr(args, "cut_polygon", None) or getattr(args, "brush3d", None):
+            _mask3d_edit(args, vol, out)
         if args.mask_preview is not None:
             # "Mask 3D preview" (Mask.create_3d_preview -> VolumeMask.create_volume, volume_mask.py:36-119) of the resident mask
             from . import volume as V
@@ -448,6 +450,54 @@ def _strct(conn: int) -> np.ndarray:
     return _structure(3, CON3D[conn])
 
 
+def parse_cut_polygon(values):
+    """--cut-polygon MODE DEPTH X Y X Y ...: (edit mode, depth value 0..1, (N, 2) display points)"""
+    if len(values) < 4 or len(values) % 2:
+        raise ValueError("--cut-polygon takes MODE DEPTH and then X Y pairs")
+    mode, depth = int(values[0]), float(values[1])
+    if mode not in (0, 1):
+        raise ValueError("--cut-polygon MODE is 0 (include) or 1 (exclude)")
+    return mode, depth, np.array([float(v) for v in values[2:]], np.float64).reshape(-1, 2)
+
+
+def parse_brush3d(values):
+    """--brush3d MODE SIZE X Y Z ...: (edit mode, brush size, (N, 3) world points)"""
+    if len(values) < 5 or (len(values) - 2) % 3:
+        raise ValueError("--brush3d takes MODE SIZE and then X Y Z triples")
+    mode = int(values[0])
+    if mode not in (0, 1):
+        raise ValueError("--brush3d MODE is 0 (include) or 1 (exclude)")
+    return mode, float(values[1]), np.array([float(v) for v in values[2:]], np.float64).reshape(-1, 3)
+
+
+def _mask3d_edit(args, vol, out):
+    """the 3-D mask editor (Mask3DEditorState.CutMaskFromPolygons / brush_stroke, mask3d_editor_state.py) on the resident mask:
+    every --cut-polygon is one completed polygon cut through the --view camera of a --cut-size viewport, down to
+    near + (far - near) * DEPTH; every --brush3d is one drag"""
+    from . import mask3d_editor as M3
+    from . import volume as V
+
+    if args.cut_polygon:
+        w, h = args.cut_size
+        cam = V.resolve_camera(args.view, vol.shape, vol.spacing, (w, h))
+        near, far = M3.default_clipping_range(cam)
+        m, mv = M3.camera_matrices(cam, (w, h), (near, far))
+        out["cut_polygon"] = []
+        for values in args.cut_polygon:
+            mode, depth, pts = parse_cut_polygon(values)
+            with vol.timer.span("cut_polygon"):
+                flags = vol.cut_mask([pts], (w, h), m, mv, near + (far - near) * depth, mode)
+            out["cut_polygon"].append({"mode": mode, "depth": depth, "points": len(pts), "size": [w, h], "view": args.view,
+                                       "slices_changed": int(flags.sum())})
+    if args.brush3d:
+        out["brush3d"] = []
+        for values in args.brush3d:
+            mode, size, pts = parse_brush3d(values)
+            with vol.timer.span("brush3d"):
+                flags = vol.brush_mask_stroke(pts, size, mode)
+            out["brush3d"].append({"mode": mode, "size": size, "dabs": len(pts), "slices_changed": int(flags.sum())})
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m invesalius3_amd.headless", description=__doc__.split("\n")[0])
     ap.add_argument("project", help=".inv3 file")
@@ -465,6 +515,13 @@ def main(argv=None) -> int:
     ap.add_argument("--seed", nargs="+", type=int, default=None, metavar="X Y Z", help="keep the region grown (in the image, inside the threshold range) from these voxels; refused for a hand-edited --mask")
     ap.add_argument("--crop", nargs=6, type=int, default=None, metavar=("XI", "XF", "YI", "YF", "ZI", "ZF"),
                     help="crop the mask to this box of voxel limits (the Crop mask tool), after --threshold and --seed")
+    ap.add_argument("--cut-polygon", nargs="+", action="append", default=None, metavar="MODE DEPTH X Y",
+                    help="cut the mask with a polygon of display points drawn on the --view camera's --cut-size viewport (the 3-D mask "
+                         "editor): MODE 0 keeps what is inside, 1 removes it; DEPTH 0..1 of the clipping range; repeatable; after "
+                         "--threshold, --seed and --crop")
+    ap.add_argument("--cut-size", nargs=2, type=int, metavar=("W", "H"), default=(512, 512), help="viewport of --cut-polygon (default 512 512)")
+    ap.add_argument("--brush3d", nargs="+", action="append", default=None, metavar="MODE SIZE X Y Z",
+                    help="a drag of the 3-D brush through these world points: MODE 1 erases, 0 paints 255; SIZE the diameter; repeatable")
     ap.add_argument("--flip", type=int, choices=(0, 1, 2), default=None, metavar="AXIS",
                     help="flip the image along axis 0 (z), 1 (y) or 2 (x) first (the Flip tool); masks are cleared")
     ap.add_argument("--swap-axes", nargs=2, type=int, default=None, metavar=("A", "B"),
