@@ -132,6 +132,16 @@ def test_high_valence_fan_spills_out_of_registers(ivxlib, oracle):
     oracle.context_aware_smoothing(want, mesh.faces, mesh.normals, *OPTS)
     rs.ca_smoothing(mesh, *OPTS)
     assert np.array_equal(mesh.vertices, want)
+    # float32 vertices round the Laplacian sums away every half-step and with them the neighbour order this test is about: the
+    # same fan with jittered float64 vertices, where the reference's result does depend on that order
+    # (tests/test_surface_switch_cases_host.py::test_float64_fans_show_the_neighbour_order)
+    import _surface_switch_cases as S
+    v64, f64, _ = S.closed_fan(k, 0, seed=2, dtype=np.float64)
+    mesh = rs.Mesh.from_indexed(v64, f64)
+    want = mesh.vertices.copy()
+    oracle.context_aware_smoothing(want, mesh.faces, mesh.normals, *OPTS)
+    rs.ca_smoothing(mesh, *OPTS)
+    assert mesh.vertices.dtype == np.float64 and np.array_equal(mesh.vertices, want)
 
 
 def test_bench_surface_smoothing_matches_oracle_and_reports_both_times(ivxlib, oracle, capsys):
