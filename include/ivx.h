@@ -920,6 +920,31 @@ int ivx_dev_flood_apply_levels(const ivx_flood_plan *p, const uint64_t *reached,
  * dx % 64 == 0, a 16-byte aligned mask and 8-byte aligned planes only (IVX_EINVAL). */
 int ivx_dev_mask_from_planes(const ivx_flood_plan *p, const uint64_t *inside_bits, const uint64_t *reached, uint8_t *mask,
                              int v_in, int v_sel, void *stream);
+/* The write that follows a flood on its stream (ivx_dev_flood_grow_select): none, or one of the three single-kernel writes
+ * above with the flood's `reached` plane -- ivx_dev_mask_from_planes(p, inside_bits, reached, mask, v_in, v_sel),
+ * ivx_dev_flood_apply_levels(p, reached, inside_bits, mask, v_in, v_sel), ivx_dev_flood_apply(p, reached, IVX_U8, mask, v_sel).
+ * Fields a kind does not use are ignored. */
+enum { IVX_FLOOD_WRITE_NONE = 0, IVX_FLOOD_WRITE_MASK_FROM_PLANES = 1, IVX_FLOOD_WRITE_APPLY_LEVELS = 2, IVX_FLOOD_WRITE_APPLY_U8 = 3 };
+typedef struct ivx_flood_write {
+    int32_t kind, v_in, v_sel, reserved;
+    const uint64_t *inside_bits;
+    uint8_t *mask;
+} ivx_flood_write;
+/* ivx_dev_flood_grow, then `write` queued behind it from the same call: the host launches the write's kernel the moment it has
+ * seen the flood end, so the GPU does not wait for the caller to learn of the end and come back with the write.  The write
+ * lands behind whatever the flood queued last, on every path the flood can take (rounds, union-find escape, IVX_FLOOD_MODE=
+ * ccl, the unfused start, a plan without tiles); same bits as the two calls one after the other.  The two writes from the
+ * bit planes go one step further: while the rounds' lists run out the flood queues the write among its rounds, as a launch
+ * that reads the next round's list length on the device and returns at once unless it is zero, so the write starts where
+ * the first idle round would have, without the host in between (IVX_FLOOD_EARLY=0: only after the host has seen the end).  `look_ahead`: rounds the
+ * host keeps queued beyond the newest one it has seen start, 0 .. 8; negative = the default, by the list length (see
+ * ivx_flood_look_ahead); IVX_FLOOD_BATCH, if set, overrides either.  The rounds and *rounds do not depend on it.  If the flood fails nothing is
+ * written; an error of the write is returned after a completed flood. */
+int ivx_dev_flood_grow_select(const ivx_flood_plan *p, int dtype, const void *data, double t0, double t1,
+                              const int64_t *seeds_xyz, int64_t nseeds, uint64_t *cand, uint64_t *reached, void *scratch,
+                              int *rounds, const ivx_flood_write *write, int look_ahead, void *stream);
+/* host only, for tests: the default look-ahead behind a round that starts with `n_list` tiles on its list */
+int ivx_flood_look_ahead(int64_t n_list, int32_t *look_ahead);
 /* both writes of a GUI region-grow in one pass: out[v] = fill and mask[v] = select where reached
  * (floodfill_threshold's out + `mask[out_mask.astype(bool)] = 254`, styles.py:3200-3214) */
 int ivx_dev_flood_apply2(const ivx_flood_plan *p, const uint64_t *reached, uint8_t *out, int fill, uint8_t *mask,

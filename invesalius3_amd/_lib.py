@@ -39,6 +39,15 @@ class FloodPlan(ctypes.Structure):
     _fields_ = [("dz", c_i64), ("dy", c_i64), ("dx", c_i64), ("wx", c_i64), ("strct_bits", ctypes.c_uint32)]
 
 
+FLOOD_WRITE_NONE, FLOOD_WRITE_MASK_FROM_PLANES, FLOOD_WRITE_APPLY_LEVELS, FLOOD_WRITE_APPLY_U8 = 0, 1, 2, 3
+
+
+class FloodWrite(ctypes.Structure):
+    """struct ivx_flood_write (include/ivx.h): the write ivx_dev_flood_grow_select queues behind the flood"""
+    _fields_ = [("kind", ctypes.c_int32), ("v_in", ctypes.c_int32), ("v_sel", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("inside_bits", c_vp), ("mask", c_vp)]
+
+
 class VolrenParams(ctypes.Structure):
     """struct ivx_volren_params (include/ivx.h)."""
     _fields_ = [
@@ -90,6 +99,11 @@ def _declare(lib):
                        ("ivx_dev_mask_from_planes", [ctypes.POINTER(FloodPlan), c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp]),
                        ("ivx_dev_flood_candidates_ranges", [ctypes.POINTER(FloodPlan), c_vp, ctypes.c_double, ctypes.c_double, c_vp,
                                                             ctypes.c_int, ctypes.c_double, c_vp, c_vp, c_vp]),
+                       # flood + the write of its result in one call: ..., rounds, write, look-ahead, stream
+                       ("ivx_dev_flood_grow_select", [ctypes.POINTER(FloodPlan), ctypes.c_int, c_vp, ctypes.c_double, ctypes.c_double,
+                                                      c_vp, c_i64, c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_int),
+                                                      ctypes.POINTER(FloodWrite), ctypes.c_int, c_vp]),
+                       ("ivx_flood_look_ahead", [c_i64, ctypes.POINTER(ctypes.c_int32)]),
                        # the image geometry tools (flip, swap axes, gantry tilt) and the calls that keep a mask's zeros off the link
                        ("ivx_dev_image_flip", [c_vp, c_i64, c_i64, c_i64, sz, ctypes.c_int, c_vp]),
                        ("ivx_image_flip", [c_vp, i64p, i64p, sz, ctypes.c_int]),

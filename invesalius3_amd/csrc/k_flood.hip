@@ -710,8 +710,9 @@ __device__ __forceinline__ void count_visits(unsigned int *cnt, unsigned int rou
 }
 // `line` (pinned host memory, ivx::progress_line): word 0 = tag | round + 1 | tiles on this round's list, stored as the
 // round STARTS (everything before it in the stream is complete, so the count is final); word 1 = tag | round + 1 of the
-// last round that had any work.  The host polls word 0, keeps a few rounds queued ahead of the newest one it has seen
-// start, and stops when a round starts with an empty list.
+// last round that had any work.  The host polls word 0, keeps up to a few rounds queued ahead of the newest one it has
+// seen start, and stops when a round starts with an empty list -- or when word 2 = tag | rounds in front | 1 arrives: the
+// report of a write that was queued among the rounds and found the next list empty (ApplyWhen).
 // MODE 0: candidate plane; 1 (directed): `cand` holds the six edge planes of k_flood_edges_auto instead; 2 (linear): the
 // three arc planes of k_wsa_planes (k_costlevels.hip) and scipy's linear-index neighbourhood (tile_update_lin)
 template <int MODE>
@@ -1198,9 +1199,22 @@ __global__ __launch_bounds__(256) void k_flood_apply16(const uint16_t *__restric
 // chunk's 16 bytes after its bits have arrived: a second, dependent round trip).  Chunks without a reached bit are not written
 // -- unless ALL: then `out` holds nothing yet (a plane-only threshold) and every chunk is written, `reached` may be NULL (no
 // bit), and a wave's four stores are 1 KiB contiguous each.
+// WHEN: the launch was queued before the flood's end was known (flood_run_impl).  It goes ahead only if the list of the
+// round that would run next is empty -- the flood is over, `reached` is final -- and then says so in word 2 of the progress
+// line as it starts; otherwise every workgroup returns at once.  `next_len` NULL: unconditional.
+struct ApplyWhen {
+    const unsigned int *next_len;
+    unsigned long long *line;
+    unsigned long long report;
+};
 template <bool ALL>
 __global__ __launch_bounds__(256) void k_flood_apply_levels16(const uint16_t *__restrict__ reached, const uint16_t *__restrict__ inside,
-                                                              int64_t nchunks, uint4 *__restrict__ out, uint8_t v_in, uint8_t v_sel) {
+                                                              int64_t nchunks, uint4 *__restrict__ out, uint8_t v_in, uint8_t v_sel,
+                                                              ApplyWhen when) {
+    if (when.next_len) {
+        if (*when.next_len != 0u) return; // (nothing in the stream writes the counter while this kernel runs)
+        if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&when.line[2], when.report, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
     const int64_t stride = (int64_t)gridDim.x * 1024;
     const unsigned int in4 = 0x01010101u * v_in, sel4 = 0x01010101u * v_sel;
     for (int64_t i0 = (int64_t)blockIdx.x * 1024 + threadIdx.x; i0 < nchunks; i0 += stride) {
@@ -1586,8 +1600,59 @@ static int poll_line(volatile unsigned long long *line, long spins, hipStream_t 
     IVX_REQUIRE(done(*word), IVX_EHIP, "%s", never);
     return IVX_OK;
 }
+// k_flood_apply_levels16's launch for ivx_dev_flood_apply_levels (ALL false), ivx_dev_mask_from_planes (ALL true) and the
+// flood's own early launch of either; levels_check() is the argument check of the two
+static int levels_check(const Tiles &t, const uint64_t *reached, const uint64_t *inside_bits, const uint8_t *mask, int v_in, int v_sel,
+                        bool all) {
+    if (all) {
+        IVX_REQUIRE(inside_bits && mask, IVX_EINVAL, "mask_from_planes: null plane or mask");
+        IVX_REQUIRE(t.dx % 64 == 0 && ((uintptr_t)mask & 15) == 0 && (((uintptr_t)inside_bits | (uintptr_t)reached) & 7) == 0, IVX_EINVAL,
+                    "mask_from_planes: rows of whole 64-voxel words, a 16-byte aligned mask and 8-byte aligned planes only");
+        IVX_REQUIRE(v_in >= 0 && v_in <= 255 && v_sel >= 0 && v_sel <= 255, IVX_EINVAL, "mask_from_planes: levels are bytes");
+    } else {
+        IVX_REQUIRE(reached && inside_bits && mask, IVX_EINVAL, "flood_apply_levels: null plane or mask");
+        IVX_REQUIRE(t.dx % 64 == 0 && ((uintptr_t)mask & 15) == 0, IVX_EINVAL,
+                    "flood_apply_levels: rows of whole 64-voxel words and a 16-byte aligned mask only");
+        IVX_REQUIRE(v_in >= 0 && v_in <= 255 && v_sel >= 0 && v_sel <= 255, IVX_EINVAL, "flood_apply_levels: levels are bytes");
+    }
+    return IVX_OK;
+}
+static int launch_levels(const Tiles &t, const uint64_t *reached, const uint64_t *inside, uint8_t *mask, int v_in, int v_sel, bool all,
+                         const ApplyWhen &when, hipStream_t st) {
+    const int64_t nchunks = t.dz * t.dy * t.dx / 16;
+    if (!nchunks) return IVX_OK;
+    const int64_t blocks = ivx::cdiv(nchunks, 1024);
+    auto k = all ? k_flood_apply_levels16<true> : k_flood_apply_levels16<false>;
+    hipLaunchKernelGGL(k, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, st, (const uint16_t *)reached,
+                       (const uint16_t *)inside, nchunks, (uint4 *)mask, (uint8_t)v_in, (uint8_t)v_sel, when);
+    IVX_LAUNCH_CHECK();
+    return IVX_OK;
+}
+// The default look-ahead: how many rounds the host keeps queued beyond the newest one it has seen start, by that round's
+// list length.  Every round queued ahead when the first empty one reports is a launch for nothing, so the fewer the better
+// -- as long as the host can queue the next round before the one it has just seen start is over.  A round of
+// AHEAD_LONG_LIST tiles or more runs longer than the host's way from the poll to the next launch, so nothing needs to be
+// queued behind it yet; behind a shorter one (the flood's tail: a few microseconds each) one round waits ready.
+// profiles/flood_end_ab.md has the measurements of the fixed values 0 .. 3 against this.
+constexpr unsigned AHEAD_LONG_LIST = 384u;
+static int default_look_ahead(unsigned n_list) { return n_list >= AHEAD_LONG_LIST ? 0 : 1; }
+// The write ivx_dev_flood_grow_select wants behind the flood.  Between the start of the first empty round and the start of a
+// kernel the host launches on seeing it lie ~15 us (the report's way to the host, the launch's way to the GPU), whatever
+// the host does in between; the rounds queued ahead only fill that time.  So when the lists are running out -- the round
+// just seen has fewer than EARLY_BELOW tiles and at most half of the one seen before -- the flood queues the write itself,
+// behind the rounds already in the stream, as a launch that looks at the next round's list length on the device
+// (ApplyWhen): empty, and the write runs where the first idle round would have; not empty, and it costs ~3 us.  One such
+// launch is outstanding at a time and at most EARLY_TRIES per flood, so a flood whose lists shrink and recover pays
+// ~6 us at most.  `written` comes back true when such a launch went ahead: the caller then has nothing left to queue.
+struct EarlyWrite {
+    const ivx_flood_write *w;
+    bool written;
+};
+constexpr unsigned EARLY_BELOW = 96u;
+constexpr int EARLY_TRIES = 2;
+// `look_ahead` < 0: default_look_ahead() of every round seen; IVX_FLOOD_BATCH (0 .. BATCH), if set, overrides either
 static int flood_run_impl(const ivx_flood_plan *p, const uint64_t *cand, ivx::FloodMode mode, uint64_t *reached, void *scratch_,
-                          int *rounds, void *stream, const Fresh *fresh = nullptr) {
+                          int *rounds, void *stream, const Fresh *fresh = nullptr, int look_ahead = -1, EarlyWrite *early = nullptr) {
     const bool sym = mode == ivx::FLOOD_SYMMETRIC;
     Tiles t;
     int rc = make_tiles(p, &t);
@@ -1628,15 +1693,21 @@ static int flood_run_impl(const ivx_flood_plan *p, const uint64_t *cand, ivx::Fl
     // Counters live in a ring of RING dwords indexed by the round number: round r reads cnt[r % RING] (entries of its
     // list), appends to cnt[(r+1) % RING] and clears cnt[(r+2) % RING] for the round after -- no host-side resets, so
     // rounds can be queued back to back.  Every round reports the length of its list to a pinned progress line as it
-    // starts; the host keeps `ahead` rounds queued beyond the newest round it has seen start (a wait + re-launch round
-    // trip would leave the GPU idle for 35-45 us) and stops at the first round that starts empty.  The rounds queued
-    // ahead at that point find empty lists: a few ~2 us launches that later work simply queues behind.
+    // starts; the host keeps `ahead` rounds queued beyond the newest round it has seen start (waiting for a round's END
+    // before launching the next would leave the GPU idle for 35-45 us) and stops at the first round that starts empty.
+    // `ahead` may be 0: the next round is then queued while the one just seen runs.  The `ahead` rounds queued behind
+    // the first empty one find empty lists too: ~4.4 us each that the step's next kernel waits behind, which is why
+    // the look-ahead is kept as short as the host's reaction allows (default_look_ahead).
     constexpr int RING = 2 * BATCH;
-    static const int ahead = [] {
+    static const int env_ahead = [] { // IVX_FLOOD_BATCH: a fixed look-ahead for every flood, 0 .. BATCH (A/B measurements)
         const char *e = getenv("IVX_FLOOD_BATCH");
-        const int v = e ? atoi(e) : 3;
-        return v < 1 ? 1 : (v > BATCH ? BATCH : v);
+        if (!e || !*e) return -1;
+        const int v = atoi(e);
+        return v < 0 ? 0 : (v > BATCH ? BATCH : v);
     }();
+    const int fixed_ahead = env_ahead >= 0 ? env_ahead : (look_ahead > BATCH ? BATCH : look_ahead);
+    // before any round has reported its length is not known: one round waits behind the first
+    int ahead = fixed_ahead >= 0 ? fixed_ahead : 1;
     if (coarse_ok(t, mode)) {
         static const Fresh no_seeds = {0, nullptr, 0.0, 0.0, {{}, 0}};
         rc = fresh ? coarse_pass<true>(t, s, scr, cand, reached, *fresh, CNT_CLEARED, st)
@@ -1672,6 +1743,21 @@ static int flood_run_impl(const ivx_flood_plan *p, const uint64_t *cand, ivx::Fl
         return IVX_OK;
     };
     static const bool trace = getenv("IVX_FLOOD_TRACE") != nullptr;
+    // the early write (EarlyWrite): the two kinds that are one launch of k_flood_apply_levels16 with arguments it accepts
+    static const bool early_on = [] { // IVX_FLOOD_EARLY=0: the write only after the host has seen the end (A/B)
+        const char *e = getenv("IVX_FLOOD_EARLY");
+        return !(e && e[0] == '0');
+    }();
+    const bool early_all = early && early->w->kind == IVX_FLOOD_WRITE_MASK_FROM_PLANES;
+    int early_left = 0;
+    if (early_on && early && (early_all || early->w->kind == IVX_FLOOD_WRITE_APPLY_LEVELS) &&
+        levels_check(t, reached, early->w->inside_bits, early->w->mask, early->w->v_in, early->w->v_sel, early_all) == IVX_OK)
+        early_left = EARLY_TRIES;
+    if (early_left) __atomic_store_n((unsigned long long *)line + 2, 0ull, __ATOMIC_RELEASE); // (a report of this tag's last turn)
+    int64_t early_at = -1; // rounds in the stream in front of the outstanding early write, -1: none outstanding
+    unsigned long long early_report = 0;
+    bool early_seen = false; // its report has arrived
+    unsigned int prev_list = 0xffffffffu;
     int64_t seen = 0; // rounds seen starting
     for (;;) {
         while (queued < seen + 1 + ahead)
@@ -1679,20 +1765,45 @@ static int flood_run_impl(const ivx_flood_plan *p, const uint64_t *cand, ivx::Fl
         // wait for a round beyond `seen` to report; a few hundred ms without news: the safe path once
         unsigned long long v = 0;
         rc = poll_line(line, 20000000L, st,
-                       [tag, seen](unsigned long long w) { return (uint32_t)(w >> 56) == tag && (int64_t)((w >> 32) & 0xffffffull) > seen; },
+                       [&](unsigned long long w) {
+                           if (early_at >= 0 && __atomic_load_n((const unsigned long long *)line + 2, __ATOMIC_ACQUIRE) == early_report)
+                               return early_seen = true;
+                           return (uint32_t)(w >> 56) == tag && (int64_t)((w >> 32) & 0xffffffull) > seen;
+                       },
                        "flood: the queued rounds never reported", &v);
         if (rc) return rc;
+        if (early_seen) { // the early write is running: every round in front of it is complete, and the flood with them
+            const unsigned long long u = __atomic_load_n((const unsigned long long *)line + 1, __ATOMIC_ACQUIRE);
+            total_rounds = (uint32_t)(u >> 56) == tag ? (int)((u >> 32) & 0xffffffull) : 0;
+            early->written = true;
+            if (trace) fprintf(stderr, "ivx flood: the write behind round %lld went ahead (%d rounds with work)\n", (long long)early_at, total_rounds);
+            break;
+        }
         seen = (int64_t)((v >> 32) & 0xffffffull);
         const unsigned int n_list = (unsigned int)(v & 0xffffffffull);
         if (trace) fprintf(stderr, "ivx flood: round %lld starts with %u of %lld tiles (%lld queued)\n", (long long)seen, n_list,
                            (long long)t.ntiles, (long long)queued);
         if (n_list < arm.below) arm.word = nullptr; // that round has opened the gate: nothing left for the guard to do
         grid = n_list >= 384u ? grid_max : (n_list >= 96u ? (grid_max < 512u ? grid_max : 512u) : (grid_max < 128u ? grid_max : 128u));
+        if (fixed_ahead < 0) ahead = default_look_ahead(n_list);
         if (n_list == 0) { // converged: word 1 holds the last round that had work (if any, and if it is ours)
             const unsigned long long u = __atomic_load_n((const unsigned long long *)line + 1, __ATOMIC_ACQUIRE);
             total_rounds = (uint32_t)(u >> 56) == tag ? (int)((u >> 32) & 0xffffffull) : 0;
+            // an early write behind rounds that include the last one with work finds the next list empty: it goes (or went) ahead
+            if (early_at >= 0 && total_rounds <= early_at) early->written = true;
             break;
         }
+        if (early_at >= 0 && seen > early_at) early_at = -1; // the round behind it has work: it has returned at once
+        if (early_left > 0 && early_at < 0 && n_list < EARLY_BELOW && n_list <= prev_list / 2u) {
+            early_at = queued;
+            early_left--;
+            early_report = ((unsigned long long)tag << 56) | ((unsigned long long)(queued & 0xffffff) << 32) | 1ull;
+            if (trace) fprintf(stderr, "ivx flood: write queued behind round %lld\n", (long long)queued);
+            rc = launch_levels(t, reached, early->w->inside_bits, early->w->mask, early->w->v_in, early->w->v_sel, early_all,
+                               ApplyWhen{cnt + queued % RING, (unsigned long long *)line, early_report}, st);
+            if (rc) return rc;
+        }
+        prev_list = n_list;
         total_rounds = (int)seen;
         if (sym && total_rounds >= CCL_ESCAPE_ROUNDS && ivx::ccl_supported(p->strct_bits)) {
             // long, thin region: stop paying one launch per tile hop -- every reached bit so far is correct, the
@@ -1710,14 +1821,19 @@ static int flood_run_impl(const ivx_flood_plan *p, const uint64_t *cand, ivx::Fl
     return IVX_OK;
 }
 
+// The entry points from before ivx_dev_flood_grow_select keep three rounds queued ahead, as every flood did until the
+// default followed the list length: the watershed's cost levels run one short flood per level, each on the heels of the
+// last, and the sharded step's floods are resumed round by round; both measured slower with the step's default
+// (profiles/flood_end_ab.md section 6), which pays only together with the early write.
+constexpr int AHEAD_CHAINED = 3;
 int ivx::flood_run(const ivx_flood_plan *p, const uint64_t *planes, ivx::FloodMode mode, uint64_t *reached, void *scratch,
                    int *rounds, void *stream) {
-    return flood_run_impl(p, planes, mode, reached, scratch, rounds, stream);
+    return flood_run_impl(p, planes, mode, reached, scratch, rounds, stream, nullptr, AHEAD_CHAINED);
 }
 
 extern "C" int ivx_dev_flood_run(const ivx_flood_plan *p, const uint64_t *cand, uint64_t *reached, void *scratch_,
                                  int *rounds, void *stream) {
-    return flood_run_impl(p, cand, ivx::FLOOD_SYMMETRIC, reached, scratch_, rounds, stream);
+    return flood_run_impl(p, cand, ivx::FLOOD_SYMMETRIC, reached, scratch_, rounds, stream, nullptr, AHEAD_CHAINED);
 }
 // does a flood of `nseeds` seeds take the fused start (clear and seed inside the coarse pass)?
 static bool fused_start(const Tiles &t, int64_t nseeds) {
@@ -1730,9 +1846,9 @@ static bool fused_start(const Tiles &t, int64_t nseeds) {
 // clear + seed + run in one call: the flood of `seeds` over `cand` into a plane whose old contents are dead.  With at most
 // 16 seeds and a standard structuring element the clearing and the seeding ride on the coarse pass (three launches before
 // the rounds instead of five, no separate pass over the plane); otherwise the three calls run one after the other.
-extern "C" int ivx_dev_flood_grow(const ivx_flood_plan *p, int dtype, const void *data, double t0, double t1,
-                                  const int64_t *seeds_xyz, int64_t nseeds, uint64_t *cand, uint64_t *reached, void *scratch_,
-                                  int *rounds, void *stream) {
+static int flood_grow_impl(const ivx_flood_plan *p, int dtype, const void *data, double t0, double t1, const int64_t *seeds_xyz,
+                           int64_t nseeds, uint64_t *cand, uint64_t *reached, void *scratch_, int *rounds, void *stream,
+                           int look_ahead, EarlyWrite *early = nullptr) {
     Tiles t;
     int rc = make_tiles(p, &t);
     if (rc) return rc;
@@ -1746,7 +1862,7 @@ extern "C" int ivx_dev_flood_grow(const ivx_flood_plan *p, int dtype, const void
     if (!fused_start(t, nseeds)) {
         if ((rc = ivx_dev_flood_clear(p, reached, scratch_, stream))) return rc;
         if ((rc = ivx_dev_flood_seed(p, dtype, data, t0, t1, seeds_xyz, nseeds, cand, reached, scratch_, stream))) return rc;
-        return flood_run_impl(p, cand, ivx::FLOOD_SYMMETRIC, reached, scratch_, rounds, stream);
+        return flood_run_impl(p, cand, ivx::FLOOD_SYMMETRIC, reached, scratch_, rounds, stream, nullptr, look_ahead, early);
     }
     ivx::ccl_invalidate(scratch_);
     Fresh f;
@@ -1757,7 +1873,18 @@ extern "C" int ivx_dev_flood_grow(const ivx_flood_plan *p, int dtype, const void
     f.sp.n = (int)nseeds;
     for (int64_t n = 0; n < nseeds; n++)
         for (int q = 0; q < 3; q++) f.sp.xyz[n][q] = seeds_xyz[3 * n + q];
-    return flood_run_impl(p, cand, ivx::FLOOD_SYMMETRIC, reached, scratch_, rounds, stream, &f);
+    return flood_run_impl(p, cand, ivx::FLOOD_SYMMETRIC, reached, scratch_, rounds, stream, &f, look_ahead, early);
+}
+extern "C" int ivx_dev_flood_grow(const ivx_flood_plan *p, int dtype, const void *data, double t0, double t1,
+                                  const int64_t *seeds_xyz, int64_t nseeds, uint64_t *cand, uint64_t *reached, void *scratch_,
+                                  int *rounds, void *stream) {
+    return flood_grow_impl(p, dtype, data, t0, t1, seeds_xyz, nseeds, cand, reached, scratch_, rounds, stream, AHEAD_CHAINED);
+}
+// host only, for tests: default_look_ahead() of a round that starts with `n_list` tiles
+extern "C" int ivx_flood_look_ahead(int64_t n_list, int32_t *look_ahead) {
+    IVX_REQUIRE(look_ahead && n_list >= 0, IVX_EINVAL, "flood_look_ahead: NULL or negative argument");
+    *look_ahead = default_look_ahead(n_list > 0xffffffffll ? 0xffffffffu : (unsigned)n_list);
+    return IVX_OK;
 }
 extern "C" int ivx_dev_flood_visits(const ivx_flood_plan *p, const void *scratch_, uint32_t out[2], void *stream) {
     IVX_REQUIRE(scratch_ && out, IVX_EINVAL, "flood_visits: NULL argument");
@@ -1801,7 +1928,7 @@ extern "C" int ivx_flood_describe(const ivx_flood_plan *p, int64_t nseeds, int32
 
 extern "C" int ivx_dev_flood_run_edges(const ivx_flood_plan *p, const uint64_t *edges, uint64_t *reached, void *scratch_,
                                        int *rounds, void *stream) {
-    return flood_run_impl(p, edges, ivx::FLOOD_DIRECTED, reached, scratch_, rounds, stream);
+    return flood_run_impl(p, edges, ivx::FLOOD_DIRECTED, reached, scratch_, rounds, stream, nullptr, AHEAD_CHAINED);
 }
 
 extern "C" int ivx_flood_edges_bytes(const ivx_flood_plan *p, size_t *nbytes) {
@@ -1933,17 +2060,8 @@ extern "C" int ivx_dev_flood_apply_levels(const ivx_flood_plan *p, const uint64_
     Tiles t;
     int rc = make_tiles(p, &t);
     if (rc) return rc;
-    IVX_REQUIRE(reached && inside_bits && mask, IVX_EINVAL, "flood_apply_levels: null plane or mask");
-    IVX_REQUIRE(t.dx % 64 == 0 && ((uintptr_t)mask & 15) == 0, IVX_EINVAL,
-                "flood_apply_levels: rows of whole 64-voxel words and a 16-byte aligned mask only");
-    IVX_REQUIRE(v_in >= 0 && v_in <= 255 && v_sel >= 0 && v_sel <= 255, IVX_EINVAL, "flood_apply_levels: levels are bytes");
-    const int64_t nchunks = t.dz * t.dy * t.dx / 16;
-    if (!nchunks) return IVX_OK;
-    const int64_t blocks = ivx::cdiv(nchunks, 1024);
-    hipLaunchKernelGGL(k_flood_apply_levels16<false>, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, ivx::S(stream),
-                       (const uint16_t *)reached, (const uint16_t *)inside_bits, nchunks, (uint4 *)mask, (uint8_t)v_in, (uint8_t)v_sel);
-    IVX_LAUNCH_CHECK();
-    return IVX_OK;
+    if ((rc = levels_check(t, reached, inside_bits, mask, v_in, v_sel, false))) return rc;
+    return launch_levels(t, reached, inside_bits, mask, v_in, v_sel, false, ApplyWhen{nullptr, nullptr, 0ull}, ivx::S(stream));
 }
 
 // the whole mask from its planes: v_sel where reached (NULL: nowhere), else v_in where inside, else 0 -- every byte is written
@@ -1952,17 +2070,31 @@ extern "C" int ivx_dev_mask_from_planes(const ivx_flood_plan *p, const uint64_t 
     Tiles t;
     int rc = make_tiles(p, &t);
     if (rc) return rc;
-    IVX_REQUIRE(inside_bits && mask, IVX_EINVAL, "mask_from_planes: null plane or mask");
-    IVX_REQUIRE(t.dx % 64 == 0 && ((uintptr_t)mask & 15) == 0 && (((uintptr_t)inside_bits | (uintptr_t)reached) & 7) == 0, IVX_EINVAL,
-                "mask_from_planes: rows of whole 64-voxel words, a 16-byte aligned mask and 8-byte aligned planes only");
-    IVX_REQUIRE(v_in >= 0 && v_in <= 255 && v_sel >= 0 && v_sel <= 255, IVX_EINVAL, "mask_from_planes: levels are bytes");
-    const int64_t nchunks = t.dz * t.dy * t.dx / 16;
-    if (!nchunks) return IVX_OK;
-    const int64_t blocks = ivx::cdiv(nchunks, 1024);
-    hipLaunchKernelGGL(k_flood_apply_levels16<true>, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, ivx::S(stream),
-                       (const uint16_t *)reached, (const uint16_t *)inside_bits, nchunks, (uint4 *)mask, (uint8_t)v_in, (uint8_t)v_sel);
-    IVX_LAUNCH_CHECK();
-    return IVX_OK;
+    if ((rc = levels_check(t, reached, inside_bits, mask, v_in, v_sel, true))) return rc;
+    return launch_levels(t, reached, inside_bits, mask, v_in, v_sel, true, ApplyWhen{nullptr, nullptr, 0ull}, ivx::S(stream));
+}
+
+// ivx_dev_flood_grow and the write of its result in one call.  The two writes from the bit planes are queued by the flood
+// itself while its lists run out (EarlyWrite); where that launch did not go ahead, or for another kind of write, the
+// write's kernel is queued as soon as the host has seen the flood end (the first round that starts empty, or whatever
+// path the flood took instead), without the way back to the caller in between, through the entry point it names.
+extern "C" int ivx_dev_flood_grow_select(const ivx_flood_plan *p, int dtype, const void *data, double t0, double t1,
+                                         const int64_t *seeds_xyz, int64_t nseeds, uint64_t *cand, uint64_t *reached,
+                                         void *scratch_, int *rounds, const ivx_flood_write *write, int look_ahead, void *stream) {
+    IVX_REQUIRE(write && write->kind >= IVX_FLOOD_WRITE_NONE && write->kind <= IVX_FLOOD_WRITE_APPLY_U8, IVX_EINVAL,
+                "flood_grow_select: no write description, or one of an unknown kind");
+    IVX_REQUIRE(write->kind == IVX_FLOOD_WRITE_NONE || write->mask, IVX_EINVAL, "flood_grow_select: the write has no mask");
+    EarlyWrite early = {write, false};
+    int rc = flood_grow_impl(p, dtype, data, t0, t1, seeds_xyz, nseeds, cand, reached, scratch_, rounds, stream, look_ahead, &early);
+    if (rc || early.written) return rc;
+    switch (write->kind) {
+    case IVX_FLOOD_WRITE_MASK_FROM_PLANES:
+        return ivx_dev_mask_from_planes(p, write->inside_bits, reached, write->mask, write->v_in, write->v_sel, stream);
+    case IVX_FLOOD_WRITE_APPLY_LEVELS:
+        return ivx_dev_flood_apply_levels(p, reached, write->inside_bits, write->mask, write->v_in, write->v_sel, stream);
+    case IVX_FLOOD_WRITE_APPLY_U8: return ivx_dev_flood_apply(p, reached, IVX_U8, write->mask, (double)write->v_sel, stream);
+    default: return IVX_OK;
+    }
 }
 
 extern "C" int ivx_dev_flood_apply2(const ivx_flood_plan *p, const uint64_t *reached, uint8_t *out, int fill,

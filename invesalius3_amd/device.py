@@ -180,8 +180,11 @@ class Timer:
             L.check(L.lib().ivx_event_record(e1, self.t.stream))
             self.t.spans.append((self.name, self.e0, e1))
 
+    def records(self, name) -> bool:
+        return self.only is None or name in self.only
+
     def span(self, name):
-        if self.only is not None and name not in self.only:
+        if not self.records(name):
             return Timer._OFF
         return Timer._Span(self, name)
 
@@ -241,6 +244,8 @@ class DeviceVolume:
         self._apply_levels = os.environ.get("IVX_APPLY_LEVELS", "1") != "0"  # (A/B: mask[reached] = v from the bit planes alone)
         self._use_ranges = os.environ.get("IVX_RANGES", "1") != "0"  # (A/B: threshold / candidates from the per-word records)
         self._mask_defer = os.environ.get("IVX_MASK_DEFER", "1") != "0"  # (A/B: plane-only threshold, mask bytes written later)
+        self._select = os.environ.get("IVX_FLOOD_SELECT", "1") != "0"  # (A/B: the flood's write queued by the flood's own call)
+        self._look_ahead = -1  # ivx_dev_flood_grow_select's look-ahead; negative = the library's default (tests drive 0 .. 3)
         # (min, max) of every 64-voxel x-word of the image (ivx_dev_image_ranges_i16): written by the first fused threshold
         # after the image's bytes changed, read by every later one.  Dropped with the image (_image_touched), like _range_valid.
         self._ranges = None
@@ -498,12 +503,19 @@ class DeviceVolume:
         self._before_flood()
         cand, shared = self._candidate_plane(image, t0, t1, fill)
         rounds = ctypes.c_int(0)
+        write = self._flood_write(fill, select_value) if self._select else None
         # clear + seed + run (an in-range seed is already a candidate here: the kernel's OR is a no-op on a shared plane)
-        L.check(lib.ivx_dev_flood_grow(p, L.I16, img_ptr, ctypes.c_double(t0), ctypes.c_double(t1), L.ptr(seeds),
-                                       c64(len(seeds)), cand.ptr, self.reached.ptr, self.flood_scratch.ptr,
-                                       ctypes.byref(rounds), st), "region_grow")
+        if write is not None:
+            # ... and the one kernel _apply_reached would queue, from the same call: it is in the stream when Python gets back
+            L.check(lib.ivx_dev_flood_grow_select(p, L.I16, img_ptr, ctypes.c_double(t0), ctypes.c_double(t1), L.ptr(seeds),
+                                                  c64(len(seeds)), cand.ptr, self.reached.ptr, self.flood_scratch.ptr,
+                                                  ctypes.byref(rounds), ctypes.byref(write), int(self._look_ahead), st), "region_grow")
+        else:
+            L.check(lib.ivx_dev_flood_grow(p, L.I16, img_ptr, ctypes.c_double(t0), ctypes.c_double(t1), L.ptr(seeds),
+                                           c64(len(seeds)), cand.ptr, self.reached.ptr, self.flood_scratch.ptr,
+                                           ctypes.byref(rounds), st), "region_grow")
         self._gate_armed = False  # an armed gate has been opened by this flood
-        self._apply_reached(fill, select_value, shared)
+        self._apply_reached(fill, select_value, shared, queued=write is not None)
         return rounds.value
 
     def flood_visits(self):
@@ -541,30 +553,52 @@ class DeviceVolume:
                                                  self.cand.ptr, self.stream))
         return self.cand, False
 
-    def _apply_reached(self, fill, select_value, shared):
-        """out_mask[reached] = fill and, when asked, mask[reached] = select_value; keeps the notes in step."""
+    def _write_kind(self, fill, select_value):
+        """Which single kernel writes the flood's result while out_mask's write can be deferred (L.FLOOD_WRITE_*), from the
+        volume's notes alone -- the flood's outcome has no say; None where out_mask's bytes have to be written as well."""
+        if not (self._out_logically_zero() and int(fill) != 0):
+            return None
+        if select_value is not None and self._mask_levels == (255, None) and self._mbits_valid and self._apply_levels:
+            # the mask's bytes are still to be written: one pass writes all of them, the selected ones as select_value; or
+            # mask == 255 * plane, byte for byte: a touched chunk's bytes follow from the two bit planes, no byte is read
+            return L.FLOOD_WRITE_MASK_FROM_PLANES if self._mask_pending else L.FLOOD_WRITE_APPLY_LEVELS
+        return L.FLOOD_WRITE_APPLY_U8 if select_value is not None else L.FLOOD_WRITE_NONE
+
+    def _flood_write(self, fill, select_value):
+        """The write for ivx_dev_flood_grow_select to queue behind the flood it is about to run, or None where the two calls
+        stay: out_mask's bytes are due too (ivx_dev_flood_apply2 or its own pass), or the timer wants the write's span."""
+        kind = self._write_kind(fill, select_value)
+        if kind is None or (kind == L.FLOOD_WRITE_MASK_FROM_PLANES and self.timer.records("mask_bytes")):
+            return None
+        if kind == L.FLOOD_WRITE_APPLY_U8:
+            self._materialize_mask()  # that kernel changes bytes of a mask that has to be there: the flood does not touch it
+        return L.FloodWrite(kind=kind, v_in=255, v_sel=int(select_value) if select_value is not None else 0,
+                            inside_bits=self._mbits.ptr.value, mask=self.mask.raw.value)
+
+    def _apply_reached(self, fill, select_value, shared, queued=False):
+        """out_mask[reached] = fill and, when asked, mask[reached] = select_value; keeps the notes in step.
+        `queued`: ivx_dev_flood_grow_select has queued the kernel of _write_kind() already."""
         lib, p, st = L.lib(), ctypes.byref(self.plan), self.stream
         if select_value is not None:
             self._mp_cells_valid = False
-        defer = self._out_logically_zero() and int(fill) != 0
-        levels = select_value is not None and self._mask_levels == (255, None) and self._mbits_valid and self._apply_levels
-        if not (defer and levels):
+        kind = self._write_kind(fill, select_value)
+        assert kind is not None or not queued
+        if kind not in (L.FLOOD_WRITE_MASK_FROM_PLANES, L.FLOOD_WRITE_APPLY_LEVELS):
             self._materialize_mask()
         else:
             self._defer_pays = True  # a threshold's mask met the flood's apply untouched: the next one defers (again)
-        if defer:
+        if kind is not None:
             self._out_pending = int(fill)  # bytes stay zero; self.reached carries the result until it is needed
-            if levels and self._mask_pending:
-                # the mask's bytes are still to be written: this pass writes all of them, the selected ones as select_value
-                with self.timer.span("mask_bytes"):
-                    L.check(lib.ivx_dev_mask_from_planes(p, self._mbits.ptr, self.reached.ptr, self.mask.raw, 255, int(select_value),
-                                                         st), "mask_from_planes")
+            if kind == L.FLOOD_WRITE_MASK_FROM_PLANES:
+                if not queued:
+                    with self.timer.span("mask_bytes"):
+                        L.check(lib.ivx_dev_mask_from_planes(p, self._mbits.ptr, self.reached.ptr, self.mask.raw, 255,
+                                                             int(select_value), st), "mask_from_planes")
                 self._mask_pending = False
-            elif levels:
-                # mask == 255 * plane, byte for byte: a touched chunk's bytes follow from the two bit planes, no byte is read
+            elif kind == L.FLOOD_WRITE_APPLY_LEVELS and not queued:
                 L.check(lib.ivx_dev_flood_apply_levels(p, self.reached.ptr, self._mbits.ptr, self.mask.raw, 255, int(select_value), st),
                         "flood_apply_levels")
-            elif select_value is not None:
+            elif kind == L.FLOOD_WRITE_APPLY_U8 and not queued:
                 L.check(lib.ivx_dev_flood_apply(p, self.reached.ptr, L.U8, self.mask.raw, ctypes.c_double(int(select_value)), st))
         elif select_value is not None:
             L.check(lib.ivx_dev_flood_apply2(p, self.reached.ptr, self.out_mask.raw, int(fill), self.mask.raw,

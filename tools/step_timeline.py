@@ -1,13 +1,13 @@
 """Print the kernel timeline of the last complete bench step from a rocprofv3 kernel trace CSV
 (rocprofv3 --kernel-trace --output-format csv ... -- python bench.py): start offset, gap to the previous
-kernel's end, duration, grid, name.  A step runs from one k_threshold16_bits to the next; the next step's threshold is
+kernel's end, duration, grid, name.  A step runs from one k_threshold16* kernel to the next; the next step's threshold is
 printed as the last line, so its gap is what the GPU waited for between two steps."""
 import csv
 import sys
 
 rows = list(csv.DictReader(open(sys.argv[1])))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-idx = [i for i, r in enumerate(rows) if "k_threshold16_bits" in r["Kernel_Name"]]
+idx = [i for i, r in enumerate(rows) if "k_threshold16" in r["Kernel_Name"]]  # (_bits, _plane, _plane_use: whichever the step runs)
 i0, i1 = idx[-2], idx[-1]
 t0 = int(rows[i0]["Start_Timestamp"])
 prev = t0
