@@ -943,6 +943,19 @@ typedef struct ivx_flood_write {
 int ivx_dev_flood_grow_select(const ivx_flood_plan *p, int dtype, const void *data, double t0, double t1,
                               const int64_t *seeds_xyz, int64_t nseeds, uint64_t *cand, uint64_t *reached, void *scratch,
                               int *rounds, const ivx_flood_write *write, int look_ahead, void *stream);
+/* ivx_dev_flood_grow_select for a flood that a surface call follows.  Marching cubes' count reads the inside plane only, and
+ * nothing in the stream reads the bytes the write produces, so where `write` is one of the two writes from the bit planes
+ * (and dx % 64 == 0 etc. as they require) every launch of it is one kernel that also counts the triangles of the piece `mc`
+ * (one iso-value, ny == dy, nx == dx, nz <= dz; its inside plane is write->inside_bits from slice 0) into `mc_scratch`: the
+ * count's dependent loads run under the write's stores.  The scan is queued behind the launch that went ahead and
+ * *counted = 1: `mc_scratch` is then what ivx_dev_mc_count_bits_async(mc, write->inside_bits, mc_scratch, stream) leaves, and
+ * ivx_dev_mc_list / _emit* / _total_early may follow.  Otherwise -- another write kind, a piece that does not fit, the
+ * union-find escape, IVX_FLOOD_MODE=ccl -- the call is ivx_dev_flood_grow_select and *counted = 0.  Same mask bytes, same
+ * counts as the separate calls. */
+int ivx_dev_flood_grow_select_count(const ivx_flood_plan *p, int dtype, const void *data, double t0, double t1,
+                                    const int64_t *seeds_xyz, int64_t nseeds, uint64_t *cand, uint64_t *reached, void *scratch,
+                                    int *rounds, const ivx_flood_write *write, int look_ahead, const ivx_mc_params *mc,
+                                    void *mc_scratch, int *counted, void *stream);
 /* host only, for tests: the default look-ahead behind a round that starts with `n_list` tiles on its list */
 int ivx_flood_look_ahead(int64_t n_list, int32_t *look_ahead);
 /* both writes of a GUI region-grow in one pass: out[v] = fill and mask[v] = select where reached

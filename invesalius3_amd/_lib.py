@@ -103,6 +103,10 @@ def _declare(lib):
                        ("ivx_dev_flood_grow_select", [ctypes.POINTER(FloodPlan), ctypes.c_int, c_vp, ctypes.c_double, ctypes.c_double,
                                                       c_vp, c_i64, c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_int),
                                                       ctypes.POINTER(FloodWrite), ctypes.c_int, c_vp]),
+                       ("ivx_dev_flood_grow_select_count", [ctypes.POINTER(FloodPlan), ctypes.c_int, c_vp, ctypes.c_double, ctypes.c_double,
+                                                            c_vp, c_i64, c_vp, c_vp, c_vp, ctypes.POINTER(ctypes.c_int),
+                                                            ctypes.POINTER(FloodWrite), ctypes.c_int, ctypes.POINTER(McParams), c_vp,
+                                                            ctypes.POINTER(ctypes.c_int), c_vp]),
                        ("ivx_flood_look_ahead", [c_i64, ctypes.POINTER(ctypes.c_int32)]),
                        # the image geometry tools (flip, swap axes, gantry tilt) and the calls that keep a mask's zeros off the link
                        ("ivx_dev_image_flip", [c_vp, c_i64, c_i64, c_i64, sz, ctypes.c_int, c_vp]),

@@ -118,6 +118,17 @@ enum FloodMode {
 int flood_run(const ivx_flood_plan *p, const uint64_t *planes, FloodMode mode, uint64_t *reached, void *scratch, int *rounds,
               void *stream);
 
+// Marching cubes' count in the launch of a flood's mask write (k_mc.hip; ivx_dev_flood_grow_select_count in k_flood.hip).
+// mc_ride_ok: can the piece `p` be counted from the inside plane of a (dz, dy, dx) volume?  mc_ride_begin: the piece record
+// of a count from that plane.  mc_ride_launch: the write (levels_write.h) and the count as one kernel, under `when`;
+// mc_ride_scan: the count's scan, behind the launch that went ahead.
+struct ApplyWhen;
+bool mc_ride_ok(const ivx_mc_params *p, const void *scratch, int64_t dz, int64_t dy, int64_t dx);
+void mc_ride_begin(void *scratch, const uint64_t *inside_bits);
+int mc_ride_launch(const ivx_mc_params *p, void *scratch, const uint64_t *reached, const uint64_t *inside, int64_t nchunks, uint8_t *mask,
+                   int v_in, int v_sel, bool all, const ApplyWhen &when, hipStream_t st);
+int mc_ride_scan(const ivx_mc_params *p, void *scratch, hipStream_t st);
+
 // GPU -> host mailbox in pinned, host-coherent memory: a 1-thread kernel copies up to 32 dwords and then stores a
 // sequence number; the host spins on the sequence word instead of paying a stream synchronisation round trip
 // (~5 us instead of ~40 us).  Falls back to hipStreamSynchronize if the word does not arrive in time.

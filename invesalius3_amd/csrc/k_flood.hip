@@ -37,7 +37,10 @@
 #include <stdlib.h>
 
 #include "flood_tiles.h"
+#include "levels_write.h"
 #include "words_from_records.h" // short8_t, words_from_records
+
+using ivx::ApplyWhen;
 
 namespace {
 
@@ -1199,44 +1202,19 @@ __global__ __launch_bounds__(256) void k_flood_apply16(const uint16_t *__restric
 // chunk's 16 bytes after its bits have arrived: a second, dependent round trip).  Chunks without a reached bit are not written
 // -- unless ALL: then `out` holds nothing yet (a plane-only threshold) and every chunk is written, `reached` may be NULL (no
 // bit), and a wave's four stores are 1 KiB contiguous each.
-// WHEN: the launch was queued before the flood's end was known (flood_run_impl).  It goes ahead only if the list of the
-// round that would run next is empty -- the flood is over, `reached` is final -- and then says so in word 2 of the progress
-// line as it starts; otherwise every workgroup returns at once.  `next_len` NULL: unconditional.
-struct ApplyWhen {
-    const unsigned int *next_len;
-    unsigned long long *line;
-    unsigned long long report;
-};
+// WHEN (ivx::ApplyWhen, levels_write.h, with the body both this kernel and marching cubes' k_mc_count_write run): the launch
+// was queued before the flood's end was known and goes ahead only if the next round's list is empty.
 template <bool ALL>
 __global__ __launch_bounds__(256) void k_flood_apply_levels16(const uint16_t *__restrict__ reached, const uint16_t *__restrict__ inside,
                                                               int64_t nchunks, uint4 *__restrict__ out, uint8_t v_in, uint8_t v_sel,
                                                               ApplyWhen when) {
-    if (when.next_len) {
-        if (*when.next_len != 0u) return; // (nothing in the stream writes the counter while this kernel runs)
-        if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&when.line[2], when.report, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if (ivx::apply_when_skips(when)) return;
     const int64_t stride = (int64_t)gridDim.x * 1024;
     const unsigned int in4 = 0x01010101u * v_in, sel4 = 0x01010101u * v_sel;
     for (int64_t i0 = (int64_t)blockIdx.x * 1024 + threadIdx.x; i0 < nchunks; i0 += stride) {
-        unsigned int m[4], b[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int64_t i = i0 + u * 256;
-            m[u] = i < nchunks && (!ALL || reached) ? reached[i] : 0u;
-            b[u] = i < nchunks ? inside[i] : 0u;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            if (ALL ? i0 + u * 256 >= nchunks : !m[u]) continue;
-            // bit e of four -> 0xff in byte e (the products' bits e + 7 k are all different: no carries)
-            auto bytes = [](unsigned int bits4) { return ((bits4 * 0x00204081u) & 0x01010101u) * 0xffu; };
-            auto word = [&](unsigned int r4, unsigned int i4) {
-                const unsigned int rs = bytes(r4);
-                return (sel4 & rs) | (in4 & bytes(i4) & ~rs);
-            };
-            out[i0 + u * 256] = make_uint4(word(m[u] & 15u, b[u] & 15u), word(m[u] >> 4 & 15u, b[u] >> 4 & 15u),
-                                           word(m[u] >> 8 & 15u, b[u] >> 8 & 15u), word(m[u] >> 12 & 15u, b[u] >> 12 & 15u));
-        }
+        ivx::LevelsWords w;
+        ivx::levels_load<ALL>(reached, inside, nchunks, i0, w);
+        ivx::levels_store<ALL>(w, nchunks, i0, out, in4, sel4);
     }
 }
 
@@ -1617,10 +1595,16 @@ static int levels_check(const Tiles &t, const uint64_t *reached, const uint64_t 
     }
     return IVX_OK;
 }
+// `ride`: the launch is marching cubes' k_mc_count_write, which does this write and the count of the piece `ride->p`
+struct McRide {
+    const ivx_mc_params *p;
+    void *scratch;
+};
 static int launch_levels(const Tiles &t, const uint64_t *reached, const uint64_t *inside, uint8_t *mask, int v_in, int v_sel, bool all,
-                         const ApplyWhen &when, hipStream_t st) {
+                         const ApplyWhen &when, hipStream_t st, const McRide *ride = nullptr) {
     const int64_t nchunks = t.dz * t.dy * t.dx / 16;
     if (!nchunks) return IVX_OK;
+    if (ride) return ivx::mc_ride_launch(ride->p, ride->scratch, reached, inside, nchunks, mask, v_in, v_sel, all, when, st);
     const int64_t blocks = ivx::cdiv(nchunks, 1024);
     auto k = all ? k_flood_apply_levels16<true> : k_flood_apply_levels16<false>;
     hipLaunchKernelGGL(k, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, st, (const uint16_t *)reached,
@@ -1644,9 +1628,14 @@ static int default_look_ahead(unsigned n_list) { return n_list >= AHEAD_LONG_LIS
 // (ApplyWhen): empty, and the write runs where the first idle round would have; not empty, and it costs ~3 us.  One such
 // launch is outstanding at a time and at most EARLY_TRIES per flood, so a flood whose lists shrink and recover pays
 // ~6 us at most.  `written` comes back true when such a launch went ahead: the caller then has nothing left to queue.
+// `ride`: every launch of the write for this flood carries the count (McRide), so the one that goes ahead counts.  `plain`
+// comes back true when the flood took the union-find path instead of ending on its rounds: the write is then queued as
+// before, and nothing of marching cubes behind it.
 struct EarlyWrite {
     const ivx_flood_write *w;
     bool written;
+    const McRide *ride = nullptr;
+    bool plain = false;
 };
 constexpr unsigned EARLY_BELOW = 96u;
 constexpr int EARLY_TRIES = 2;
@@ -1686,6 +1675,7 @@ static int flood_run_impl(const ivx_flood_plan *p, const uint64_t *cand, ivx::Fl
         if (rounds) *rounds = 1;
         // the dirty-tile list is not used by this path; keep it empty so a later frontier run starts clean
         IVX_HIP(hipMemsetAsync(dirty[0], 0, (size_t)t.ntiles, st));
+        if (early) early->plain = true;
         return ivx::ccl_run(p, cand, reached, scratch_, st);
     }
     int total_rounds = 0;
@@ -1800,7 +1790,7 @@ static int flood_run_impl(const ivx_flood_plan *p, const uint64_t *cand, ivx::Fl
             early_report = ((unsigned long long)tag << 56) | ((unsigned long long)(queued & 0xffffff) << 32) | 1ull;
             if (trace) fprintf(stderr, "ivx flood: write queued behind round %lld\n", (long long)queued);
             rc = launch_levels(t, reached, early->w->inside_bits, early->w->mask, early->w->v_in, early->w->v_sel, early_all,
-                               ApplyWhen{cnt + queued % RING, (unsigned long long *)line, early_report}, st);
+                               ApplyWhen{cnt + queued % RING, (unsigned long long *)line, early_report}, st, early->ride);
             if (rc) return rc;
         }
         prev_list = n_list;
@@ -1813,6 +1803,7 @@ static int flood_run_impl(const ivx_flood_plan *p, const uint64_t *cand, ivx::Fl
             IVX_HIP(hipMemsetAsync(dirty[1], 0, (size_t)t.ntiles, st));
             if ((rc = ivx::ccl_run(p, cand, reached, scratch_, st))) return rc;
             total_rounds += 1;
+            if (early) early->plain = true;
             break;
         }
         IVX_REQUIRE(total_rounds < (1 << 24) - 64, IVX_EHIP, "flood: did not converge");
@@ -2078,23 +2069,70 @@ extern "C" int ivx_dev_mask_from_planes(const ivx_flood_plan *p, const uint64_t 
 // itself while its lists run out (EarlyWrite); where that launch did not go ahead, or for another kind of write, the
 // write's kernel is queued as soon as the host has seen the flood end (the first round that starts empty, or whatever
 // path the flood took instead), without the way back to the caller in between, through the entry point it names.
-extern "C" int ivx_dev_flood_grow_select(const ivx_flood_plan *p, int dtype, const void *data, double t0, double t1,
-                                         const int64_t *seeds_xyz, int64_t nseeds, uint64_t *cand, uint64_t *reached,
-                                         void *scratch_, int *rounds, const ivx_flood_write *write, int look_ahead, void *stream) {
+static int grow_select_impl(const ivx_flood_plan *p, int dtype, const void *data, double t0, double t1, const int64_t *seeds_xyz,
+                            int64_t nseeds, uint64_t *cand, uint64_t *reached, void *scratch_, int *rounds, const ivx_flood_write *write,
+                            int look_ahead, const ivx_mc_params *mc, void *mc_scratch, int *counted, void *stream) {
     IVX_REQUIRE(write && write->kind >= IVX_FLOOD_WRITE_NONE && write->kind <= IVX_FLOOD_WRITE_APPLY_U8, IVX_EINVAL,
                 "flood_grow_select: no write description, or one of an unknown kind");
     IVX_REQUIRE(write->kind == IVX_FLOOD_WRITE_NONE || write->mask, IVX_EINVAL, "flood_grow_select: the write has no mask");
+    if (counted) *counted = 0;
     EarlyWrite early = {write, false};
-    int rc = flood_grow_impl(p, dtype, data, t0, t1, seeds_xyz, nseeds, cand, reached, scratch_, rounds, stream, look_ahead, &early);
-    if (rc || early.written) return rc;
-    switch (write->kind) {
-    case IVX_FLOOD_WRITE_MASK_FROM_PLANES:
-        return ivx_dev_mask_from_planes(p, write->inside_bits, reached, write->mask, write->v_in, write->v_sel, stream);
-    case IVX_FLOOD_WRITE_APPLY_LEVELS:
-        return ivx_dev_flood_apply_levels(p, reached, write->inside_bits, write->mask, write->v_in, write->v_sel, stream);
-    case IVX_FLOOD_WRITE_APPLY_U8: return ivx_dev_flood_apply(p, reached, IVX_U8, write->mask, (double)write->v_sel, stream);
-    default: return IVX_OK;
+    const bool all = write->kind == IVX_FLOOD_WRITE_MASK_FROM_PLANES;
+    const McRide ride = {mc, mc_scratch};
+    Tiles t;
+    int rc = make_tiles(p, &t);
+    if (rc) return rc;
+    if (mc && counted && (all || write->kind == IVX_FLOOD_WRITE_APPLY_LEVELS) &&
+        levels_check(t, reached, write->inside_bits, write->mask, write->v_in, write->v_sel, all) == IVX_OK &&
+        ivx::mc_ride_ok(mc, mc_scratch, t.dz, t.dy, t.dx)) {
+        early.ride = &ride;
+        ivx::mc_ride_begin(mc_scratch, write->inside_bits); // (the count reads the write's inside plane in place)
     }
+    rc = flood_grow_impl(p, dtype, data, t0, t1, seeds_xyz, nseeds, cand, reached, scratch_, rounds, stream, look_ahead, &early);
+    if (rc) return rc;
+    const bool fused = early.ride && !early.plain;
+    if (!early.written) {
+        switch (write->kind) {
+        case IVX_FLOOD_WRITE_MASK_FROM_PLANES:
+        case IVX_FLOOD_WRITE_APPLY_LEVELS:
+            if (fused)
+                rc = launch_levels(t, reached, write->inside_bits, write->mask, write->v_in, write->v_sel, all, ApplyWhen{nullptr, nullptr, 0ull},
+                                   ivx::S(stream), &ride);
+            else if (all)
+                rc = ivx_dev_mask_from_planes(p, write->inside_bits, reached, write->mask, write->v_in, write->v_sel, stream);
+            else
+                rc = ivx_dev_flood_apply_levels(p, reached, write->inside_bits, write->mask, write->v_in, write->v_sel, stream);
+            break;
+        case IVX_FLOOD_WRITE_APPLY_U8: rc = ivx_dev_flood_apply(p, reached, IVX_U8, write->mask, (double)write->v_sel, stream); break;
+        default: break;
+        }
+        if (rc) return rc;
+    }
+    if (fused) { // the launch that went ahead has counted: the scan behind it, and the caller has a counted piece
+        if ((rc = ivx::mc_ride_scan(mc, mc_scratch, ivx::S(stream)))) return rc;
+        *counted = 1;
+    }
+    return IVX_OK;
+}
+extern "C" int ivx_dev_flood_grow_select(const ivx_flood_plan *p, int dtype, const void *data, double t0, double t1,
+                                         const int64_t *seeds_xyz, int64_t nseeds, uint64_t *cand, uint64_t *reached,
+                                         void *scratch_, int *rounds, const ivx_flood_write *write, int look_ahead, void *stream) {
+    return grow_select_impl(p, dtype, data, t0, t1, seeds_xyz, nseeds, cand, reached, scratch_, rounds, write, look_ahead, nullptr, nullptr,
+                            nullptr, stream);
+}
+// ivx_dev_flood_grow_select for a flood that a surface call follows: where the write is one of the two from the bit planes,
+// every launch of it is marching cubes' count of the piece `mc` from the write's inside plane in the same kernel
+// (k_mc_count_write, k_mc.hip), with the scan queued behind the launch that went ahead; *counted = 1 then, and the piece in
+// `mc_scratch` is what ivx_dev_mc_count_bits_async(mc, write->inside_bits, mc_scratch, stream) would have left.  Every other
+// write kind, a piece the plane does not fit, the union-find escape and IVX_FLOOD_MODE=ccl: the write as
+// ivx_dev_flood_grow_select queues it, *counted = 0 and nothing of marching cubes in the stream.
+extern "C" int ivx_dev_flood_grow_select_count(const ivx_flood_plan *p, int dtype, const void *data, double t0, double t1,
+                                               const int64_t *seeds_xyz, int64_t nseeds, uint64_t *cand, uint64_t *reached,
+                                               void *scratch_, int *rounds, const ivx_flood_write *write, int look_ahead,
+                                               const ivx_mc_params *mc, void *mc_scratch, int *counted, void *stream) {
+    IVX_REQUIRE(mc && mc_scratch && counted, IVX_EINVAL, "flood_grow_select_count: null piece, scratch or result");
+    return grow_select_impl(p, dtype, data, t0, t1, seeds_xyz, nseeds, cand, reached, scratch_, rounds, write, look_ahead, mc, mc_scratch,
+                            counted, stream);
 }
 
 extern "C" int ivx_dev_flood_apply2(const ivx_flood_plan *p, const uint64_t *reached, uint8_t *out, int fill,

@@ -18,6 +18,9 @@
 //                    word) with per-piece magic multipliers (McDiv), and a wave whose rows are all source rows
 //                    takes load_corners' interior form (no clamps, no row tests, one row base per lane): 344 ->
 //                    177 VALU in front of the first barrier, 34.0 -> 27.4 us at 512^3.
+//   2w. k_mc_count_write  the count with the mask write of a flood that ends in front of the surface call carried by the same
+//                    lanes (levels_write.h; ivx_dev_flood_grow_select_count): 134 MB of stores under the count's dependent
+//                    loads, 38 us for the pair instead of 22 + 26 (profiles/mc_ride_ab.md).
 //   3. k_mc_scan     exclusive scan of the per-workgroup sums (u64 offsets), one workgroup per 16 384 sums,
 //                    consecutive lanes on consecutive sums (16-byte loads and stores): 11.4 -> 4.9 us.
 //   3b. k_mc_list    one 64-bit descriptor per triangle in output order: the active cells of a workgroup's 256 words,
@@ -33,6 +36,7 @@
 // Vertex arithmetic is done in double and rounded once to float32, exactly like the oracle.
 #include <algorithm>
 
+#include "levels_write.h"
 #include "mc_common.h"
 
 #define MC_TABLE_QUAL static __device__ __attribute__((aligned(16))) const
@@ -255,9 +259,18 @@ __device__ __forceinline__ Corner8 load_corners(const uint64_t *__restrict__ bit
 // ONE or two full waves instead of being scattered over four mostly idle ones (37 -> 34 us on the bench volume).  What
 // every lane of every wave runs in front of the first barrier costs as much as the walks: see load_corners' interior form and
 // mc_split_wid.  A workgroup without active cells (54 % of them on the bench surface) leaves after the first barrier.
-__global__ __launch_bounds__(256) void k_mc_count(const uint64_t *__restrict__ bits, Geom g, size_t nwords,
-                                                  uint64_t pbits, uint16_t *__restrict__ counts,
-                                                  uint32_t *__restrict__ bsum) {
+// RIDE: the same lanes also carry the flood's mask write (levels_write.h; k_mc_count_write below).  The write's plane words are
+// loaded with the corner words, its stores leave once the corner words have been consumed -- a workgroup that leaves after the
+// first barrier stores before it leaves --, and nothing behind them waits for memory: the walk reads LDS only.
+struct McRideArgs {
+    const uint16_t *reached, *inside; // the write's two planes as 16-bit words, one per chunk of 16 voxels
+    int64_t nchunks;
+    uint4 *out;
+    unsigned int in4, sel4;
+};
+template <bool RIDE, bool ALL>
+__device__ __forceinline__ void mc_count_body(const uint64_t *__restrict__ bits, const Geom &g, size_t nwords, uint64_t pbits,
+                                              uint16_t *__restrict__ counts, uint32_t *__restrict__ bsum, const McRideArgs &ride) {
     __shared__ uint32_t s_part[4], s_wcnt[4];
     __shared__ uint8_t s_ntri[256];
     __shared__ uint64_t s_c[256][5]; // per active word: the four even corner words + the active mask
@@ -265,6 +278,25 @@ __global__ __launch_bounds__(256) void k_mc_count(const uint64_t *__restrict__ b
     __shared__ uint16_t s_slot[256];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const uint8_t ntri = MC_NTRI[tid]; // (in flight with the corner loads; stored below, when they are back)
+    // the write's first stretch: the workgroup's own, as in k_flood_apply_levels16 (1 KiB per store instruction of a wave)
+    const int64_t ride_i0 = (int64_t)blockIdx.x * 1024 + tid;
+    LevelsWords lw;
+    if (RIDE) levels_load<ALL>(ride.reached, ride.inside, ride.nchunks, ride_i0, lw);
+    // the stretches beyond the grid's first trip (a count's grid may be shorter than the write's), by whoever is leaving
+    auto ride_rest = [&]() {
+        if (!RIDE) return;
+        const int64_t stride = (int64_t)gridDim.x * 1024;
+        for (int64_t i0 = ride_i0 + stride; i0 < ride.nchunks; i0 += stride) {
+            LevelsWords w2;
+            levels_load<ALL>(ride.reached, ride.inside, ride.nchunks, i0, w2);
+            levels_store<ALL>(w2, ride.nchunks, i0, ride.out, ride.in4, ride.sel4);
+        }
+    };
+    auto ride_store = [&]() {
+#if !defined(IVX_RIDE_NO_STORES)
+        if (RIDE) levels_store<ALL>(lw, ride.nchunks, ride_i0, ride.out, ride.in4, ride.sel4);
+#endif
+    };
     const size_t wid = (size_t)blockIdx.x * 256 + tid;
     uint64_t act = 0;
     Corner8 r;
@@ -275,6 +307,9 @@ __global__ __launch_bounds__(256) void k_mc_count(const uint64_t *__restrict__ b
         act = r.active;
         if (!act) counts[wid] = 0;
     }
+#if defined(IVX_RIDE_STORES_EARLY) // (A/B: the stores in front of the first barrier)
+    ride_store();
+#endif
     const unsigned long long am = __ballot(act != 0);
     if (lane == 0) s_wcnt[wv] = (uint32_t)__popcll(am);
     s_ntri[tid] = ntri;
@@ -282,8 +317,19 @@ __global__ __launch_bounds__(256) void k_mc_count(const uint64_t *__restrict__ b
     uint32_t before = 0;
     for (int q = 0; q < wv; q++) before += s_wcnt[q];
     const uint32_t nact = s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
+#if !defined(IVX_RIDE_STORES_EARLY)
+    ride_store();
+#endif
+#if defined(IVX_RIDE_NO_WALK) // (A/B: the count's second half compiled out; the counts are then wrong)
+    if (RIDE) {
+        if (tid == 0) bsum[blockIdx.x] = 0;
+        ride_rest();
+        return;
+    }
+#endif
     if (!nact) { // (uniform) no active cell in the 256 words, as in 5 006 workgroups of 9 253 on the bench surface
         if (tid == 0) bsum[blockIdx.x] = 0;
+        ride_rest();
         return;
     }
     if (act) {
@@ -323,6 +369,23 @@ __global__ __launch_bounds__(256) void k_mc_count(const uint64_t *__restrict__ b
     if (lane == 0) s_part[wv] = s;
     __syncthreads();
     if (tid == 0) bsum[blockIdx.x] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+    ride_rest();
+}
+__global__ __launch_bounds__(256) void k_mc_count(const uint64_t *__restrict__ bits, Geom g, size_t nwords,
+                                                  uint64_t pbits, uint16_t *__restrict__ counts,
+                                                  uint32_t *__restrict__ bsum) {
+    mc_count_body<false, false>(bits, g, nwords, pbits, counts, bsum, McRideArgs{});
+}
+// k_mc_count and k_flood_apply_levels16<ALL> in one launch, for a flood that ends in front of a surface call
+// (ivx_dev_flood_grow_select_count).  The grid is the count's; the write's stretches are handed out as that kernel hands them
+// out, a second trip where the count's grid is the shorter one.  WHEN as there: a launch that finds the next round's list
+// not empty returns at once, count included -- the launch that goes ahead is the one that counts.
+template <bool ALL>
+__global__ __launch_bounds__(256) void k_mc_count_write(const uint64_t *__restrict__ bits, Geom g, size_t nwords, uint64_t pbits,
+                                                        uint16_t *__restrict__ counts, uint32_t *__restrict__ bsum, McRideArgs ride,
+                                                        ApplyWhen when) {
+    if (apply_when_skips(when)) return;
+    mc_count_body<true, ALL>(bits, g, nwords, pbits, counts, bsum, ride);
 }
 
 // ---- 3. scan of workgroup sums (single workgroup of 1024) ---------------------------------------------
@@ -840,6 +903,39 @@ static int mc_read_total_early(const ivx_mc_params *p, const Scratch &s, void *s
     return mc_read_total(p, s, scratch_, ntris, st);
 }
 
+// The three parts of a count behind the inside planes.  (1) the piece record: whatever was counted into the scratch before is
+// void, a plane handed in is read in place until the next count.  (2) classify + count, one launch per iso-value.  (3) the scan
+// of the workgroup sums, which -- for one iso-value -- publishes the total itself under a mailbox number the record keeps.
+static void mc_count_record(void *scratch_, const uint64_t *inside_bits) { mc_pieces().begin_count(scratch_, inside_bits); }
+static int mc_count_launch(const ivx_mc_params *p, const Geom &g, const Scratch &s, void *scratch_, hipStream_t st) {
+    char *scratch = (char *)scratch_;
+    uint32_t *bsum = (uint32_t *)(scratch + s.off_bsum);
+    for (int q = 0; q < p->niso; q++) {
+        const uint64_t *bits = mc_bits_ptr(scratch, s, q);
+        uint16_t *counts = (uint16_t *)(scratch + s.off_counts) + (size_t)q * s.nwords;
+        hipLaunchKernelGGL(k_mc_count, dim3((unsigned)s.nblocks), dim3(256), 0, st, bits, g, s.nwords, pad_bits(p, q),
+                           counts, bsum + (size_t)q * s.nblocks);
+        IVX_LAUNCH_CHECK();
+    }
+    return IVX_OK;
+}
+static int mc_count_scan(const ivx_mc_params *p, const Scratch &s, void *scratch_, hipStream_t st) {
+    char *scratch = (char *)scratch_;
+    uint32_t *bsum = (uint32_t *)(scratch + s.off_bsum);
+    uint64_t *boff = (uint64_t *)(scratch + s.off_boff);
+    const size_t nb = s.nblocks * (size_t)p->niso;
+    uint32_t *mb = nullptr, seq = 0;
+    if (p->niso == 1) { // the scan publishes the total itself (ivx_dev_mc_total_early; two iso-values need the split too)
+        int rc = ivx::mailbox_reserve(&mb, &seq);
+        if (rc) return rc;
+        mc_pieces().set_total_seq(scratch_, seq);
+    }
+    hipLaunchKernelGGL(k_mc_scan, dim3((unsigned)std::max<size_t>(1, (nb + 16383) / 16384)), dim3(1024), 0, st, bsum, nb, boff, mb,
+                       seq);
+    IVX_LAUNCH_CHECK();
+    return IVX_OK;
+}
+
 // A count: [the inside planes of the voxels `a` into the scratch, unless the caller hands in the plane of its one iso-value,]
 // classify + count + scan (queued, nothing comes back to the host), and -- when `ntris` is wanted -- the total
 static int mc_count_impl(const ivx_mc_params *p, const void *a, const uint64_t *inside_bits, void *scratch_, int64_t *ntris,
@@ -855,27 +951,48 @@ static int mc_count_impl(const ivx_mc_params *p, const void *a, const uint64_t *
     IVX_REQUIRE(a || inside_bits, IVX_EINVAL, "mc_count: neither voxels nor an inside plane");
     char *scratch = (char *)scratch_;
     hipStream_t st = S(stream);
-    mc_pieces().begin_count(scratch_, inside_bits); // (a plane handed in is read in place until the next count on this scratch)
+    mc_count_record(scratch_, inside_bits);
     if (!inside_bits && (rc = mc_inside_planes(p, g, s, a, scratch + s.off_bits, p->iso[0], p->iso[1], st))) return rc;
-    uint32_t *bsum = (uint32_t *)(scratch + s.off_bsum);
-    uint64_t *boff = (uint64_t *)(scratch + s.off_boff);
-    for (int q = 0; q < p->niso; q++) {
-        const uint64_t *bits = mc_bits_ptr(scratch, s, q);
-        uint16_t *counts = (uint16_t *)(scratch + s.off_counts) + (size_t)q * s.nwords;
-        hipLaunchKernelGGL(k_mc_count, dim3((unsigned)s.nblocks), dim3(256), 0, st, bits, g, s.nwords, pad_bits(p, q),
-                           counts, bsum + (size_t)q * s.nblocks);
-        IVX_LAUNCH_CHECK();
-    }
-    const size_t nb = s.nblocks * (size_t)p->niso;
-    uint32_t *mb = nullptr, seq = 0;
-    if (p->niso == 1) { // the scan publishes the total itself (ivx_dev_mc_total_early; two iso-values need the split too)
-        if ((rc = ivx::mailbox_reserve(&mb, &seq))) return rc;
-        mc_pieces().set_total_seq(scratch_, seq);
-    }
-    hipLaunchKernelGGL(k_mc_scan, dim3((unsigned)std::max<size_t>(1, (nb + 16383) / 16384)), dim3(1024), 0, st, bsum, nb, boff, mb,
-                       seq);
-    IVX_LAUNCH_CHECK();
+    if ((rc = mc_count_launch(p, g, s, scratch_, st))) return rc;
+    if ((rc = mc_count_scan(p, s, scratch_, st))) return rc;
     return ntris ? mc_read_total_early(p, s, scratch_, ntris, st) : IVX_OK;
+}
+
+// ---- the count that rides on a flood's mask write (k_flood.hip: ivx_dev_flood_grow_select_count) ---------------------------
+// The piece must be one the count can take from the flood's own inside plane: one iso-value, rows as wide as the volume's,
+// and no more slices than the plane has.
+bool ivx::mc_ride_ok(const ivx_mc_params *p, const void *scratch, int64_t dz, int64_t dy, int64_t dx) {
+    Geom g;
+    Scratch s;
+    bool empty;
+    if (!p || !scratch || mc_piece_layout(p, &g, &s, &empty) != IVX_OK || empty) return false;
+    return p->niso == 1 && p->ny == dy && p->nx == dx && p->nz <= dz;
+}
+void ivx::mc_ride_begin(void *scratch, const uint64_t *inside_bits) { mc_count_record(scratch, inside_bits); }
+int ivx::mc_ride_launch(const ivx_mc_params *p, void *scratch_, const uint64_t *reached, const uint64_t *inside, int64_t nchunks,
+                        uint8_t *mask, int v_in, int v_sel, bool all, const ApplyWhen &when, hipStream_t st) {
+    Geom g;
+    Scratch s;
+    bool empty;
+    int rc = mc_piece_layout(p, &g, &s, &empty);
+    if (rc) return rc;
+    IVX_REQUIRE(!empty && p->niso == 1 && nchunks > 0, IVX_EINVAL, "mc_ride: an empty piece or volume, or two iso-values");
+    char *scratch = (char *)scratch_;
+    const McRideArgs ride = {(const uint16_t *)reached, (const uint16_t *)inside, nchunks, (uint4 *)mask, 0x01010101u * (uint8_t)v_in,
+                             0x01010101u * (uint8_t)v_sel};
+    auto k = all ? k_mc_count_write<true> : k_mc_count_write<false>;
+    hipLaunchKernelGGL(k, dim3((unsigned)s.nblocks), dim3(256), 0, st, mc_bits_ptr(scratch, s, 0), g, s.nwords, pad_bits(p, 0),
+                       (uint16_t *)(scratch + s.off_counts), (uint32_t *)(scratch + s.off_bsum), ride, when);
+    IVX_LAUNCH_CHECK();
+    return IVX_OK;
+}
+int ivx::mc_ride_scan(const ivx_mc_params *p, void *scratch, hipStream_t st) {
+    Geom g;
+    Scratch s;
+    bool empty;
+    int rc = mc_piece_layout(p, &g, &s, &empty);
+    if (rc) return rc;
+    return mc_count_scan(p, s, scratch, st);
 }
 
 extern "C" int ivx_dev_mc_count(const ivx_mc_params *p, const void *a, void *scratch_, int64_t *ntris, void *stream) {

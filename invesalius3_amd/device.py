@@ -14,6 +14,7 @@ from typing import NamedTuple, Optional
 import numpy as np
 
 from . import _lib as L
+from .mc_ride import RideBook
 
 
 class _MaskLevels(NamedTuple):
@@ -245,6 +246,8 @@ class DeviceVolume:
         self._use_ranges = os.environ.get("IVX_RANGES", "1") != "0"  # (A/B: threshold / candidates from the per-word records)
         self._mask_defer = os.environ.get("IVX_MASK_DEFER", "1") != "0"  # (A/B: plane-only threshold, mask bytes written later)
         self._select = os.environ.get("IVX_FLOOD_SELECT", "1") != "0"  # (A/B: the flood's write queued by the flood's own call)
+        # marching cubes' count in the launch of the flood's mask write (mc_ride.py has the rules); IVX_MC_RIDE=0: never
+        self._ride = RideBook(os.environ.get("IVX_MC_RIDE", "1") != "0")
         self._look_ahead = -1  # ivx_dev_flood_grow_select's look-ahead; negative = the library's default (tests drive 0 .. 3)
         # (min, max) of every 64-voxel x-word of the image (ivx_dev_image_ranges_i16): written by the first fused threshold
         # after the image's bytes changed, read by every later one.  Dropped with the image (_image_touched), like _range_valid.
@@ -505,7 +508,22 @@ class DeviceVolume:
         rounds = ctypes.c_int(0)
         write = self._flood_write(fill, select_value) if self._select else None
         # clear + seed + run (an in-range seed is already a candidate here: the kernel's OR is a no-op on a shared plane)
-        if write is not None:
+        piece = self._piece_to_ride(write, shared, select_value)
+        if piece is not None:
+            # ... and marching cubes' count of the piece the last surface call took, in the launch of that write: nothing in the
+            # step reads the mask bytes the write produces, and the count reads the inside plane only, which this write leaves
+            # as it is -- the count's dependent loads run under the write's stores instead of behind them
+            counted = ctypes.c_int(0)
+            L.check(lib.ivx_dev_flood_grow_select_count(p, L.I16, img_ptr, ctypes.c_double(t0), ctypes.c_double(t1), L.ptr(seeds),
+                                                        c64(len(seeds)), cand.ptr, self.reached.ptr, self.flood_scratch.ptr,
+                                                        ctypes.byref(rounds), ctypes.byref(write), int(self._look_ahead),
+                                                        ctypes.byref(piece[0]), self._mc_scratch.ptr, ctypes.byref(counted), st),
+                    "region_grow")
+            if counted.value:
+                self._ride.rode(self._mbits_version)
+            else:
+                self._ride.drop()  # (the call has reset the scratch's piece record)
+        elif write is not None:
             # ... and the one kernel _apply_reached would queue, from the same call: it is in the stream when Python gets back
             L.check(lib.ivx_dev_flood_grow_select(p, L.I16, img_ptr, ctypes.c_double(t0), ctypes.c_double(t1), L.ptr(seeds),
                                                   c64(len(seeds)), cand.ptr, self.reached.ptr, self.flood_scratch.ptr,
@@ -517,6 +535,21 @@ class DeviceVolume:
         self._gate_armed = False  # an armed gate has been opened by this flood
         self._apply_reached(fill, select_value, shared, queued=write is not None)
         return rounds.value
+
+    def _piece_to_ride(self, write, shared, select_value):
+        """(params, z0) of the piece whose count this region growing's write can carry, or None: the write is one of the two
+        from the bit planes, the inside plane is the flood's own candidate plane and stays what it is (select_value >= 127),
+        the surface call before this one counted that piece from the plane into the scratch and buffer that are still there,
+        no prefetch is using them, and the timer brackets neither of the two kernels (their spans keep their meaning)."""
+        if (write is None or write.kind not in (L.FLOOD_WRITE_MASK_FROM_PLANES, L.FLOOD_WRITE_APPLY_LEVELS) or not shared
+                or select_value is None or int(select_value) < 127 or not self._fuse or self._prefetch is not None
+                or self._mc_scratch is None or self._tris is None or self.timer.records("mc_count")
+                or self.timer.records("mask_bytes")):
+            return None
+        piece = self._ride.piece_to_ride()
+        if piece is None or piece[1] != 0 or piece[0].ny != self.dy or piece[0].nx != self.dx or piece[0].nz > self.dz:
+            return None
+        return piece
 
     def flood_visits(self):
         """(tile visits, length of the first round's list) of the last flood of this volume (L.flood_visits)"""
@@ -1011,6 +1044,7 @@ class DeviceVolume:
         L.check(L.lib().ivx_dev_mc_scratch_bytes(ctypes.byref(p), ctypes.byref(nb)))
         if self._mc_scratch is None or self._mc_scratch.nbytes < nb.value:
             self._join_prefetch()
+            self._ride.drop()
             if self._mc_scratch is not None:
                 self.sync()  # (marching_cubes returns with the emit still queued: it reads the block about to be freed)
                 self._mc_scratch.close()
@@ -1090,6 +1124,7 @@ class DeviceVolume:
         src, plane = self._mc_setup(p, z0)
         if plane is None:
             return False
+        self._ride.drop()  # the prefetch counts into the same scratch
         lib, s2 = L.lib(), self._second_stream()
         cap = self._tris.nbytes // 36
         L.check(lib.ivx_event_record(self._sync_events[0], self.stream))   # the plane is complete at this point
@@ -1150,15 +1185,25 @@ class DeviceVolume:
                 # the surface outgrew the buffer: take the ordinary path below (it re-counts and re-emits)
         src, plane = self._mc_setup(p, z0)
         n = ctypes.c_int64(0)
+        # the region growing before this call may have counted this very piece in its write's launch (mc_ride.py); a timer that
+        # brackets the count gets a count to bracket
+        if plane is not None and self._tris is not None and not self.timer.records("mc_count"):
+            rode = self._ride.take(p, z0, self._mbits_version)
+        else:
+            rode = False
+            self._ride.drop()
+        # (armed by the first call too: it ends with a triangle buffer, which is what the steady state needs)
+        self._ride.surface_counted(p, z0, plane is not None)
         if self._tris is not None:
             # steady state: the triangle buffer of the previous call gives a capacity, so count, list and emit are queued
             # back to back and the count is read afterwards (no host round trip between the two halves)
             cap = self._tris.nbytes // 36
-            with self.timer.span("mc_count"):
-                if plane is not None:
-                    L.check(lib.ivx_dev_mc_count_bits_async(ctypes.byref(p), plane, self._mc_scratch.ptr, self.stream), "mc_count")
-                else:
-                    L.check(lib.ivx_dev_mc_count_async(ctypes.byref(p), src, self._mc_scratch.ptr, self.stream), "mc_count")
+            if not rode:
+                with self.timer.span("mc_count"):
+                    if plane is not None:
+                        L.check(lib.ivx_dev_mc_count_bits_async(ctypes.byref(p), plane, self._mc_scratch.ptr, self.stream), "mc_count")
+                    else:
+                        L.check(lib.ivx_dev_mc_count_async(ctypes.byref(p), src, self._mc_scratch.ptr, self.stream), "mc_count")
             with self.timer.span("mc_emit"):
                 self._emit(p, src, plane, z0, cap, self.stream)
             # the scan published the count itself: it is here long before the emit ends, and the next call's kernels can be
@@ -1197,6 +1242,8 @@ class DeviceVolume:
         else:
             p, z0 = self._surface_params(from_binary, min_value, max_value, fill_border_holes)
         self._join_prefetch()  # same scratch
+        self._ride.drop()
+        self._ride.surface_counted(p, z0, False)
         src, plane = self._mc_setup(p, z0)
         nt, nv = ctypes.c_int64(0), ctypes.c_int64(0)
         with self.timer.span("mc_count"):

@@ -57,7 +57,12 @@ def main():
         # k_threshold16_plane_use keep the prefix)
         once = sum(stats[k][0] for k in stats if k.startswith("k_threshold16"))
         nsteps = once if sys.argv[4] == "auto" else int(sys.argv[4])
-        stage_of = lambda k: ("threshold" if k.startswith("k_threshold") else "marching_cubes" if k.startswith("k_mc_")
+        # The timed steps of the bench carry marching cubes' count in the launch of the flood's mask write (k_mc_count_write,
+        # inside region_grow's bracket); the warm-up and the bracketed extra steps of the same run keep the two kernels.  The
+        # figure is for a TIMED step: one k_mc_count_write, no k_mc_count, no k_flood_apply_levels16.
+        rides = any(k.startswith("k_mc_count_write") for k in stats)
+        stage_of = lambda k: ("threshold" if k.startswith("k_threshold") else "region_grow" if k.startswith("k_mc_count_write")
+                              else "marching_cubes" if k.startswith("k_mc_")
                               else "region_grow" if k.startswith(("k_flood_", "k_ccl_", "k_scan_")) and not k.startswith("k_flood_count")
                               else None)
         traffic = {}
@@ -71,6 +76,8 @@ def main():
             # over the steps (14 launches / 13 steps made the figure 8 % high); only kernels that run several
             # times per step (the flood's rounds) are averaged
             lps = calls / nsteps if (calls >= 2 * nsteps or calls < nsteps) else 1.0
+            if rides and (k == "k_mc_count" or k.startswith(("k_mc_count_write", "k_flood_apply_levels16"))):
+                lps = 1.0 if k.startswith("k_mc_count_write") else 0.0
             traffic[st] = traffic.get(st, 0.0) + per_launch * lps
         import os
         sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
