@@ -41,6 +41,7 @@ extern "C" {
 #define IVX_EDOM (-4)   /* NumCast failure                      -> ValueError (Rust: unwrap panic) */
 #define IVX_EHIP (-5)   /* HIP runtime error / no device        -> RuntimeError                    */
 #define IVX_ESTALE (-6) /* a registered host array was written without ivx_host_touch (only with the stale check on) */
+#define IVX_EINTERNAL (-7) /* a bounded device loop ran to its bound: a defect of the library -> RuntimeError */
 
 /* dtype codes (image dtypes accepted by the reference's ImageTypes3 enum, invesalius_rs/src/types.rs:4-70) */
 #define IVX_U8 0
@@ -1519,6 +1520,45 @@ int ivx_comm_recv(void *comm, void *buf, size_t nbytes, int peer, void *stream);
  * failed.  Collective: every rank calls it.  At world 1, where the entry points never reach RCCL, it drives RCCL directly
  * on the one-rank communicator (all-reduce, all-gather, broadcast, a grouped send + receive to itself). */
 int ivx_comm_selftest(void *comm, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * surface import: a triangle soup (what an STL file holds) to a welded indexed mesh (csrc/k_meshweld.hip)
+ *   replaces vtkSTLReader's point merge (vtkMergePoints::InsertUniquePoint per corner in file order) behind
+ *   Surface.CreateSurfaceFromFile, and ConvertPolydataToInv's transform (invesalius/data/surface.py:625-870).
+ * Weld: corners whose three float32 coordinates compare equal as numbers are one point (-0.0 == +0.0); the stored point is the
+ * first occurrence with its own bits; ids by first occurrence in corner order 3 t + c; a facet whose ids are not pairwise
+ * different is dropped afterwards (its points stay), the kept facets in order.  A coordinate that is not finite is IVX_EDOM.
+ * Limits: 3 T <= 2^31 - 1 (IVX_EDOM before any launch); the table has the power of two >= 2 * 3 T slots.
+ *   ivx_mesh_weld_slots   that slot count (host only, no device needed)
+ *   ivx_mesh_weld_bytes   the scratch ivx_dev_mesh_weld needs for T triangles
+ *   ivx_dev_mesh_weld     soup (3 T, 3) float32 -> verts_out (room for 3 T points), faces_out (room for T facets) and the
+ *                         IVX_WELD_COUNT_WORDS uint32 words of counts_out, all device memory; queue-only.  The caller downloads
+ *                         the words: IVX_WELD_OVERRUN set is IVX_EINTERNAL, IVX_WELD_NONFINITE set is IVX_EDOM.
+ *   ivx_dev_stl_unpack    the bytes of a binary STL of T records (84 + 50 T of them, at a 16-byte aligned device address) ->
+ *                         the soup; *flag (device, zeroed by the caller) gets bit 0 when a coordinate is not finite
+ *   ivx_dev_mesh_transform_points  out[i] = float32(((m[r][0] x + m[r][1] y) + m[r][2] z) + m[r][3]) in float64, rows 0..2 of
+ *                         the row-major 4 x 4 `m16` (host memory); out may be verts
+ * Host forms take host pointers (verts_out: room for 3 T points, faces_out: T facets, counts: IVX_WELD_COUNT_WORDS int64);
+ * ivx_mesh_stl_weld takes the whole file (nbytes must be 84 + 50 * its count: IVX_EDOM).
+ * ---------------------------------------------------------------------------------------------- */
+#define IVX_WELD_COUNT_WORDS 32
+#define IVX_WELD_VERTS 0      /* points of the welded mesh */
+#define IVX_WELD_KEPT 1       /* facets kept */
+#define IVX_WELD_DROPPED 2    /* degenerate facets dropped */
+#define IVX_WELD_OVERRUN 3    /* a probe walked the whole table */
+#define IVX_WELD_NONFINITE 4  /* a coordinate was not finite */
+#define IVX_WELD_MAX_PROBE 5  /* the longest walk, in slots past the home slot */
+#define IVX_WELD_LOG2_SLOTS 6 /* log2 of the table's slot count */
+#define IVX_WELD_HIST 8       /* 16 words: corners by walk length 0, 1, 2-3, 4-7, ..., >= 16384 */
+int ivx_mesh_weld_slots(int64_t n_corners, uint64_t *slots);
+int ivx_mesh_weld_bytes(int64_t ntris, size_t *bytes);
+int ivx_dev_mesh_weld(const float *soup, int64_t ntris, void *scratch, float *verts_out, int32_t *faces_out,
+                      uint32_t *counts_out, void *stream);
+int ivx_dev_stl_unpack(const uint8_t *bytes, int64_t ntris, float *soup_out, uint32_t *flag, void *stream);
+int ivx_dev_mesh_transform_points(const float *verts, int64_t nverts, const double *m16, float *out, void *stream);
+int ivx_mesh_weld(const float *soup, int64_t ntris, float *verts_out, int32_t *faces_out, int64_t *counts);
+int ivx_mesh_stl_weld(const uint8_t *file_bytes, size_t nbytes, float *verts_out, int32_t *faces_out, int64_t *counts);
+int ivx_mesh_transform_points(const float *verts, int64_t nverts, const double *m16, float *out);
 
 #ifdef __cplusplus
 }

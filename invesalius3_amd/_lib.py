@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("IVX_LIB_PATH") or os.path.join(_HERE, "libivx.so")  # IVX_LIB_PATH: A/B builds of the same ABI
 
 IVX_OK, IVX_EINVAL, IVX_ERANGE, IVX_ENOMEM, IVX_EDOM, IVX_EHIP, IVX_ESTALE = 0, -1, -2, -3, -4, -5, -6
+IVX_EINTERNAL = -7
 U8, I16, F64, U16, F32, I32, I64, I8 = 0, 1, 2, 3, 4, 5, 6, 7
 DT = {np.dtype(np.uint8): U8, np.dtype(np.int16): I16, np.dtype(np.float64): F64, np.dtype(np.uint16): U16, np.dtype(np.float32): F32, np.dtype(np.int32): I32,
       np.dtype(np.int64): I64}
@@ -62,6 +63,9 @@ class VolrenParams(ctypes.Structure):
 
 
 ROI_ELLIPSE, ROI_POLYGON, ROI_MAX_POINTS, ROI_RECORD_BYTES = 0, 1, 2048, 40
+# the words of the weld's counts (IVX_WELD_* of include/ivx.h)
+WELD_COUNT_WORDS, WELD_VERTS, WELD_KEPT, WELD_DROPPED, WELD_OVERRUN, WELD_NONFINITE, WELD_MAX_PROBE, WELD_LOG2_SLOTS, WELD_HIST = 32, 0, 1, 2, 3, 4, 5, 6, 8
+WELD_MAX_CORNERS = 2 ** 31 - 1
 
 
 class Roi(ctypes.Structure):
@@ -146,7 +150,14 @@ def _declare(lib):
                        ("ivx_m3e_cut", [c_vp, i64p, i64p, c_vp, ctypes.c_double, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp,
                                         ctypes.c_int, i64p]),
                        ("ivx_m3e_brush_stroke", [c_vp, c_vp, i64p, i64p, c_vp, c_vp, c_i64, ctypes.c_double, ctypes.c_int, i64p]),
-                       ("ivx_m3e_apply", [c_vp, c_vp, i64p, i64p, i64p]), ("ivx_m3e_flag_planes", [c_vp, i64p, i64p])):
+                       ("ivx_m3e_apply", [c_vp, c_vp, i64p, i64p, i64p]), ("ivx_m3e_flag_planes", [c_vp, i64p, i64p]),
+                       # surface import: table size, scratch size, weld, STL unpack, point transform; host forms
+                       ("ivx_mesh_weld_slots", [c_i64, u64p]), ("ivx_mesh_weld_bytes", [c_i64, ctypes.POINTER(sz)]),
+                       ("ivx_dev_mesh_weld", [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+                       ("ivx_dev_stl_unpack", [c_vp, c_i64, c_vp, c_vp, c_vp]),
+                       ("ivx_dev_mesh_transform_points", [c_vp, c_i64, c_vp, c_vp, c_vp]),
+                       ("ivx_mesh_weld", [c_vp, c_i64, c_vp, c_vp, c_vp]), ("ivx_mesh_stl_weld", [c_vp, sz, c_vp, c_vp, c_vp]),
+                       ("ivx_mesh_transform_points", [c_vp, c_i64, c_vp, c_vp])):
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = args, ctypes.c_int
 

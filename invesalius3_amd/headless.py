@@ -13,6 +13,8 @@
     python -m invesalius3_amd.headless CASE.inv3 --threshold 226 3071 --largest --view iso --surface-png bone.png --surface-interpolation phong
     python -m invesalius3_amd.headless CASE.inv3 --threshold 226 3071 --show-slice AXIAL 40 --window 2000 300 --colour-table Rainbow --png slice.png
     python -m invesalius3_amd.headless CASE.inv3 --density-ellipse AXIAL 40 120 98 40 140 98 40 120 110 40 --remeasure --measures-json m.json --save CASE_out.inv3
+    python -m invesalius3_amd.headless --import-surface part.stl --largest --stl out.stl
+    python -m invesalius3_amd.headless CASE.inv3 --import-surface scanner.ply --import-world --split parts/
 
 What the reference does through its GUI for the same result: Slice.SetMaskThreshold / do_threshold_to_all_slices
 (invesalius/data/slice_.py:1240-1247, 1739-1769), the Image Filters dialog (slice_.py:2330-2539), the deep-learning segmentation (segmentation/deep_learning/segment.py), the 3-D view's volume rendering (data/volume.py:575-707), the region-growing tool (styles.py:3151-3216),
@@ -161,116 +163,7 @@ def run(args) -> dict:
         with vol.timer.span("surface"):
             nv, nt = vol.marching_cubes_indexed(from_binary=True, fill_border_holes=True)
         verts_buf, faces_buf = vol._verts, vol._faces
-        out["surface"] = {"vertices": nv, "triangles": nt}
-        keep_v = keep_f = None
-        if args.largest and nt:
-            from .device import DeviceBuffer
-            keep_v, keep_f = DeviceBuffer(nv * 12 + 16), DeviceBuffer(nt * 12 + 16)
-            n1, n2, nr = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
-            with vol.timer.span("keep_largest"):
-                L.check(lib.ivx_dev_mesh_keep_largest(verts_buf.ptr, c64(nv), faces_buf.ptr, c64(nt), keep_v.ptr, c64(nv),
-                                                      keep_f.ptr, c64(nt), ctypes.byref(n1), ctypes.byref(n2),
-                                                      ctypes.byref(nr), vol.stream), "keep_largest")
-            verts_buf, faces_buf, nv, nt = keep_v, keep_f, n1.value, n2.value
-            out["largest"] = {"regions": nr.value, "vertices": nv, "triangles": nt}
-        seeded = None
-        if args.surface_seed and nt:
-            # Surface.OnSeedSurface -> pu.JoinSeedsParts (surface.py:363-411): the GUI's point pick is the nearest point here
-            from . import polydata_utils as pu
-            whole = pu.DeviceMesh(verts_buf, nv, faces_buf, nt, vol.stream)
-            picks = [tuple(args.surface_seed[i:i + 3]) for i in range(0, len(args.surface_seed), 3)]
-            with vol.timer.span("surface_seed"):
-                ids = [whole.nearest_point(xyz) for xyz in picks]
-                seeded = whole.select_seeded(ids)
-            out["surface_seed"] = {"points": [list(xyz) for xyz in picks], "point_ids": ids, "vertices": seeded.nverts,
-                                   "triangles": seeded.ntris}
-            verts_buf, faces_buf, nv, nt = seeded.verts, seeded.faces, seeded.nverts, seeded.ntris
-        shell = None
-        if args.remove_nonvisible and nt:
-            # Surface.OnRemoveNonVisibleFaces -> pu.RemoveNonVisibleFaces (surface.py:413-435) on the resident mesh
-            from . import polydata_utils as pu
-            with vol.timer.span("remove_nonvisible"):
-                shell = pu.RemoveNonVisibleFaces(pu.DeviceMesh(verts_buf, nv, faces_buf, nt, vol.stream))
-            out["remove_nonvisible"] = {"vertices": shell.nverts, "triangles": shell.ntris, "removed_triangles": nt - shell.ntris}
-            verts_buf, faces_buf, nv, nt = shell.verts, shell.faces, shell.nverts, shell.ntris
-        if args.smooth and nt:
-            from .device import DeviceBuffer
-            nrm = DeviceBuffer(nt * 24 + 16)
-            with vol.timer.span("smooth"):
-                L.check(lib.ivx_dev_mesh_face_normals(verts_buf.ptr, L.F32, faces_buf.ptr, c64(nt), nrm.ptr, vol.stream))
-                L.check(lib.ivx_dev_context_aware_smoothing(verts_buf.ptr, L.F32, c64(nv), faces_buf.ptr, c64(nt), nrm.ptr,
-                                                            ctypes.c_double(args.angle), ctypes.c_double(args.max_distance),
-                                                            ctypes.c_double(args.min_weight), ctypes.c_int(args.steps), None,
-                                                            None, vol.stream), "ca_smoothing")
-            nrm.close()
-            out["smooth"] = {"angle": args.angle, "max_distance": args.max_distance, "min_weight": args.min_weight,
-                             "steps": args.steps}
-        from .device import DeviceBuffer
-        mass = DeviceBuffer(64)
-        with vol.timer.span("mass"):
-            L.check(lib.ivx_dev_mesh_mass_properties(verts_buf.ptr, faces_buf.ptr, c64(nt), mass.ptr, vol.stream))
-        vol.sync()
-        m = mass.download((8,), np.float64)
-        out["volume"], out["area"] = float(m[0]), float(m[1])
-        mass.close()
-        verts = faces = None
-        if args.stl:
-            verts = verts_buf.download((nv, 3), np.float32)
-            faces = faces_buf.download((nt, 3), np.int32)
-            sp.write_stl_binary(args.stl, verts[faces])
-            out["stl"] = args.stl
-        if getattr(args, "surface_png", None):
-            # the 3-D view's picture of the final surface (Surface._show_surface, surface.py:1061-1116, under the viewer's
-            # camera of the IMAGE: the picture overlays --render), with the point normals the reference's actor carries
-            from . import surface_view as SV
-            from . import volume as V
-            if verts is None:
-                verts = verts_buf.download((nv, 3), np.float32)
-                faces = faces_buf.download((nt, 3), np.int32)
-            pv, pf, pn, _ = sp.point_normals(verts, faces)
-            w, h = args.size
-            actor = SV.SurfaceActor(pv, pf, pn, colour=args.surface_colour, transparency=args.surface_transparency)
-            rgba8 = SV.render_surfaces([actor], args.view, (w, h), shape=vol.shape, spacing=vol.spacing,
-                                       interpolation=args.surface_interpolation, rgba8=True)
-            V.write_png(args.surface_png, rgba8)
-            out["surface_view"] = {"png": args.surface_png, "view": args.view, "size": [w, h], "colour": list(args.surface_colour),
-                                   "transparency": args.surface_transparency, "interpolation": args.surface_interpolation,
-                                   "vertices": int(len(pv)), "triangles": int(len(pf))}
-        if args.geodesic:
-            # the measurement panel's geodesic measure (GeodesicMeasure._draw_line, measures.py:1202-1256) on the final surface
-            from . import polydata_utils as pu
-            picks = [tuple(args.geodesic[i:i + 3]) for i in range(0, len(args.geodesic), 3)]
-            final = pu.DeviceMesh(verts_buf, nv, faces_buf, nt, vol.stream)
-            try:
-                with vol.timer.span("geodesic"):
-                    geo = final.geodesic(points=picks)
-            finally:
-                final.close()  # (frees the graph; the buffers are not its own)
-            out["geodesic"] = {"points": [list(xyz) for xyz in picks], "point_ids": [int(i) for i in geo.point_ids],
-                               "segment_lengths": geo.segment_lengths, "length_mm": geo.length, "path_points": len(geo.points)}
-            if args.geodesic_npy:
-                np.save(args.geodesic_npy, geo.points)
-                out["geodesic"]["npy"] = args.geodesic_npy
-        if args.split is not None:
-            # Surface.OnSplitSurface -> pu.SplitDisconectedParts (surface.py:319-361) on the final surface: one STL per part, in
-            # region order, and every part's measures (CreateSurfaceFromPolydata takes them per part, surface.py:953-960)
-            from . import polydata_utils as pu
-            os.makedirs(args.split, exist_ok=True)
-            with vol.timer.span("split"):
-                parts = pu.DeviceMesh(verts_buf, nv, faces_buf, nt, vol.stream).split()
-                measures = parts.mass_properties()
-            table = parts.table
-            rows = []
-            for r in range(parts.n):
-                if int(table[r, 1]) < args.split_min_triangles:
-                    continue
-                pv, pf = parts.download(r)
-                name = os.path.join(args.split, "part_%05d.stl" % r)
-                sp.write_stl_binary(name, pv[pf])
-                rows.append({"part": r, "triangles": int(table[r, 1]), "vertices": int(table[r, 3]), "volume": float(measures[r, 0]),
-                             "area": float(measures[r, 1]), "stl": name})
-            parts.close()
-            out["split"] = {"regions": parts.n, "min_triangles": args.split_min_triangles, "parts": rows}
+        _surface_tail(args, lib, out, verts_buf, faces_buf, nv, nt, vol.stream, vol.timer, vol.sync, (vol.shape, vol.spacing))
         if args.save:
             rec = prj.new_mask(proj, args.mask_name, (lo, hi))
             rec.matrix[1:, 1:, 1:] = mask
@@ -288,18 +181,171 @@ def run(args) -> dict:
             prj.save_inv3(args.save, proj)
             out["saved"] = args.save
         out["gpu_ms"] = {k: round(float(sum(v)), 4) for k, v in vol.timer.collect().items()}
-        for b in (keep_v, keep_f):
-            if b is not None:
-                b.close()
-        if shell is not None:
-            shell.close()
-        if seeded is not None:
-            seeded.close()
     finally:
         vol.close()
         for b in bound:
             b.release()
         proj.close()
+        out["wall_s"] = round(time.perf_counter() - t_all, 3)
+    return out
+
+
+def _surface_tail(args, lib, out, verts_buf, faces_buf, nv, nt, stream, timer, sync, geometry):
+    """everything the driver does with a surface once it is resident (two device buffers, nv points, nt triangles): --largest,
+    --surface-seed, --remove-nonvisible, --smooth, the measures, --stl, --surface-png, --geodesic, --split.  The surface comes
+    from marching cubes on the mask or from --import-surface; `geometry`: the image's (shape, spacing) for the camera of
+    --surface-png, or None without an image"""
+    out["surface"] = {"vertices": nv, "triangles": nt}
+    keep_v = keep_f = None
+    if args.largest and nt:
+        from .device import DeviceBuffer
+        keep_v, keep_f = DeviceBuffer(nv * 12 + 16), DeviceBuffer(nt * 12 + 16)
+        n1, n2, nr = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        with timer.span("keep_largest"):
+            L.check(lib.ivx_dev_mesh_keep_largest(verts_buf.ptr, c64(nv), faces_buf.ptr, c64(nt), keep_v.ptr, c64(nv),
+                                                  keep_f.ptr, c64(nt), ctypes.byref(n1), ctypes.byref(n2),
+                                                  ctypes.byref(nr), stream), "keep_largest")
+        verts_buf, faces_buf, nv, nt = keep_v, keep_f, n1.value, n2.value
+        out["largest"] = {"regions": nr.value, "vertices": nv, "triangles": nt}
+    seeded = None
+    if args.surface_seed and nt:
+        # Surface.OnSeedSurface -> pu.JoinSeedsParts (surface.py:363-411): the GUI's point pick is the nearest point here
+        from . import polydata_utils as pu
+        whole = pu.DeviceMesh(verts_buf, nv, faces_buf, nt, stream)
+        picks = [tuple(args.surface_seed[i:i + 3]) for i in range(0, len(args.surface_seed), 3)]
+        with timer.span("surface_seed"):
+            ids = [whole.nearest_point(xyz) for xyz in picks]
+            seeded = whole.select_seeded(ids)
+        out["surface_seed"] = {"points": [list(xyz) for xyz in picks], "point_ids": ids, "vertices": seeded.nverts,
+                               "triangles": seeded.ntris}
+        verts_buf, faces_buf, nv, nt = seeded.verts, seeded.faces, seeded.nverts, seeded.ntris
+    shell = None
+    if args.remove_nonvisible and nt:
+        # Surface.OnRemoveNonVisibleFaces -> pu.RemoveNonVisibleFaces (surface.py:413-435) on the resident mesh
+        from . import polydata_utils as pu
+        with timer.span("remove_nonvisible"):
+            shell = pu.RemoveNonVisibleFaces(pu.DeviceMesh(verts_buf, nv, faces_buf, nt, stream))
+        out["remove_nonvisible"] = {"vertices": shell.nverts, "triangles": shell.ntris, "removed_triangles": nt - shell.ntris}
+        verts_buf, faces_buf, nv, nt = shell.verts, shell.faces, shell.nverts, shell.ntris
+    if args.smooth and nt:
+        from .device import DeviceBuffer
+        nrm = DeviceBuffer(nt * 24 + 16)
+        with timer.span("smooth"):
+            L.check(lib.ivx_dev_mesh_face_normals(verts_buf.ptr, L.F32, faces_buf.ptr, c64(nt), nrm.ptr, stream))
+            L.check(lib.ivx_dev_context_aware_smoothing(verts_buf.ptr, L.F32, c64(nv), faces_buf.ptr, c64(nt), nrm.ptr,
+                                                        ctypes.c_double(args.angle), ctypes.c_double(args.max_distance),
+                                                        ctypes.c_double(args.min_weight), ctypes.c_int(args.steps), None,
+                                                        None, stream), "ca_smoothing")
+        nrm.close()
+        out["smooth"] = {"angle": args.angle, "max_distance": args.max_distance, "min_weight": args.min_weight,
+                         "steps": args.steps}
+    from .device import DeviceBuffer
+    mass = DeviceBuffer(64)
+    with timer.span("mass"):
+        L.check(lib.ivx_dev_mesh_mass_properties(verts_buf.ptr, faces_buf.ptr, c64(nt), mass.ptr, stream))
+    sync()
+    m = mass.download((8,), np.float64)
+    out["volume"], out["area"] = float(m[0]), float(m[1])
+    mass.close()
+    verts = faces = None
+    if args.stl:
+        verts = verts_buf.download((nv, 3), np.float32)
+        faces = faces_buf.download((nt, 3), np.int32)
+        sp.write_stl_binary(args.stl, verts[faces])
+        out["stl"] = args.stl
+    if getattr(args, "surface_png", None):
+        # the 3-D view's picture of the final surface (Surface._show_surface, surface.py:1061-1116, under the viewer's
+        # camera of the IMAGE: the picture overlays --render), with the point normals the reference's actor carries
+        from . import surface_view as SV
+        from . import volume as V
+        if verts is None:
+            verts = verts_buf.download((nv, 3), np.float32)
+            faces = faces_buf.download((nt, 3), np.int32)
+        pv, pf, pn, _ = sp.point_normals(verts, faces)
+        w, h = args.size
+        actor = SV.SurfaceActor(pv, pf, pn, colour=args.surface_colour, transparency=args.surface_transparency)
+        rgba8 = SV.render_surfaces([actor], args.view, (w, h), shape=geometry[0], spacing=geometry[1],
+                                   interpolation=args.surface_interpolation, rgba8=True)
+        V.write_png(args.surface_png, rgba8)
+        out["surface_view"] = {"png": args.surface_png, "view": args.view, "size": [w, h], "colour": list(args.surface_colour),
+                               "transparency": args.surface_transparency, "interpolation": args.surface_interpolation,
+                               "vertices": int(len(pv)), "triangles": int(len(pf))}
+    if args.geodesic:
+        # the measurement panel's geodesic measure (GeodesicMeasure._draw_line, measures.py:1202-1256) on the final surface
+        from . import polydata_utils as pu
+        picks = [tuple(args.geodesic[i:i + 3]) for i in range(0, len(args.geodesic), 3)]
+        final = pu.DeviceMesh(verts_buf, nv, faces_buf, nt, stream)
+        try:
+            with timer.span("geodesic"):
+                geo = final.geodesic(points=picks)
+        finally:
+            final.close()  # (frees the graph; the buffers are not its own)
+        out["geodesic"] = {"points": [list(xyz) for xyz in picks], "point_ids": [int(i) for i in geo.point_ids],
+                           "segment_lengths": geo.segment_lengths, "length_mm": geo.length, "path_points": len(geo.points)}
+        if args.geodesic_npy:
+            np.save(args.geodesic_npy, geo.points)
+            out["geodesic"]["npy"] = args.geodesic_npy
+    if args.split is not None:
+        # Surface.OnSplitSurface -> pu.SplitDisconectedParts (surface.py:319-361) on the final surface: one STL per part, in
+        # region order, and every part's measures (CreateSurfaceFromPolydata takes them per part, surface.py:953-960)
+        from . import polydata_utils as pu
+        os.makedirs(args.split, exist_ok=True)
+        with timer.span("split"):
+            parts = pu.DeviceMesh(verts_buf, nv, faces_buf, nt, stream).split()
+            measures = parts.mass_properties()
+        table = parts.table
+        rows = []
+        for r in range(parts.n):
+            if int(table[r, 1]) < args.split_min_triangles:
+                continue
+            pv, pf = parts.download(r)
+            name = os.path.join(args.split, "part_%05d.stl" % r)
+            sp.write_stl_binary(name, pv[pf])
+            rows.append({"part": r, "triangles": int(table[r, 1]), "vertices": int(table[r, 3]), "volume": float(measures[r, 0]),
+                         "area": float(measures[r, 1]), "stl": name})
+        parts.close()
+        out["split"] = {"regions": parts.n, "min_triangles": args.split_min_triangles, "parts": rows}
+    for b in (keep_v, keep_f):
+        if b is not None:
+            b.close()
+    if shell is not None:
+        shell.close()
+    if seeded is not None:
+        seeded.close()
+
+
+def run_import(args) -> dict:
+    """--import-surface FILE: Surface.OnImportSurfaceFile (surface.py:619-845) -- the file's mesh, welded on the GPU where the
+    format holds a soup, takes the place of the marching-cubes surface; --import-world converts it from world to InVesalius
+    coordinates with the project's affine, spacing and shape first (ConvertPolydataToInv).  No image is opened otherwise."""
+    from . import surface as S
+    from .device import Timer
+
+    t_all = time.perf_counter()
+    out, convert, geometry = {}, None, None
+    if args.project is not None:
+        proj = prj.open_inv3(args.project)
+        try:
+            out.update({"project": proj.name, "shape": list(proj.matrix_shape), "spacing": list(proj.spacing)})
+            geometry = (tuple(proj.matrix_shape), tuple(proj.spacing))
+            if args.import_world:
+                affine = np.eye(4) if proj.affine is None else np.array(proj.affine, np.float64).reshape(4, 4)
+                convert = (affine, proj.spacing, proj.matrix_shape)
+        finally:
+            proj.close()
+    lib = L.lib()
+    imp = S.CreateSurfaceFromFile(args.import_surface, convert_to_inv=convert)
+    mesh, timer = imp.mesh, Timer(None)
+    try:
+        c = imp.counts
+        out["import"] = {"file": args.import_surface, "name": imp.name, "format": imp.format, "facets_read": c["facets_read"],
+                         "vertices": mesh.nverts, "triangles": mesh.ntris, "dropped": c["dropped"], "volume": imp.volume,
+                         "area": imp.area, "world": bool(args.import_world)}
+        _surface_tail(args, lib, out, mesh.verts, mesh.faces, mesh.nverts, mesh.ntris, mesh.stream, timer, mesh.sync, geometry)
+        mesh.sync()
+        out["gpu_ms"] = {k: round(float(sum(v)), 4) for k, v in timer.collect().items()}
+    finally:
+        imp.close()
         out["wall_s"] = round(time.perf_counter() - t_all, 3)
     return out
 
@@ -500,7 +546,12 @@ def _mask3d_edit(args, vol, out):
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m invesalius3_amd.headless", description=__doc__.split("\n")[0])
-    ap.add_argument("project", help=".inv3 file")
+    ap.add_argument("project", nargs="?", default=None, help=".inv3 file (may be left out with --import-surface)")
+    ap.add_argument("--import-surface", metavar="FILE", default=None,
+                    help="import a surface file (.stl, .ply, .vtp) instead of making one from a mask: --largest, --remove-nonvisible, "
+                         "--surface-seed, --split, --smooth, --geodesic and --stl act on it; not with --threshold or --segment")
+    ap.add_argument("--import-world", action="store_true",
+                    help="convert the imported surface from world to InVesalius coordinates with the project's affine, spacing and shape")
     g = ap.add_mutually_exclusive_group()
     g.add_argument("--threshold", nargs=2, type=int, metavar=("LO", "HI"), help="threshold the image into a new mask")
     g.add_argument("--mask", type=int, default=0, help="use the project's mask with this index (default 0)")
@@ -597,6 +648,30 @@ def main(argv=None) -> int:
     ap.add_argument("--mask-name", default="GPU mask")
     args = ap.parse_args(argv)
     args.argv = list(sys.argv[1:] if argv is None else argv)
+    if args.import_surface is not None:
+        if args.threshold is not None or args.segment is not None or "--mask" in args.argv or args.seed:
+            ap.error("--import-surface takes the place of --threshold / --segment / --mask / --seed: name one source of the surface")
+        image_flags = ("filter", "render", "mask_preview", "show_slice", "save", "crop", "cut_polygon", "brush3d", "flip", "swap_axes",
+                       "gantry_tilt", "density_ellipse", "density_polygon", "remeasure")
+        given = [f for f in image_flags if getattr(args, f, None)]
+        if given:
+            ap.error("--import-surface works on the surface alone: --%s needs the image or the mask" % given[0].replace("_", "-"))
+        if args.geodesic_npy is not None and args.geodesic is None:
+            ap.error("--geodesic-npy needs --geodesic")
+        if args.import_world and args.project is None:
+            ap.error("--import-world needs the project whose affine, spacing and shape it uses")
+        if args.surface_png is not None and args.project is None:
+            ap.error("--surface-png of an imported surface needs the project whose image sets the camera")
+        if args.geodesic is not None and (len(args.geodesic) < 6 or len(args.geodesic) % 3):
+            ap.error("--geodesic takes two or more triples of x y z")
+        if args.surface_seed and len(args.surface_seed) % 3:
+            ap.error("--surface-seed takes triples of x y z")
+        print(json.dumps(run_import(args)))
+        return 0
+    if args.project is None:
+        ap.error("the following arguments are required: project")
+    if args.import_world:
+        ap.error("--import-world needs --import-surface FILE")
     if args.segment is not None:
         if args.weights is None:
             ap.error("--segment needs --weights FILE")

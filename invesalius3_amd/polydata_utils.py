@@ -133,6 +133,69 @@ class DeviceMesh:
             m.faces.upload(f)
         return m
 
+    # ---- surface import ----
+    @classmethod
+    def _weld(cls, soup_buf, ntris: int, stream=None):
+        """the weld of the (3 T, 3) float32 soup in `soup_buf` (csrc/k_meshweld.hip): the mesh, its `weld_counts` set; waits
+        for the counts, so the caller may free the soup afterwards.  The buffers keep their worst-case room (3 T points)."""
+        from . import surface as S
+        from .device import DeviceBuffer
+        lib = L.lib()
+        nb = ctypes.c_size_t(0)
+        L.check(lib.ivx_mesh_weld_bytes(ctypes.c_int64(ntris), ctypes.byref(nb)), "mesh_weld_bytes")
+        bufs = [DeviceBuffer(nb.value + 16), DeviceBuffer(L.WELD_COUNT_WORDS * 4), DeviceBuffer(ntris * 36 + 16), DeviceBuffer(ntris * 12 + 16)]
+        scratch, cnt, ov, of = bufs
+        try:
+            L.check(lib.ivx_dev_mesh_weld(soup_buf.ptr, ctypes.c_int64(ntris), scratch.ptr, ov.ptr, of.ptr, cnt.ptr, stream), "mesh_weld")
+            L.check(lib.ivx_stream_synchronize(stream) if stream else lib.ivx_device_synchronize())
+            counts = S.counts_dict(cnt.download((L.WELD_COUNT_WORDS,), np.uint32), ntris)
+        except Exception:
+            for b in bufs:
+                b.close()
+            raise
+        scratch.close()
+        cnt.close()
+        m = cls(ov, counts["vertices"], of, counts["facets"], stream, owns=True)
+        m.weld_counts = counts
+        return m
+
+    @classmethod
+    def from_soup(cls, tris, stream=None):
+        """The welded mesh of a triangle soup ((T, 3, 3) float32, what an STL file holds): coincident corners share one id, by
+        first occurrence; degenerate facets are dropped; a coordinate that is not finite is a ValueError.  `weld_counts`
+        holds the counts (`surface.counts_dict`)."""
+        from . import surface as S
+        from .device import DeviceBuffer
+        t = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 3, 3)
+        S.check_facet_count(len(t))  # (raises before anything is launched)
+        soup = DeviceBuffer(t.nbytes + 16)
+        try:
+            if len(t):
+                soup.upload(t)
+            return cls._weld(soup, len(t), stream)
+        finally:
+            soup.close()
+
+    @classmethod
+    def from_stl_bytes(cls, data, stream=None):
+        """`from_soup` of a binary STL file's bytes: the file goes to the device as it is and is unpacked there"""
+        from . import surface as S
+        from .device import DeviceBuffer
+        if S.stl_kind(data) != "binary":
+            raise ValueError("from_stl_bytes takes a binary STL (surface.read_stl parses the ASCII form)")
+        nt = S.check_facet_count((len(data) - S.STL_HEADER) // S.STL_RECORD)
+        raw = np.frombuffer(data, np.uint8)
+        lib = L.lib()
+        file_buf, soup, flag = DeviceBuffer(len(raw) + 16), DeviceBuffer(nt * 36 + 16), DeviceBuffer(16)
+        try:
+            file_buf.upload(raw)
+            flag.zero(stream)
+            L.check(lib.ivx_dev_stl_unpack(file_buf.ptr, ctypes.c_int64(nt), soup.ptr, flag.ptr, stream), "stl_unpack")
+            return cls._weld(soup, nt, stream)  # (the weld raises the non-finite flag for the same coordinates)
+        finally:
+            for b in (file_buf, soup, flag):
+                b.close()
+
     def sync(self):
         L.check(L.lib().ivx_stream_synchronize(self.stream) if self.stream else L.lib().ivx_device_synchronize())
 
