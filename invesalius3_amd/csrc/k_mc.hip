@@ -35,6 +35,7 @@
 // Output order == the oracle's (iso-major, then k, j, i raster order of cells), so parity is an array compare.
 // Vertex arithmetic is done in double and rounded once to float32, exactly like the oracle.
 #include <algorithm>
+#include <type_traits>
 
 #include "levels_write.h"
 #include "mc_common.h"
@@ -631,14 +632,18 @@ __global__ __launch_bounds__(256) void k_mc_list(const uint64_t *__restrict__ bi
     }
 }
 
-// 4b. emit: a flat, regular kernel -- one lane per triangle of the list, 256 consecutive triangles per workgroup.
-//     Nothing but the 9-KB staging buffer in LDS, so eight workgroups share a CU and hide each other's gather latency.
+// 4b. emit: a flat, regular kernel -- one lane per triangle of the list, 256 consecutive triangles (a chunk) at a time.
+//     Workgroup b of G takes the chunks b, b + G, b + 2G, ... and stages the tables once; G is one workgroup per chunk for
+//     all but very large surfaces, which get as many workgroups as the chip holds at once (emit_grid says where the line is
+//     and why).  Nothing passes between workgroups: a plain grid-stride loop.  The kernel is bound
+//     by the vector instructions it issues (profiles/mc_emit_chunks_ab.md), so what counts here is their number per triangle.
 // The nine floats of ONE triangle: cell (k, j, i) of the padded grid, case `idx`, triangle `rel` of the case.  s_tri = the
-// triangle table (rows of 15), s_e0 / s_e1 / s_ec = the per-edge constants (see k_mc_emit).
-template <typename T, bool LEVELS>
+// triangle table (rows of 15), s_e0 / s_e1 / s_ec = the per-edge constants, s_tt = McLevels::tt (see k_mc_emit).
+// WIDE (LEVELS only): the `sel` plane has 2^31 or more 32-bit halves, their offsets take 64-bit arithmetic.
+template <typename T, bool LEVELS, bool WIDE>
 __device__ __forceinline__ void mc_triangle(const T *__restrict__ a, const Geom &g, const McLevels &lv, double iso,
-                                            const uint8_t *s_tri, const int *s_e0, const int *s_e1, const int *s_ec, int32_t k,
-                                            int32_t j, int32_t i, int idx, int rel, float *o) {
+                                            const uint8_t *s_tri, const int *s_e0, const int *s_e1, const int *s_ec,
+                                            const double *s_tt, int32_t k, int32_t j, int32_t i, int idx, int rel, float *o) {
     const int32_t ka = k - (int32_t)g.pb, ja = ((int32_t)g.NY - 1 - j) - (int32_t)g.pxy; // source row of corner (dy=0, dz=0)
     const int32_t ia = i - (int32_t)g.pxy;
     const bool fast = ka >= 0 && ka + 1 < (int32_t)g.nz && ja - 1 >= 0 && ja < (int32_t)g.ny && ia >= 0 &&
@@ -655,11 +660,20 @@ __device__ __forceinline__ void mc_triangle(const T *__restrict__ a, const Geom 
             const int ax = c & 3, bx = (c >> 2) & 1, by = (c >> 3) & 1, bz = (c >> 4) & 1;
             const int lo = bx + 2 * by + 4 * bz; // corner numbers of the edge's ends in the case index
             const bool in0 = (idx >> lo) & 1, in1 = (idx >> (lo + (1 << ax))) & 1; // exactly one of them is inside
-            // the inside end is a source voxel (padding is never inside a from_binary piece): its bit of `sel`
+            // the inside end is a source voxel (padding is never inside a from_binary piece): its bit of `sel`, read with the
+            // 32-bit half of the plane word that holds it
             const int32_t kk = k + bz + (in1 && ax == 2), jj = j + by + (in1 && ax == 1), ii = i + bx + (in1 && ax == 0);
-            const int64_t sk = kk - (int32_t)g.pb, sj = ((int32_t)g.NY - 1 - jj) - (int32_t)g.pxy, si = ii - (int32_t)g.pxy;
-            const uint64_t wsel = lv.sel[(sk * g.ny + sj) * g.ws + (si >> 6)];
-            ttl[v] = lv.tt[(in0 ? 2 : 0) + (int)((wsel >> (si & 63)) & 1ull)];
+            const int32_t sk = kk - (int32_t)g.pb, sj = ((int32_t)g.NY - 1 - jj) - (int32_t)g.pxy, si = ii - (int32_t)g.pxy;
+            const int64_t half = WIDE ? (((int64_t)sk * g.ny + sj) * g.ws + (si >> 6)) * 2 + ((si >> 5) & 1)
+                                      : (int64_t)(((sk * (int32_t)g.ny + sj) * (int32_t)g.ws + (si >> 6)) * 2 + ((si >> 5) & 1));
+#if IVX_EMIT_CONST_SEL
+            const uint32_t wsel = 0u; // (leave-out build: no gather; the vertices next to selected voxels are wrong)
+#else
+            const uint32_t wsel = ((const uint32_t *)lv.sel)[half];
+#endif
+            // (from LDS: lv.tt[variable] is a load from the argument segment, one more round trip behind the gather's, and
+            // selects among the four values are fourteen vector instructions per vertex)
+            ttl[v] = s_tt[(in0 ? 2 : 0) + (int)((wsel >> (si & 31)) & 1u)];
             ec[v] = c;
         }
     } else if (fast) { // interior cell: one base pointer, six byte/short gathers at table offsets, issued back to back
@@ -697,30 +711,49 @@ __device__ __forceinline__ void mc_triangle(const T *__restrict__ a, const Geom 
     }
 }
 
-template <typename T, bool LEVELS>
+// Lane tid's descriptor of chunk c.  The load is unconditional -- a lane behind the list's end reads the last entry again, and
+// the caller asks `c * 256 + tid < ntris` where it uses the value --: the compiler counts only loads and stores that every path
+// issues when it decides how many may still be in flight at a wait, so a load under a branch would make the wait for it a wait
+// for the stores issued behind it as well.
+__device__ __forceinline__ uint64_t emit_desc(const uint64_t *__restrict__ list, uint64_t ntris, uint64_t c, int tid) {
+    const uint64_t t = c * 256 + tid;
+    return list[t < ntris ? t : ntris - 1]; // (a non-temporal load here measured the same)
+}
+
+// ALIGNED: `tris` is 16-byte aligned, whole chunks leave as 16-byte stores (run_emit decides both template flags).
+template <typename T, bool LEVELS, bool ALIGNED, bool WIDE>
 __global__ __launch_bounds__(256) void k_mc_emit(const T *__restrict__ a, Geom g, double iso0, double iso1,
                                                  const uint64_t *__restrict__ split_dev,
                                                  const uint64_t *__restrict__ total_dev,
                                                  const uint64_t *__restrict__ list, uint64_t cap,
                                                  float *__restrict__ tris, McLevels lv) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_tri[256 * 15];
     __shared__ __attribute__((aligned(16))) float s_out[256 * 9];
+    __shared__ int s_e0[12], s_e1[12], s_ec[12];
+    __shared__ double s_tt[4];
     const int tid = threadIdx.x;
-    // The grid covers the output CAPACITY; how many triangles there really are (and where iso 1's begin) is read from
+    // The grid covers at most the output CAPACITY; how many triangles there really are (and where iso 1's begin) is read from
     // the scan's result on the device, so the host can queue this kernel before it knows the count.
     const uint64_t total = *total_dev, split = *split_dev;
     const uint64_t ntris = total < cap ? total : cap;
-    const uint64_t T0 = (uint64_t)blockIdx.x * 256;
-    if (T0 >= ntris) return;
-    // the triangle table (3 840 bytes, rows of 15) as 960 dwords, layout unchanged
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-        if (q * 256 + tid < 960) ((uint32_t *)s_tri)[q * 256 + tid] = ((const uint32_t *)&MC_TRI[0][0])[q * 256 + tid];
-    const uint64_t T_ = T0 + tid;
-    const double iso = T_ < split ? iso0 : iso1;
-    // per-edge constants, once per workgroup: voxel offsets of the edge's two end points relative to the cell's corner
-    // (0,0,0) (dy runs against the source rows: the Y flip) and the end point / axis codes.  |offset| <= ny*nx + nx + 1.
-    __shared__ int s_e0[12], s_e1[12], s_ec[12];
+    const uint64_t nchunks = (ntris + 255) >> 8, G = gridDim.x;
+    uint64_t c = blockIdx.x;
+    if (c >= nchunks) return;
+    uint64_t d = emit_desc(list, ntris, c, tid);
+    // once per workgroup: the triangle table (3 840 bytes, rows of 15) as 960 dwords, layout unchanged ...
+#if IVX_EMIT_TABLE_GLOBAL
+    const uint8_t *s_tri = &MC_TRI[0][0]; // (leave-out build: no copy, the table is read where it lies)
+#else
+    __shared__ __attribute__((aligned(16))) uint8_t s_tri[256 * 15];
+    // (three loads that every lane issues and a fourth by 192 lanes: under one condition each they wait for one another)
+    const uint32_t *tri32 = (const uint32_t *)&MC_TRI[0][0];
+    const uint32_t t0 = tri32[tid], t1 = tri32[256 + tid], t2 = tri32[512 + tid];
+    if (tid < 192) ((uint32_t *)s_tri)[768 + tid] = tri32[768 + tid];
+    ((uint32_t *)s_tri)[tid] = t0;
+    ((uint32_t *)s_tri)[256 + tid] = t1;
+    ((uint32_t *)s_tri)[512 + tid] = t2;
+#endif
+    // ... the per-edge constants: voxel offsets of the edge's two end points relative to the cell's corner (0,0,0) (dy runs
+    // against the source rows: the Y flip) and the end point / axis codes (|offset| <= ny*nx + nx + 1) ...
     const int plane32 = (int)(g.ny * g.nx), nx32 = (int)g.nx;
     if (tid < 12) {
         int ax, bx, by, bz;
@@ -730,29 +763,48 @@ __global__ __launch_bounds__(256) void k_mc_emit(const T *__restrict__ a, Geom g
         s_e1[tid] = o0 + (ax == 2 ? plane32 : (ax == 1 ? -nx32 : 1));
         s_ec[tid] = ax | (bx << 2) | (by << 3) | (bz << 4);
     }
-    const bool live = T_ < ntris;
-    const uint64_t d = live ? list[T_] : 0ull; // (a non-temporal load here measured the same)
+    if (LEVELS && tid < 4) s_tt[tid] = lv.tt[tid]; // ... and the four interpolation weights of the LEVELS form
     __syncthreads();
-    if (live) {
-        const int b = (int)(d >> 11) & 63, idx = (int)(d >> 3) & 255, rel = (int)d & 7;
-        const uint32_t w = (uint32_t)(d >> 17) & 0x7fffu;
-        const int32_t k = (int32_t)(d >> 48), j = (int32_t)((d >> 32) & 0xffffull);
-        mc_triangle<T, LEVELS>(a, g, lv, iso, s_tri, s_e0, s_e1, s_ec, k, j, (int32_t)w * 64 + b, idx, rel, s_out + tid * 9);
-    }
-    __syncthreads();
-    const uint32_t nt_chunk = ntris - T0 < 256 ? (uint32_t)(ntris - T0) : 256u;
-    float *dst = tris + T0 * 9;
-    if (nt_chunk == 256 && ((uintptr_t)tris & 15) == 0) { // a whole chunk (9 216 bytes, 16-byte aligned): 576 16-byte stores
-        typedef float float4_t __attribute__((ext_vector_type(4)));
-        float4_t *d4 = (float4_t *)dst;
-        const float4_t *s4 = (const float4_t *)s_out;
-        // non-temporal: the soup is written once and never read by the pipeline -- keeping it out of the L2 leaves the cache to the
-        // list and the planes (k_mc_list + k_mc_emit 120 -> 105 us on the bench surface, step 0.440 -> 0.419 ms)
-        __builtin_nontemporal_store(s4[tid], &d4[tid]);
-        __builtin_nontemporal_store(s4[tid + 256], &d4[tid + 256]);
-        if (tid < 64) __builtin_nontemporal_store(s4[tid + 512], &d4[tid + 512]);
-    } else {
-        for (uint32_t f = tid; f < nt_chunk * 9; f += 256) dst[f] = s_out[f];
+#if IVX_EMIT_NO_STORES
+    const bool stores = cap == ~0ull; // (leave-out build: no store runs, and the compiler cannot know it)
+#else
+    const bool stores = true;
+#endif
+    for (;;) {
+        const uint64_t T0 = c * 256;
+        if (T0 + tid < ntris) {
+            const int b = (int)(d >> 11) & 63, idx = (int)(d >> 3) & 255, rel = (int)d & 7;
+            const uint32_t w = (uint32_t)(d >> 17) & 0x7fffu;
+            const int32_t k = (int32_t)(d >> 48), j = (int32_t)((d >> 32) & 0xffffull);
+            mc_triangle<T, LEVELS, WIDE>(a, g, lv, T0 + tid < split ? iso0 : iso1, s_tri, s_e0, s_e1, s_ec, s_tt, k, j,
+                                         (int32_t)w * 64 + b, idx, rel, s_out + tid * 9);
+        }
+        // the next chunk's descriptors are asked for IN FRONT of this chunk's stores: a wave's loads and stores are counted in the
+        // order of their issue, so the wait for the descriptor leaves the stores in flight
+        const uint64_t dn = emit_desc(list, ntris, c + G, tid);
+        __syncthreads();
+        const uint32_t nt_chunk = ntris - T0 < 256 ? (uint32_t)(ntris - T0) : 256u;
+        float *dst = tris + T0 * 9;
+        if (!ALIGNED || nt_chunk < 256) {
+            if (stores)
+                for (uint32_t f = tid; f < nt_chunk * 9; f += 256) dst[f] = s_out[f];
+            // (a partial chunk is the list's last, and it leaves from inside its own branch: the waits of the ALIGNED loop
+            // then see no path without the whole chunk's stores)
+            if (ALIGNED) break;
+        } else if (stores) { // a whole chunk (9 216 bytes, 16-byte aligned): 576 16-byte stores
+            typedef float float4_t __attribute__((ext_vector_type(4)));
+            float4_t *d4 = (float4_t *)dst;
+            const float4_t *s4 = (const float4_t *)s_out;
+            // non-temporal: the soup is written once and never read by the pipeline -- keeping it out of the L2 leaves the cache to the
+            // list and the planes (k_mc_list + k_mc_emit 120 -> 105 us on the bench surface, step 0.440 -> 0.419 ms)
+            __builtin_nontemporal_store(s4[tid], &d4[tid]);
+            __builtin_nontemporal_store(s4[tid + 256], &d4[tid + 256]);
+            if (tid < 64) __builtin_nontemporal_store(s4[tid + 512], &d4[tid + 512]);
+        }
+        c += G;
+        if (c >= nchunks) break;
+        d = dn;
+        __syncthreads(); // (the staging buffer is read out: the next chunk may write it)
     }
 }
 
@@ -776,6 +828,52 @@ static int run_bits(const ivx_mc_params *p, const Geom &g, const Scratch &s, con
     return IVX_OK;
 }
 
+// The emit's grid for `chunks` chunks of capacity.  Resident workgroups -- as many as the chip holds at once: CUs x the occupancy
+// the runtime reports for this kernel, asked once (the devices of a process are alike) -- pay only where each gets many
+// chunks: at 94 per workgroup (1024^3 bench surface) the step is 3 % shorter than with one chunk per workgroup, at 12 (512^3)
+// the last, nearly empty pass of the static stride costs more than the tables staged once save (profiles/mc_emit_chunks_ab.md).
+// So: resident from EMIT_RESIDENT_MIN chunks per workgroup on, else one workgroup per chunk, which the dispatcher balances.
+// Two diagnostic switches, read at every call, neither changes a result: IVX_MC_EMIT_WGS=n caps the grid at n instead (1, 2 or
+// 3 let a small surface reach the loop's start, steady state and end in the tests; a large n gives one chunk per workgroup
+// for A/B), IVX_MC_EMIT_RESIDENT_MIN=m puts m in EMIT_RESIDENT_MIN's place (1: a test-sized surface with more chunks than the
+// chip holds workgroups takes the resident grid of the occupancy query).
+constexpr int64_t EMIT_RESIDENT_MIN = 32;
+template <typename T, bool LEVELS, bool ALIGNED, bool WIDE>
+static int emit_grid(int64_t chunks, unsigned *grid) {
+    static const int64_t resident = []() {
+        int dev = 0, cus = 0, per_cu = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_mc_emit<T, LEVELS, ALIGNED, WIDE>, 256, 0) != hipSuccess)
+            return (int64_t)0;
+        return (int64_t)cus * per_cu;
+    }();
+    IVX_REQUIRE(resident > 0, IVX_EHIP, "mc: the runtime reports no occupancy for the emit kernel");
+    int64_t resident_min = EMIT_RESIDENT_MIN;
+    if (const char *e = getenv("IVX_MC_EMIT_RESIDENT_MIN"))
+        if (atoll(e) > 0) resident_min = atoll(e);
+    int64_t wgs = chunks >= resident_min * resident ? resident : chunks;
+    if (const char *e = getenv("IVX_MC_EMIT_WGS"))
+        if (atoll(e) > 0) wgs = atoll(e);
+    *grid = (unsigned)(chunks < wgs ? chunks : wgs);
+    return IVX_OK;
+}
+
+template <typename T, bool LEVELS, bool ALIGNED, bool WIDE>
+static int launch_emit(const ivx_mc_params *p, const Geom &g, const Scratch &s, const void *a, const uint64_t *boff,
+                       const void *d_list, float *tris, int64_t max_tris, hipStream_t st, const McLevels &lv) {
+    unsigned grid;
+    int rc = emit_grid<T, LEVELS, ALIGNED, WIDE>(ivx::cdiv(max_tris, (int64_t)256), &grid);
+    if (rc) return rc;
+    // iso 1's triangles follow iso 0's: boff is one scan over [iso0 blocks | iso1 blocks], so both list passes write
+    // disjoint ranges of ONE list and one flat emit covers all of it; the kernel reads the total (boff[nb]) and the
+    // iso-0 / iso-1 split (boff[nblocks]) on the device
+    const size_t nb = s.nblocks * (size_t)p->niso;
+    hipLaunchKernelGGL((k_mc_emit<T, LEVELS, ALIGNED, WIDE>), dim3(grid), dim3(256), 0, st, (const T *)a, g, p->iso[0], p->iso[1],
+                       boff + (p->niso == 2 ? s.nblocks : nb), boff + nb, (const uint64_t *)d_list, (uint64_t)max_tris, tris, lv);
+    IVX_LAUNCH_CHECK();
+    return IVX_OK;
+}
+
 template <typename T>
 static int run_emit(const ivx_mc_params *p, const Geom &g, const Scratch &s, const void *a, const char *scratch,
                     float *tris, int64_t max_tris, hipStream_t st, const McLevels *lv) {
@@ -783,22 +881,24 @@ static int run_emit(const ivx_mc_params *p, const Geom &g, const Scratch &s, con
     void *d_list;
     int rc = ws_get_s(WS_MCLIST, st, (size_t)max_tris * 8 + 64, &d_list);
     if (rc) return rc;
-    // iso 1's triangles follow iso 0's: boff is one scan over [iso0 blocks | iso1 blocks], so both list passes write
-    // disjoint ranges of ONE list and one flat emit covers all of it; the kernel reads the total (boff[nb]) and the
-    // iso-0 / iso-1 split (boff[nblocks]) on the device
-    const size_t nb = s.nblocks * (size_t)p->niso;
     if (!mc_pieces().list_ready(scratch, d_list, max_tris)) // not built ahead by ivx_dev_mc_list
         if ((rc = mc_queue_list(p, g, s, scratch, d_list, max_tris, st))) return rc;
-    if (lv)
-        hipLaunchKernelGGL((k_mc_emit<T, true>), dim3((unsigned)ivx::cdiv(max_tris, (int64_t)256)), dim3(256), 0, st, (const T *)a, g,
-                           p->iso[0], p->iso[1], boff + (p->niso == 2 ? s.nblocks : nb), boff + nb, (const uint64_t *)d_list,
-                           (uint64_t)max_tris, tris, *lv);
-    else
-        hipLaunchKernelGGL((k_mc_emit<T, false>), dim3((unsigned)ivx::cdiv(max_tris, (int64_t)256)), dim3(256), 0, st, (const T *)a, g,
-                           p->iso[0], p->iso[1], boff + (p->niso == 2 ? s.nblocks : nb), boff + nb, (const uint64_t *)d_list,
-                           (uint64_t)max_tris, tris, McLevels{nullptr, 0.0, 0.0, 0.0, {0.0, 0.0, 0.0, 0.0}});
-    IVX_LAUNCH_CHECK();
-    return IVX_OK;
+    const bool aligned = ((uintptr_t)tris & 15) == 0; // (else every chunk takes the scalar copy-out)
+    if (lv) { // the mask's known levels: uint8 only (ivx_dev_mc_emit_levels)
+        if constexpr (std::is_same<T, uint8_t>::value) {
+            const bool wide = g.nz * g.ny * g.ws >= (1ll << 30); // 32-bit halves of the `sel` plane: 2^31 or more
+            if (wide)
+                return aligned ? launch_emit<T, true, true, true>(p, g, s, a, boff, d_list, tris, max_tris, st, *lv)
+                               : launch_emit<T, true, false, true>(p, g, s, a, boff, d_list, tris, max_tris, st, *lv);
+            return aligned ? launch_emit<T, true, true, false>(p, g, s, a, boff, d_list, tris, max_tris, st, *lv)
+                           : launch_emit<T, true, false, false>(p, g, s, a, boff, d_list, tris, max_tris, st, *lv);
+        } else {
+            IVX_REQUIRE(false, IVX_EINVAL, "mc: the levels form takes a uint8 mask");
+        }
+    }
+    const McLevels none{nullptr, 0.0, 0.0, 0.0, {0.0, 0.0, 0.0, 0.0}};
+    return aligned ? launch_emit<T, false, true, false>(p, g, s, a, boff, d_list, tris, max_tris, st, none)
+                   : launch_emit<T, false, false, false>(p, g, s, a, boff, d_list, tris, max_tris, st, none);
 }
 
 } // namespace
