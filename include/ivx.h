@@ -1342,6 +1342,52 @@ int ivx_mask_preview(const uint8_t *matrix, const int64_t shape[3], const int64_
                      const uint32_t *prefix, const ivx_volren_params *p, void *out, float *depth);
 
 /* ------------------------------------------------------------------------------------------------
+ * 3-D scene: the ray-cast field, the surfaces and the three slice planes in ONE picture, every surface and plane fragment
+ *   blended at its depth inside the field's front-to-back composite (the reference's 3-D viewer with
+ *   IntermixIntersectingGeometryOn, invesalius/data/volume.py:644, volume_mask.py:52, and viewer_volume.SlicePlane).
+ *   The contract is DESIGN.md section 7r (S1 - S3); PARITY UNPINNED vs VTK's renderer (not installable here).
+ * The field (field_kind): IVX_SCENE_FIELD_NONE; IVX_SCENE_FIELD_IMAGE, the prepared uint16 field and uint16 cells of
+ *   ivx_dev_volren_render (strides, apron, apron_value unused); IVX_SCENE_FIELD_MASK, the uint8 mask and uint8 cells of
+ *   ivx_dev_maskren_render's composite mode with its strides and apron (n_table >= 257, no clip plane, and `p->origin` moved
+ *   by (sx, -sy, sz) as there).  p->mip must be 0.  table / prefix as for those calls.
+ * The surfaces: `layers` with the keys of ivx_dev_surface_raster for `cam`, whose viewport must be p's.
+ * The planes: at most IVX_SCENE_MAX_PLANES, one per orientation; `picture` is dense RGB8 of h rows x w columns as
+ *   get_image_slice lays a slice out (AXIAL y x x, CORONAL z x x, SAGITAL z x y); the plane lies at image slice `slice` and is
+ *   cut to the rectangle of the voxel centres 0 .. w - 1, 0 .. h - 1; unlit, blended with `opacity`.
+ * ivx_dev_scene_render  device pointers (layers, cam, planes, p: host structs that hold device pointers); only enqueues.
+ *                       out: height x width x 4 float32, or uint8 with p->out_u8; stats as for ivx_dev_volren_render.
+ * ivx_scene_render      host form: `field` is the int16 image (shift, nsmooth as for ivx_volume_render) or the padded uint8
+ *                       matrix (as for ivx_mask_preview) with `strides`; the layers' arrays and the planes' pictures are host
+ *                       pointers (the layers' keys are ignored).  Uploads, prepares, builds the cells, rasters and renders.
+ * Errors (IVX_EINVAL): more than 8 layers, more than 3 planes or a repeated orientation, p->mip, a viewport of `cam` that is
+ *   not p's.
+ * ---------------------------------------------------------------------------------------------- */
+#define IVX_SCENE_FIELD_NONE 0
+#define IVX_SCENE_FIELD_IMAGE 1
+#define IVX_SCENE_FIELD_MASK 2
+#define IVX_SCENE_MAX_PLANES 3
+#define IVX_SCENE_AXIAL 0
+#define IVX_SCENE_CORONAL 1
+#define IVX_SCENE_SAGITAL 2
+typedef struct ivx_scene_plane {
+    const uint8_t *picture; /* h x w x 3 bytes, dense */
+    int32_t h, w;
+    int32_t orientation; /* IVX_SCENE_AXIAL .. IVX_SCENE_SAGITAL */
+    int32_t slice;       /* image slice number n: world z = n sz / y = -n sy / x = n sx */
+    float opacity;
+    int32_t reserved;
+} ivx_scene_plane;
+int ivx_dev_scene_render(int field_kind, const void *field, const void *cells, const int64_t shape[3],
+                         const int64_t strides[3], int apron, int apron_value, const float *table, const uint32_t *prefix,
+                         const ivx_surface_layer *layers, int nlayers, const ivx_surface_camera *cam, int interpolation,
+                         const ivx_scene_plane *planes, int nplanes, const ivx_volren_params *p, void *out, uint64_t *stats,
+                         void *stream);
+int ivx_scene_render(int field_kind, const void *field, const int64_t shape[3], const int64_t strides[3], int shift,
+                     int nsmooth, const float *table, const uint32_t *prefix, const ivx_surface_layer *layers, int nlayers,
+                     const ivx_surface_camera *cam, int interpolation, const ivx_scene_plane *planes, int nplanes,
+                     const ivx_volren_params *p, void *out);
+
+/* ------------------------------------------------------------------------------------------------
  * slice display: window/level, colour tables, mask and aux overlays, blend -- one launch per picture
  *   replaces Slice.GetSlices (invesalius/data/slice_.py:746-830) with do_ww_wl, do_colour_image, do_colour_mask,
  *   do_custom_colour and do_blend (:1656-1695, :1771-1873).  The arithmetic of VTK's filters is stated as rules R1 - R7 in

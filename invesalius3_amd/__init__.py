@@ -13,6 +13,8 @@ Host-side mirror of the reference interface for that path and the stages next to
     invesalius3_amd.cursor             <-> invesalius/data/cursor_actors.py brush footprints, and the window a dab covers
     invesalius3_amd.surface_process    <-> invesalius/data/surface_process.py create_surface_piece, join_process_surface
     invesalius3_amd.surface            <-> invesalius/data/surface.py CreateSurfaceFromFile: STL / PLY / VTP import, welded on the GPU
+    invesalius3_amd.scene3d            <-> the 3-D viewer's one renderer: volume or mask preview, surfaces and viewer_volume.SlicePlane's
+                                           three planes in one picture, geometry intermixed at its depth
     invesalius3_amd.watershed_process  <-> invesalius/data/watershed_process.py do_watershed
     invesalius3_amd.project            <-> invesalius/project.py .inv3 container (read / write, no wx / VTK)
     invesalius3_amd.headless           command-line driver: project in -> mask / surface / measurements / STL out

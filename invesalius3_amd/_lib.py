@@ -136,6 +136,12 @@ def _declare(lib):
                        ("ivx_dev_surface_raster", [c_vp, c_i64, c_vp, c_i64, c_vp, ctypes.c_int, c_vp, c_vp]),
                        ("ivx_dev_surface_resolve", [c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
                        ("ivx_surface_render", [c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
+                       # the 3-D scene: field kind, field, cells, shape, strides, apron, apron value, table, prefix, layers, count,
+                       # camera, interpolation, planes, count, params, out, stats, stream; host form
+                       ("ivx_dev_scene_render", [ctypes.c_int, c_vp, c_vp, i64p, i64p, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, ctypes.c_int,
+                                                 c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
+                       ("ivx_scene_render", [ctypes.c_int, c_vp, i64p, i64p, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, ctypes.c_int, c_vp,
+                                             ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp]),
                        # the density measures: descriptors, count, points (host; device), count, records
                        ("ivx_dev_roi_density", [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
                        ("ivx_roi_density", [c_vp, c_i64, c_vp, c_i64, c_vp]),

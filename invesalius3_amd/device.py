@@ -376,6 +376,9 @@ class DeviceVolume:
             b._on_touch = None  # freeing is not "somebody looked at the contents"
         self._drop_volren(all_buffers=True)
         self._drop_maskren()
+        if getattr(self, "_scene3d", None) is not None:
+            self._scene3d[1].close()
+            self._scene3d = None
         for b in (self.image, self.mask, self.out_mask, self.cand, self.reached, self._mbits, self.flood_scratch,
                   self._mc_scratch, self._tris, self._verts, self._faces, self._gate, getattr(self, "_range_buf", None),
                   getattr(self, "_ranges", None),
@@ -1630,6 +1633,23 @@ class DeviceVolume:
                     "render_mask_preview")
 
         return self._render("_mp", cam["viewport"], rgba8, depth, download, launch)
+
+    def render_scene(self, camera, size, surfaces=None, planes=(), **kw):
+        """The 3-D view with everything in it (scene3d.Scene3D.render): the resident image under a composite
+        `preset=` or the resident mask in `mask_colour=`, with `surfaces` (a surface_view.Scene or SurfaceActors) and `planes`
+        (scene3d.SlicePlanes) blended at their depths.  The scene is kept for the next call with the same `surfaces` object
+        and `planes`, so its key buffers and pictures stay resident."""
+        from . import scene3d as S3
+
+        sc = getattr(self, "_scene3d", None)
+        if sc is None or sc[0] is not surfaces:
+            if sc is not None:
+                sc[1].close()
+            sc = self._scene3d = (surfaces, S3.Scene3D(self, surfaces))
+        sc[1].planes = list(planes)
+        out = sc[1].render(camera, size, **kw)
+        self.last_render_stats = sc[1].last_render_stats if kw.get("download", True) else self.last_render_stats
+        return out
 
     def volume_histogram(self) -> np.ndarray:
         """CalculateHistogram (volume.py:723-735) of the resident image: uint64 counts of the int(max - min) unit bins

@@ -163,7 +163,7 @@ def run(args) -> dict:
         with vol.timer.span("surface"):
             nv, nt = vol.marching_cubes_indexed(from_binary=True, fill_border_holes=True)
         verts_buf, faces_buf = vol._verts, vol._faces
-        _surface_tail(args, lib, out, verts_buf, faces_buf, nv, nt, vol.stream, vol.timer, vol.sync, (vol.shape, vol.spacing))
+        _surface_tail(args, lib, out, verts_buf, faces_buf, nv, nt, vol.stream, vol.timer, vol.sync, (vol.shape, vol.spacing), vol, proj)
         if args.save:
             rec = prj.new_mask(proj, args.mask_name, (lo, hi))
             rec.matrix[1:, 1:, 1:] = mask
@@ -190,11 +190,11 @@ def run(args) -> dict:
     return out
 
 
-def _surface_tail(args, lib, out, verts_buf, faces_buf, nv, nt, stream, timer, sync, geometry):
+def _surface_tail(args, lib, out, verts_buf, faces_buf, nv, nt, stream, timer, sync, geometry, vol=None, proj=None):
     """everything the driver does with a surface once it is resident (two device buffers, nv points, nt triangles): --largest,
-    --surface-seed, --remove-nonvisible, --smooth, the measures, --stl, --surface-png, --geodesic, --split.  The surface comes
-    from marching cubes on the mask or from --import-surface; `geometry`: the image's (shape, spacing) for the camera of
-    --surface-png, or None without an image"""
+    --surface-seed, --remove-nonvisible, --smooth, the measures, --stl, --surface-png, --scene-png, --geodesic, --split.  The
+    surface comes from marching cubes on the mask or from --import-surface; `geometry`: the image's (shape, spacing) for the
+    camera of --surface-png, or None without an image; `vol`, `proj`: the resident volume and the project of --scene-png"""
     out["surface"] = {"vertices": nv, "triangles": nt}
     keep_v = keep_f = None
     if args.largest and nt:
@@ -270,6 +270,37 @@ def _surface_tail(args, lib, out, verts_buf, faces_buf, nv, nt, stream, timer, s
         out["surface_view"] = {"png": args.surface_png, "view": args.view, "size": [w, h], "colour": list(args.surface_colour),
                                "transparency": args.surface_transparency, "interpolation": args.surface_interpolation,
                                "vertices": int(len(pv)), "triangles": int(len(pf))}
+    if getattr(args, "scene_png", None):
+        # the 3-D view with everything the run has in it: the ray-cast image of --render or the mask of
+        # --mask-preview composite, the final surface with the --surface-* options, and the slice planes of --slice-planes under
+        # --window, every fragment blended at its depth
+        from . import scene3d as S3
+        from . import surface_view as SV
+        from . import volume as V
+        if verts is None:
+            verts = verts_buf.download((nv, 3), np.float32)
+            faces = faces_buf.download((nt, 3), np.int32)
+        pv, pf, pn, _ = sp.point_normals(verts, faces)
+        w, h = args.size
+        actor = SV.SurfaceActor(pv, pf, pn, colour=args.surface_colour, transparency=args.surface_transparency)
+        planes = [S3.SlicePlane(o, n) for o, n in zip(("AXIAL", "CORONAL", "SAGITAL"), args.slice_planes or ()) if n >= 0]
+        field = {}
+        if args.render is not None:
+            pdir = args.presets_dir
+            if pdir is None and args.render.endswith(".plist"):
+                pdir = os.path.dirname(os.path.abspath(args.render))
+            field = {"preset": args.render, "presets_dir": pdir}
+        elif args.mask_preview is not None:
+            field = {"mask_colour": args.mask_colour}
+        with S3.Scene3D(vol, [actor] if len(pf) else None, planes) as scene:
+            with timer.span("scene"):
+                rgba8 = scene.render(args.view, (w, h), interpolation=args.surface_interpolation, rgba8=True,
+                                     state=display_state(args, proj) if planes else None, **field)
+            stats = scene.last_render_stats
+        V.write_png(args.scene_png, rgba8)
+        out["scene"] = {"png": args.scene_png, "view": args.view, "size": [w, h], "field": "image" if args.render is not None else
+                        ("mask" if args.mask_preview is not None else None), "triangles": int(len(pf)),
+                        "planes": {p.orientation: p.n for p in planes}, **stats}
     if args.geodesic:
         # the measurement panel's geodesic measure (GeodesicMeasure._draw_line, measures.py:1202-1256) on the final surface
         from . import polydata_utils as pu
@@ -474,7 +505,8 @@ def _measure_only(args) -> bool:
     """the density flags without anything that asks for a mask, a surface or a picture: the numbers (and --save) are all"""
     return (args.threshold is None and args.segment is None and not args.seed and not args.stl and not args.largest and not args.smooth
             and not args.remove_nonvisible and not args.surface_seed and args.split is None and not getattr(args, "geodesic", None)
-            and getattr(args, "crop", None) is None and not getattr(args, "surface_png", None) and args.render is None
+            and getattr(args, "crop", None) is None and not getattr(args, "surface_png", None) and not getattr(args, "scene_png", None)
+            and args.render is None
             and args.mask_preview is None and args.show_slice is None and "--mask" not in (args.argv or []))
 
 
@@ -488,7 +520,7 @@ def _render_only(args) -> bool:
     return (args.threshold is None and args.segment is None and not args.seed and not args.stl and not args.save
             and not args.largest and not args.smooth and not args.remove_nonvisible and not args.surface_seed
             and args.split is None and not getattr(args, "geodesic", None) and getattr(args, "crop", None) is None
-            and not getattr(args, "surface_png", None) and "--mask" not in (args.argv or []))
+            and not getattr(args, "surface_png", None) and not getattr(args, "scene_png", None) and "--mask" not in (args.argv or []))
 
 
 def _strct(conn: int) -> np.ndarray:
@@ -631,6 +663,12 @@ def main(argv=None) -> int:
     ap.add_argument("--surface-png", metavar="OUT", default=None,
                     help="write a shaded picture of the final surface (after --largest / --surface-seed / --remove-nonvisible / "
                          "--smooth) as an RGBA PNG, from --view at --size with the camera of the image: it overlays --render")
+    ap.add_argument("--scene-png", metavar="OUT", default=None,
+                    help="write the 3-D view with everything in it as an RGBA PNG: the image of --render or the mask of --mask-preview "
+                         "composite, the final surface (--surface-colour, --surface-transparency, --surface-interpolation) and the "
+                         "planes of --slice-planes, each blended at its depth (--view, --size)")
+    ap.add_argument("--slice-planes", nargs=3, type=int, metavar=("AXIAL_N", "CORONAL_N", "SAGITAL_N"), default=None,
+                    help="the slice planes of --scene-png at these slice numbers (-1: off), shown under --window")
     ap.add_argument("--surface-colour", nargs=3, type=float, metavar=("R", "G", "B"), default=(0.33, 1.0, 0.33),
                     help="the surface's colour, 0..1 each (default: the reference's first surface colour)")
     ap.add_argument("--surface-transparency", type=float, default=0.0, metavar="T", help="the surface's transparency, 0..1 (default 0)")
@@ -652,7 +690,7 @@ def main(argv=None) -> int:
         if args.threshold is not None or args.segment is not None or "--mask" in args.argv or args.seed:
             ap.error("--import-surface takes the place of --threshold / --segment / --mask / --seed: name one source of the surface")
         image_flags = ("filter", "render", "mask_preview", "show_slice", "save", "crop", "cut_polygon", "brush3d", "flip", "swap_axes",
-                       "gantry_tilt", "density_ellipse", "density_polygon", "remeasure")
+                       "gantry_tilt", "density_ellipse", "density_polygon", "remeasure", "scene_png")
         given = [f for f in image_flags if getattr(args, f, None)]
         if given:
             ap.error("--import-surface works on the surface alone: --%s needs the image or the mask" % given[0].replace("_", "-"))
@@ -729,6 +767,19 @@ def main(argv=None) -> int:
             ap.error("--size W H must be positive")
         if not all(0.0 <= c <= 1.0 for c in args.surface_colour) or not 0.0 <= args.surface_transparency <= 1.0:
             ap.error("--surface-colour R G B and --surface-transparency T must lie in 0..1")
+    if args.scene_png is not None:
+        if args.project is None:
+            ap.error("--scene-png needs a project: the scene is seen with the camera of its image")
+        if args.size[0] <= 0 or args.size[1] <= 0:
+            ap.error("--size W H must be positive")
+        if args.mask_preview == "iso":
+            ap.error("--scene-png composes the composite mask preview (--mask-preview composite), not the iso mode")
+        if not all(0.0 <= c <= 1.0 for c in args.surface_colour) or not 0.0 <= args.surface_transparency <= 1.0:
+            ap.error("--surface-colour R G B and --surface-transparency T must lie in 0..1")
+        if args.window is not None and not args.window[0] > 0:
+            ap.error("--window WW WL: the width must be positive")
+    elif args.slice_planes is not None:
+        ap.error("--slice-planes needs --scene-png")
     if args.show_slice is not None:
         if args.show_slice[0].upper() not in ("AXIAL", "CORONAL", "SAGITAL") or not args.show_slice[1].lstrip("-").isdigit():
             ap.error("--show-slice takes AXIAL, CORONAL or SAGITAL and a slice number")
@@ -738,8 +789,8 @@ def main(argv=None) -> int:
             ap.error("--slab K must be positive")
         if args.window is not None and not args.window[0] > 0:
             ap.error("--window WW WL: the width must be positive")
-    elif args.window is not None or args.colour_table is not None or args.projection != "normal" or args.slab != 1:
-        ap.error("--window, --colour-table, --projection and --slab need --show-slice")
+    elif (args.window is not None and args.slice_planes is None) or args.colour_table is not None or args.projection != "normal" or args.slab != 1:
+        ap.error("--window, --colour-table, --projection and --slab need --show-slice (--window also serves --slice-planes)")
     print(json.dumps(run(args)))
     return 0
 

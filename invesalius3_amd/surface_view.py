@@ -215,21 +215,16 @@ class Scene:
             have = self._out[name] = DeviceBuffer(nbytes)
         return have
 
-    def render(self, camera="iso", size=(512, 512), shape=None, spacing=None, interpolation=SURFACE_INTERPOLATION,
-               background=(0.0, 0.0, 0.0), rgba8=False, depth=False, ids=False, download=True):
-        """The picture: float32 RGBA (H, W, 4), or uint8 with `rgba8`; with `depth` and / or `ids` a dict that also holds the
-        nearest fragment's float32 depth along the view direction (+inf where empty) and its int32 (surface, triangle) (-1
-        where empty; `surface` counts the VISIBLE actors in order).  With ``download=False`` the device buffers are returned
-        instead of arrays (they belong to the scene and are overwritten by its next render)."""
+    def raster(self, cam: dict):
+        """The key buffers of the visible surfaces for the camera dict `cam`, rastered where they are not already those of
+        this camera and mesh: (the C camera, the visible residents, the `SurfaceLayer` table with mesh, keys, colour and
+        opacity filled in).  What `render` and `scene3d.Scene3D.render` resolve."""
         lib = L.lib()
-        mode = _interpolation(interpolation)
         visible = [r for r in self._res if r.actor.visible]
         if len(visible) > MAX_SURFACES:
             raise TypeError("surface view: %d visible surfaces (at most %d)" % (len(visible), MAX_SURFACES))
-        cam = self.camera(camera, size, shape, spacing)
         cc = _c_camera(cam)
-        w, h = cc.width, cc.height
-        npix = w * h
+        npix = cc.width * cc.height
         layers = (SurfaceLayer * MAX_SURFACES)()
         self.last_stages = []
         for k, r in enumerate(visible):
@@ -253,6 +248,20 @@ class Scene:
             m.keys = r.keys.ptr
             m.rgb[:] = r.actor.colour
             m.opacity = 1.0 - r.actor.transparency
+        return cc, visible, layers
+
+    def render(self, camera="iso", size=(512, 512), shape=None, spacing=None, interpolation=SURFACE_INTERPOLATION,
+               background=(0.0, 0.0, 0.0), rgba8=False, depth=False, ids=False, download=True):
+        """The picture: float32 RGBA (H, W, 4), or uint8 with `rgba8`; with `depth` and / or `ids` a dict that also holds the
+        nearest fragment's float32 depth along the view direction (+inf where empty) and its int32 (surface, triangle) (-1
+        where empty; `surface` counts the VISIBLE actors in order).  With ``download=False`` the device buffers are returned
+        instead of arrays (they belong to the scene and are overwritten by its next render)."""
+        lib = L.lib()
+        mode = _interpolation(interpolation)
+        cam = self.camera(camera, size, shape, spacing)
+        cc, visible, layers = self.raster(cam)
+        w, h = cc.width, cc.height
+        npix = w * h
         pic = self._buffer("rgba8" if rgba8 else "rgba", npix * (4 if rgba8 else 16))
         d_ids, d_depth = self._buffer("ids", npix * 8), self._buffer("depth", npix * 4)  # always: pick reads them
         bg = (ctypes.c_float * 3)(*[float(x) for x in background])

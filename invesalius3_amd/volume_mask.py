@@ -58,7 +58,7 @@ def preview_setup(colour, mode: str = "composite") -> dict:
         "mapper": "vtkGPUVolumeRayCastMapper" if iso else "vtkFixedPointVolumeRayCastMapper",
         "blend": "iso_surface" if iso else "composite",
         "jitter": iso,  # UseJitteringOn: recorded, not restated
-        "intermix_geometry": not iso,  # IntermixIntersectingGeometryOn: no geometry here
+        "intermix_geometry": not iso,  # IntermixIntersectingGeometryOn: the geometry comes in through scene3d.Scene3D
         "iso_value": ISO_VALUE if iso else None,
         # pix_diag = 2.0: SetSampleDistance(pix_diag / 5.0), SetScalarOpacityUnitDistance(pix_diag); the image sample
         # distance is without effect, as for the image's volume
